@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """bench.py -- the ray-march hot path on N GPUs of one node (contract: see the task brief).
 
-    python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3                   (the headline line only)
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full            (+ every record beside it: roofline line counts, cold-device
+                                                                      timing, orbit, other kernels / configs / voxel types, CPU baselines)
+    python bench.py ... --dump-outputs DIR                           (+ the last timed frame as DIR/frame_rgba.npy, float32)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     python bench.py --gpus N ...        (no launcher: starts the N ranks itself, as a child torch.distributed.run, before any GPU call)
 
@@ -10,6 +13,9 @@ gather of RGBA8 bands to rank 0 when N > 1).  Inputs are resident in HBM before 
 region.  Workload at N = 1 is BASELINE.json configs[2] (C3): 1024^3 f32 volume, 1920x1080,
 step 1/512, RGBA transfer function, early-ray termination.  N > 1 scales the frame with N
 (weak scaling; N = 8 is configs[3] (C4): 3840x2160, step 1/1024).
+
+A plain run sets up, warms up (W warm-up frames after the spin-up frames described below), times the K steps, writes
+the outputs if asked and prints the line.  Everything else it can measure or check is behind --full.
 """
 import argparse
 import json
@@ -32,6 +38,7 @@ BRICK = 8                  # brick edge of the algorithmic-byte model (SURVEY 8d
 
 # frame / step per GPU count: per-GPU sample budget stays that of C3 (weak scaling)
 FRAMES = {1: (1920, 1080, 512), 2: (2716, 1528, 512), 4: (3840, 2160, 512), 8: (3840, 2160, 1024)}
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs writes at most this much
 
 
 def ramp_tf() -> np.ndarray:
@@ -85,6 +92,20 @@ def spawn_ranks(n: int) -> int:
     return subprocess.call(cmd, env=env)
 
 
+def dump_outputs(out_dir: str, frame: np.ndarray) -> None:
+    """--dump-outputs: the RGBA8 frame [H, W, 4] a caller of the timed path receives, as float32 (0 ... 255, exact).  A frame
+    above DUMP_MAX_BYTES (the multi-GPU frames) is written as a fixed, seeded sample of whole rows, with the row numbers beside it."""
+    os.makedirs(out_dir, exist_ok=True)
+    H, W, _ = frame.shape
+    if H * W * 4 * 4 <= DUMP_MAX_BYTES:
+        np.save(os.path.join(out_dir, "frame_rgba.npy"), frame.astype(np.float32))
+        return
+    nrows = (DUMP_MAX_BYTES - 8 * H) // (W * 4 * 4)
+    rows = np.sort(np.random.default_rng(0).choice(H, size=nrows, replace=False))
+    np.save(os.path.join(out_dir, "frame_rgba_row_sample.npy"), frame[rows].astype(np.float32))
+    np.save(os.path.join(out_dir, "frame_row_sample_index.npy"), rows.astype(np.float64))
+
+
 def workload(args, world):
     if args.config == "c3":
         n = 1024
@@ -105,7 +126,7 @@ def workload(args, world):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (frames)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="c3", choices=["c1", "c2", "c3", "c5"])
     ap.add_argument("--volume", default="noise", choices=["noise", "brain"])
@@ -121,7 +142,12 @@ def main():
     ap.add_argument("--frame-of", type=int, default=0, help="render the frame/step an N-GPU run would use (check aid)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
+    ap.add_argument("--full", action="store_true", help="also take every record beside the headline (roofline line counts, cold-device timing, "
+                                                        "orbit, other kernels / configurations / voxel types, CPU baselines, the multi-GPU gather check)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write the last timed step's frame to DIR/*.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -213,7 +239,7 @@ def main():
             ctx.load_volume_device(v32.data_ptr(), vv.VOXEL_F32, n, n, n, tf, stream)
     torch.cuda.synchronize()
     host_vol = None
-    want_cpu = (not args.no_cpu_baseline) and rank == 0 and world == 1
+    want_cpu = args.full and (not args.no_cpu_baseline) and rank == 0 and world == 1
     if want_cpu and upload is None:
         host_vol = (v32 if args.voxel == "f32" else v8).cpu().numpy().reshape(n, n, n)
     del v32, v8
@@ -317,7 +343,7 @@ def main():
     if main_rays is not None:
         bytes_rank += 8 * W * rows_owned                   # the two texels each pixel's ray is read from
     try:
-        lines_main = line_bytes(cam, args.phong, main_rays) if world == 1 else None
+        lines_main = line_bytes(cam, args.phong, main_rays) if (world == 1 and args.full) else None
     except Exception as e:                      # an instrument beside the metric: never at its cost
         lines_main = {"error": f"{type(e).__name__}: {e}"}
     if os.environ.get("VV_STATS"):      # developer statistics from a counters-only frame (no brick marking)
@@ -334,8 +360,8 @@ def main():
     #      its steady state (MI355X, C3: frames 1-25 after the set-up take 1.05 ms, from about frame 50 on 1.00 ms --
     #      power state and translation caches; measured with --warmup 3 / 50 / 300).  A renderer runs in that steady state;
     #      the timed region is still exactly K complete frames.  VV_BENCH_SPINUP=0 disables it. ----
-    # The same K frames are first timed WITHOUT it (after the W warm-up steps only: what a driver calling `--warmup 5` would
-    # see from a cold device) and reported as `ms_per_step_first` / `roofline.frac_first`, so both readings are on record.
+    # With --full the same K frames are first timed WITHOUT it (after the W warm-up steps only: what a driver calling `--warmup 5`
+    # would see from a cold device) and reported as `ms_per_step_first` / `roofline.frac_first`, so both readings are on record.
     spinup = int(os.environ.get("VV_BENCH_SPINUP", "300"))
     cold_ms = None
     # One GPU: the K frames are timed by ONE pair of HIP events around the region (on the stream the kernels are launched on), and vv_render's own
@@ -343,6 +369,7 @@ def main():
     # N > 1 keeps a pair per frame (the ranks' kernel times are reported one by one).
     if world == 1:
         ctx.set_frame_timing(False)
+    if world == 1 and args.full:
         for _ in range(args.warmup):
             ctx.render_device(W, H, cam, G.frames[0].data_ptr(), options=opts, stream=stream, phong=args.phong, rays=main_rays)
         ce0, ce1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -387,10 +414,12 @@ def main():
         dist.barrier()
     t1 = time.perf_counter()
     frame = G.frames[(args.steps - 1) & 1]
-    # N > 1: the gathered frame is checked (untimed) against the same frame rendered unsharded on rank 0 -- a throughput
+    if args.dump_outputs and rank == 0:         # before anything below renders into `frame` again
+        dump_outputs(args.dump_outputs, frame[:H].cpu().numpy())
+    # N > 1 with --full: the gathered frame is checked (untimed) against the same frame rendered unsharded on rank 0 -- a throughput
     # number from a gather that scrambled or dropped bands would be worthless
-    gather_check = "n/a (single GPU)"
-    if world > 1 and rank == 0:
+    gather_check = "n/a (single GPU)" if world == 1 else "not run (--full)"
+    if world > 1 and rank == 0 and args.full:
         whole = torch.full_like(frame, 0)
         whole.copy_(frame)                                  # pixels the frame never writes (column W-1, row H-1) compare equal
         wo = vv.make_options(**{k: v for k, v in base.items() if k != "shard"})
@@ -447,8 +476,8 @@ def main():
         "roofline": {"bound": "hbm", "kernel": ("march_phong_kernel" if args.phong else "march_kernel (+rad_kernel)"), "achieved": round(achieved / 1e9, 1),
                      "peak": HBM_PEAK / 1e9, "unit": "GB/s", "frac": round(achieved / HBM_PEAK, 4),
                      "frac_first": None if cold_ms is None else round(bytes_rank / (cold_ms * 1e-3) / HBM_PEAK, 4),
-                     "protocol": f"frac: {args.steps} frames after {spinup} untimed spin-up frames + {args.warmup} warm-up (steady state); "
-                                 f"frac_first: the {args.steps} frames right after the {args.warmup} warm-up frames (device still ramping up)",
+                     "protocol": f"frac: {args.steps} frames after {spinup} untimed spin-up frames + {args.warmup} warm-up (steady state)"
+                                 + ("" if cold_ms is None else f"; frac_first: the {args.steps} frames right after the {args.warmup} warm-up frames (device still ramping up)"),
                      "traffic": traffic, "algorithmic_bytes_per_launch": int(bytes_rank),
                      "bytes_per_sample": round(bytes_rank / max(samples, 1), 3)},
     }
@@ -472,7 +501,7 @@ def main():
     # Not part of `value`: the other shipped march kernels on the same workload, each with its own algorithmic bytes
     # (instrumented, untimed pass) and roofline fraction: the camera off the memory axis (SURVEY 8d's second camera:
     # vv_render samples the bricked copy) and the Phong-shaded frame (march_phong_kernel).
-    plain_c3 = world == 1 and args.config == "c3" and args.view == "a" and not args.orbit and not args.phong and args.voxel == "f32" and main_rays is None and not args.size
+    plain_c3 = args.full and world == 1 and args.config == "c3" and args.view == "a" and not args.orbit and not args.phong and args.voxel == "f32" and main_rays is None and not args.size
     if plain_c3 and not os.environ.get("VV_BENCH_NO_EXTRA"):
         def timed(camera, phong, reps=20, rays=None):
             for _ in range(60):           # steady state on the other layout / kernel (see the spin-up above)

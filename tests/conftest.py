@@ -29,8 +29,6 @@ def _built():
         subprocess.check_call(["make", "-C", os.path.join(REPO, "oracle")], stdout=subprocess.DEVNULL)
     if not os.path.exists(os.path.join(REPO, "volume-viz_amd", "lib", "libvolviz_hip.so")):
         subprocess.check_call(["make", "-C", os.path.join(REPO, "volume-viz_amd")], stdout=subprocess.DEVNULL)
-    if os.path.isdir("/root/reference") and not os.path.exists(os.path.join(REPO, "oracle", "_ref", "libvvref.so")):
-        subprocess.call(["make", "-C", os.path.join(REPO, "oracle"), "ref"], stdout=subprocess.DEVNULL)
 
 
 @pytest.fixture(scope="session")

@@ -14,6 +14,8 @@ Sources of truth
   * brain_16.t3d                  written by the reference's VolumeGenerator::saveas_raw
   * slice_matrices.json           SliceWidget::getTransformationMatrix composition evaluated
                                   with the reference's compiled cs123math/CS123Matrix.cpp
+  * reference_checks.json         further outputs of the compiled reference (generator sizes,
+                                  cutting planes, .t3d read-back) that the CPU tests compare with
   * frames_oracle.npz             RGBA8 frames / slices rendered by the CPU oracle
                                   (oracle-derived regression pins; the reference has no
                                   golden images and kernel.cu cannot be built here)
@@ -87,6 +89,33 @@ def make_cut_planes(ref):
     json.dump(planes, open(os.path.join(HERE, "cut_planes_pro.json"), "w"), indent=1)
 
 
+def make_reference_checks(ref):
+    """reference_checks.json: what the compiled reference returns for the cases the CPU tests once asked it for directly
+    (tests/test_oracle.py, tests/test_host.py), so that those tests need nothing outside the repository:
+      * default_brain        sha256 of VolumeGenerator::drawDefaultBrain at a few odd sizes
+      * cut_planes_pro_wide  ref_cut_plane_pro on 300 seeded sliders (offsets in [-1, 1], angles in [-7, 7])
+      * load_raw_brain_16    VolumeGenerator::loadRawVolume (ref_load_raw) reading brain_16.t3d: voxel count, dims, sha256"""
+    brains = []
+    for nx, ny, nz in ((48, 48, 48), (31, 17, 5), (1, 1, 1), (100, 3, 2)):
+        r = np.zeros((nz, ny, nx), np.uint8)
+        ref.ref_default_brain(r.ctypes.data, nx, ny, nz)
+        brains.append(dict(dims=[nx, ny, nz], sha256=sha(r)))
+    rng = np.random.default_rng(2025)
+    planes = []
+    for _ in range(300):
+        p = [float(np.float32(v)) for v in np.concatenate([rng.uniform(-1, 1, 3), rng.uniform(-7, 7, 3)])]
+        pt = np.zeros(3, np.float32); n = np.zeros(3, np.float32)
+        ref.ref_cut_plane_pro(*p, pt.ctypes.data, n.ctypes.data)
+        planes.append(dict(params=p, point_hex=pt.tobytes().hex(), normal_hex=n.tobytes().hex()))
+    import ctypes as C
+    dims = (C.c_int * 3)()
+    out = np.zeros(16 ** 3, np.uint8)
+    count = ref.ref_load_raw(os.path.join(HERE, "brain_16.t3d").encode(), 1, out.ctypes.data, out.size, dims)
+    checks = dict(default_brain=brains, cut_planes_pro_wide=planes,
+                  load_raw_brain_16=dict(count=int(count), dims=list(dims), sha256=sha(out)))
+    json.dump(checks, open(os.path.join(HERE, "reference_checks.json"), "w"), indent=1)
+
+
 def main():
     if not os.path.isdir(REF):
         sys.exit(f"reference tree {REF} not present")
@@ -137,6 +166,7 @@ def main():
     json.dump(mats, open(os.path.join(HERE, "slice_matrices.json"), "w"), indent=1)
 
     make_cut_planes(ref)
+    make_reference_checks(ref)
 
     # --- oracle-rendered frames -----------------------------------------------------------
     vols = {"brain32": b32, "brain64": O.draw_default_brain(64, 64, 64)}
@@ -161,5 +191,7 @@ def main():
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "cut_planes":          # only the fixture added in round 5 (the others are unchanged)
         make_cut_planes(O.ref())
+    elif len(sys.argv) > 1 and sys.argv[1] == "reference_checks":  # only reference_checks.json
+        make_reference_checks(O.ref())
     else:
         main()

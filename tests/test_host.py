@@ -2,6 +2,7 @@
 include/volviz.h declares, and the host-only entry points agree with the golden vectors.
 No kernel is launched here."""
 import ctypes as C
+import hashlib
 import json
 import os
 import re
@@ -55,8 +56,8 @@ def test_slice_matrix_matches_reference(golden_dir):
 
 def test_cut_plane_from_euler_matches_reference(golden_dir):
     """vv_cut_plane_from_euler = the plane Window::renderSlice hands GLWidget::setSlicePro (window.cpp:425-443), bit for bit against planes
-    the compiled reference's own operators produced (tests/golden/cut_planes_pro.json, make_fixtures.py cut_planes), and -- where the
-    compiled reference is present -- against it directly on fresh random sliders."""
+    the compiled reference's own operators produced (tests/golden/cut_planes_pro.json, make_fixtures.py cut_planes), and on 300 seeded
+    random sliders over a wider angle range (tests/golden/reference_checks.json)."""
     for case in json.load(open(os.path.join(golden_dir, "cut_planes_pro.json"))):
         pt, n = vv.cut_plane_from_euler(*case["params"])
         assert pt.tobytes().hex() == case["point_hex"] and n.tobytes().hex() == case["normal_hex"], case["params"]
@@ -64,16 +65,11 @@ def test_cut_plane_from_euler_matches_reference(golden_dir):
     assert pt.tolist() == [0.5, 0.5, 0.5] and n.tolist() == [0.0, 0.0, 1.0]            # the sagittal plane through the centre
     pt, n = vv.cut_plane_from_euler(0.25, 0, 0, 0, float(np.float32(np.pi / 2)), 0)      # Ry(90 deg) turns +z into +x
     assert np.allclose(n, [1, 0, 0], atol=1e-6) and pt.tolist() == [0.75, 0.5, 0.5]
-    import oracle_lib as O                       # (only its loader of the compiled reference, oracle/_ref/libvvref.so)
-    ref = O.ref()
-    if ref is not None and hasattr(ref, "ref_cut_plane_pro"):
-        rng = np.random.default_rng(2025)
-        for _ in range(300):
-            p = [float(np.float32(v)) for v in np.concatenate([rng.uniform(-1, 1, 3), rng.uniform(-7, 7, 3)])]
-            rp = np.zeros(3, np.float32); rn = np.zeros(3, np.float32)
-            ref.ref_cut_plane_pro(*p, rp.ctypes.data, rn.ctypes.data)
-            pt, n = vv.cut_plane_from_euler(*p)
-            assert pt.tobytes() == rp.tobytes() and n.tobytes() == rn.tobytes(), p
+    wide = json.load(open(os.path.join(golden_dir, "reference_checks.json")))["cut_planes_pro_wide"]
+    assert len(wide) == 300
+    for case in wide:
+        pt, n = vv.cut_plane_from_euler(*case["params"])
+        assert pt.tobytes().hex() == case["point_hex"] and n.tobytes().hex() == case["normal_hex"], case["params"]
 
 
 def test_t3d_reads_reference_written_file(golden_dir, tmp_path):
@@ -96,12 +92,11 @@ def test_t3d_reads_reference_written_file(golden_dir, tmp_path):
     # errors are codes, never exit()
     assert lib.vv_t3d_read(b"/nonexistent/file.t3d", 1, buf.ctypes.data, buf.size) == -5
     assert lib.vv_t3d_read(p, 1, buf.ctypes.data, 10) == -1
-    if __import__("oracle_lib").ref() is not None:       # the reference reads back what we write
-        ref = __import__("oracle_lib").ref()
-        dims = (C.c_int * 3)()
-        out = np.zeros(16 ** 3, np.uint8)
-        assert ref.ref_load_raw(q, 1, out.ctypes.data, out.size, dims) == 16 ** 3
-        assert list(dims) == [16, 16, 16] and np.array_equal(out, buf)
+    # the reference reads back what we write: our file is byte-identical to brain_16.t3d, and what the reference's loader returned
+    # for that file is recorded in reference_checks.json
+    back = json.load(open(os.path.join(golden_dir, "reference_checks.json")))["load_raw_brain_16"]
+    assert back["count"] == 16 ** 3 and back["dims"] == [16, 16, 16]
+    assert hashlib.sha256(buf.tobytes()).hexdigest() == back["sha256"]
 
 
 def test_cut_plane_helpers():

@@ -177,3 +177,29 @@ def test_bench_reports_a_failed_rank():
 def test_bench_refuses_a_mismatched_launcher():
     r = _bench(["--gpus", "4"], {"VV_BENCH_DRYRUN": "1", "WORLD_SIZE": "2", "RANK": "0", "LOCAL_RANK": "0"})
     assert r.returncode != 0 and "--gpus 4" in (r.stderr + r.stdout)
+
+
+def test_bench_dump_outputs_format_and_cap(tmp_path):
+    """bench.py --dump-outputs: the frame as float32 [H, W, 4]; a frame above 64 MB (the multi-GPU frames) as a fixed, seeded sample of whole
+    rows, with the row numbers beside it, within the cap."""
+    import importlib.util
+    repo = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(repo, "bench.py"))
+    bench = importlib.util.module_from_spec(spec); spec.loader.exec_module(bench)
+    rng = np.random.default_rng(5)
+    small = rng.integers(0, 256, (1080, 1920, 4), dtype=np.uint8)
+    bench.dump_outputs(str(tmp_path / "a"), small)
+    got = np.load(tmp_path / "a" / "frame_rgba.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small)
+    big = rng.integers(0, 256, (2160, 3840, 4), dtype=np.uint8)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    files = sorted(os.listdir(tmp_path / "b"))
+    assert files == ["frame_rgba_row_sample.npy", "frame_row_sample_index.npy"]
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in files) <= bench.DUMP_MAX_BYTES
+    rows = np.load(tmp_path / "b" / "frame_row_sample_index.npy")
+    sample = np.load(tmp_path / "b" / "frame_rgba_row_sample.npy")
+    assert rows.dtype == np.float64 and sample.dtype == np.float32 and len(rows) > 1000
+    assert np.array_equal(sample, big[rows.astype(np.int64)])
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f))
