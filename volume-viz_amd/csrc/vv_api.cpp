@@ -37,6 +37,17 @@ struct vv_knobs {
     }
 };
 
+// The optional copies of the loaded volume, built on first use and dropped on reload: bricked (views off the memory axis),
+// z-pair (views along the memory axis), z-fastest (side views) and x-pair (side views of small / u8 volumes; built from the z-fastest copy).
+enum { CP_BRICKS = 0, CP_ZPAIR = 1, CP_ZFAST = 2, CP_XPAIR = 3, CP_N = 4 };
+struct layout_copy {
+    void *ptr = nullptr; size_t bytes = 0;
+    bool valid = false, failed = false;     // failed: not tried again until the next volume load (or an explicit vv_prepare_layouts)
+    unsigned long long last_used = 0;       // when a frame last sampled it (the least recently used copy is evicted first)
+    // what the sampler needs (VolumeView): bytes per row and per slab (pair copies), per row and per slice (z-fastest), per brick row and per brick layer / 64
+    uint32_t row = 0; uint64_t slab = 0;
+};
+
 struct vv_context {
     int device = 0;
     vv_knobs knobs;
@@ -46,16 +57,11 @@ struct vv_context {
     // volume
     void *d_vol = nullptr; size_t vol_bytes = 0; int vtype = VV_VOXEL_U8; int nx = 0, ny = 0, nz = 0;
     size_t row_pitch = 0, slice_pitch = 0, alloc_bytes = 0;   // linear layout in HBM (bytes); vol_bytes stays nx*ny*nz*voxel
-    // bricked copy of an f32 volume for views off the memory axis (built on first use, dropped on reload)
-    void *d_bricks = nullptr; bool bricks_valid = false, bricks_failed = false; uint32_t b_sy = 0, b_sz64 = 0; size_t bricks_bytes = 0;
-    // z-pair copy of an f32 volume for views along the memory axis (same life cycle)
-    void *d_zpair = nullptr; bool zpair_valid = false; uint32_t zp_row = 0, zp_slab = 0; size_t zpair_bytes = 0;
-    void *d_zfast = nullptr; bool zfast_valid = false, zfast_failed = false; uint32_t zf_row = 0; uint64_t zf_slice = 0; size_t zfast_bytes = 0;   // z-fastest copy (side views)
-    void *d_xpair = nullptr; bool xpair_valid = false, xpair_failed = false; uint32_t xp_row = 0, xp_slab = 0; size_t xpair_bytes = 0;           // x-pair copy (side views of small / u8 volumes)
-    // residency policy of the optional copies (vv_set_layout_policy): HBM budget for all of them together (0 = default, layout_budget()),
-    // whether vv_render may build a missing copy by itself, and when each copy was last sampled (the least recently used one goes first)
+    layout_copy copies[CP_N];
+    // residency policy of the optional copies (vv_set_layout_policy): HBM budget for all of them together (0 = default, layout_budget())
+    // and whether vv_render may build a missing copy by itself
     size_t layout_budget_bytes = 0; bool build_in_render = true;
-    unsigned long long frame_no = 0, last_used[4] = {0, 0, 0, 0};          // CP_BRICKS, CP_ZPAIR, CP_ZFAST, CP_XPAIR
+    unsigned long long frame_no = 0;                                          // the clock of layout_copy::last_used
     unsigned long long builds_in_render = 0;                                  // copies built inside vv_render since the volume was loaded
     float last_density = 1e9f;                                                // what the launch policy took the last frame's sampling density to be
     // transfer function
@@ -103,17 +109,12 @@ static inline hipStream_t pick_stream(const vv_context *c, void *stream)
     return (hipStream_t)stream;
 }
 
-static void drop_bricks(vv_context *c)
+static void drop_copies(vv_context *c)
 {
-    if (c->d_bricks) (void)hipFree(c->d_bricks);
-    c->d_bricks = nullptr; c->bricks_valid = false; c->bricks_failed = false; c->bricks_bytes = 0;
-    if (c->d_zpair) (void)hipFree(c->d_zpair);
-    c->d_zpair = nullptr; c->zpair_valid = false; c->zpair_bytes = 0;
-    if (c->d_zfast) (void)hipFree(c->d_zfast);
-    c->d_zfast = nullptr; c->zfast_valid = false; c->zfast_failed = false; c->zfast_bytes = 0;
-    if (c->d_xpair) (void)hipFree(c->d_xpair);
-    c->d_xpair = nullptr; c->xpair_valid = false; c->xpair_failed = false; c->xpair_bytes = 0;
-    for (int k = 0; k < 4; ++k) c->last_used[k] = 0;
+    for (layout_copy &cp : c->copies) {
+        if (cp.ptr) (void)hipFree(cp.ptr);
+        cp = layout_copy();
+    }
     c->builds_in_render = 0;
     c->view_key_valid = false;             // (a new volume: the launch-policy estimate taken from first-pass images is re-taken)
 }
@@ -178,31 +179,23 @@ static bool estimate_view_from_images(const uint8_t *front, const uint8_t *back,
     *px_cube = len / (float)(b - a);
     return true;
 }
-static bool ensure_bricks(vv_context *c, hipStream_t st);
-static bool ensure_zpair(vv_context *c, hipStream_t st);
-static bool ensure_zfast(vv_context *c, hipStream_t st);
-static bool ensure_xpair(vv_context *c, hipStream_t st);
 
 // ---- residency of the optional copies -----------------------------------------------------------------------------------------
 // All copies of a volume together stay within a budget (default: the larger of 8 GiB and 2.5 x the linear volume -- room for the bricked and the
 // z-fastest copy of an f32 volume, C3: 9.7 GB of copies beside the 4.3 GB volume, C5: 72 GiB beside 32 GiB; every copy of a u8 volume up to 1 GiB).
 // A copy that would not fit evicts copies no frame has sampled more recently (least recently used first); if that is not enough it is not built
 // and the frame takes the next layout of the policy.  Results never depend on any of this.
-enum { CP_BRICKS = 0, CP_ZPAIR = 1, CP_ZFAST = 2, CP_XPAIR = 3, CP_N = 4 };
 static size_t layout_budget(const vv_context *c)
 {
     if (c->layout_budget_bytes) return c->layout_budget_bytes;
     return std::max<size_t>((size_t)8 << 30, c->alloc_bytes / 2 * 5);
 }
-static bool copy_valid(const vv_context *c, int k) { return k == CP_BRICKS ? c->bricks_valid : k == CP_ZPAIR ? c->zpair_valid : k == CP_ZFAST ? c->zfast_valid : c->xpair_valid; }
-static size_t copy_bytes(const vv_context *c, int k) { return !copy_valid(c, k) ? 0 : k == CP_BRICKS ? c->bricks_bytes : k == CP_ZPAIR ? c->zpair_bytes : k == CP_ZFAST ? c->zfast_bytes : c->xpair_bytes; }
+static size_t copy_bytes(const vv_context *c, int k) { return c->copies[k].valid ? c->copies[k].bytes : 0; }
 static void copy_drop(vv_context *c, int k)
 {
-    void **p = k == CP_BRICKS ? &c->d_bricks : k == CP_ZPAIR ? &c->d_zpair : k == CP_ZFAST ? &c->d_zfast : &c->d_xpair;
-    if (*p) (void)hipFree(*p);                       // (hipFree waits for the device: frames still in flight on a caller's stream have finished with it)
-    *p = nullptr;
-    if (k == CP_BRICKS) { c->bricks_valid = false; c->bricks_bytes = 0; } else if (k == CP_ZPAIR) { c->zpair_valid = false; c->zpair_bytes = 0; }
-    else if (k == CP_ZFAST) { c->zfast_valid = false; c->zfast_bytes = 0; } else { c->xpair_valid = false; c->xpair_bytes = 0; }
+    layout_copy &cp = c->copies[k];
+    if (cp.ptr) (void)hipFree(cp.ptr);               // (hipFree waits for the device: frames still in flight on a caller's stream have finished with it)
+    cp.ptr = nullptr; cp.valid = false; cp.bytes = 0;
 }
 // Room for `need` more bytes of copies?  `keep`: bit mask of copies that must stay (the ones the frame being set up samples or builds from).
 static bool make_room(vv_context *c, size_t need, unsigned keep)
@@ -215,12 +208,114 @@ static bool make_room(vv_context *c, size_t need, unsigned keep)
         if (used + need <= budget) return true;
         int victim = -1;
         for (int k = 0; k < CP_N; ++k)
-            if (copy_valid(c, k) && !(keep & (1u << k)) && (victim < 0 || c->last_used[k] < c->last_used[victim])) victim = k;
+            if (c->copies[k].valid && !(keep & (1u << k)) && (victim < 0 || c->copies[k].last_used < c->copies[victim].last_used)) victim = k;
         if (victim < 0) return false;
         copy_drop(c, victim);
     }
 }
 
+// Copy k could not be built.  Remembered until the next volume load, except for the z-pair copy, which is tried again at every request.
+static bool copy_refused(vv_context *c, int k)
+{
+    if (k != CP_ZPAIR) c->copies[k].failed = true;
+    return false;
+}
+
+// Builds copy k: `bytes` of it (what the budget counts) and `pad` more bytes of allocation, [zero_from, bytes + pad) zeroed, then `build(ptr)`,
+// provided it fits the budget (evicting copies not in `keep`) and leaves 512 MiB of HBM free.  Waits for the build: later frames may come on
+// another stream.  (The build kernels write [0, bytes) only: the zeros may go first.)
+template <class Build>
+static bool build_copy(vv_context *c, int k, size_t bytes, size_t pad, size_t zero_from, unsigned keep, hipStream_t st, Build build)
+{
+    layout_copy &cp = c->copies[k];
+    size_t free_b = 0, total_b = 0;
+    if (make_room(c, bytes, keep | (1u << k)) && hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b >= bytes + (512ull << 20) &&
+        hipMalloc(&cp.ptr, bytes + pad) == hipSuccess) {
+        if (hipMemsetAsync((char *)cp.ptr + zero_from, 0, bytes + pad - zero_from, st) == hipSuccess) {
+            build(cp.ptr);
+            if (hipGetLastError() == hipSuccess && hipStreamSynchronize(st) == hipSuccess) { cp.bytes = bytes; cp.valid = true; return true; }
+        }
+        (void)hipFree(cp.ptr);
+    }
+    (void)hipGetLastError();
+    cp.ptr = nullptr;
+    return copy_refused(c, k);
+}
+
+// The copies' sizes, geometry, addressing limits and build kernels.  Each returns true when its copy is usable afterwards; a copy the limits rule
+// out is refused before anything is evicted for it, and the frame takes the next layout of the policy.  
+static bool ensure_bricks(vv_context *c, hipStream_t st)
+{
+    layout_copy &cp = c->copies[CP_BRICKS];
+    if (cp.valid || cp.failed) return cp.valid;
+    uint32_t sy = 0, sz64 = 0;
+    const size_t bytes = brick_copy_bytes(c->vtype, c->nx, c->ny, c->nz, &sy, &sz64);
+    if (sz64 >= (1u << 24) || sy >= (1u << 24)) return copy_refused(c, CP_BRICKS);          // (the sampler multiplies b_sy and b_sz64 as 24-bit values)
+    cp.row = sy; cp.slab = sz64;
+    return build_copy(c, CP_BRICKS, bytes, 16, bytes, 0, st, [&](void *p) {
+        launch_build_bricks(c->vtype, c->d_vol, c->row_pitch, c->slice_pitch, p, c->nx, c->ny, c->nz, st); });
+}
+
+static bool ensure_zpair(vv_context *c, hipStream_t st)
+{
+    layout_copy &cp = c->copies[CP_ZPAIR];
+    if (cp.valid) return true;
+    uint32_t rb = 0, sb = 0;
+    const size_t bytes = zpair_copy_bytes(c->vtype, c->nx, c->ny, c->nz, &rb, &sb);
+    if ((size_t)(c->ny + 1) * ((size_t)c->nx + 1) * 8 >= (1ull << 32) || ((size_t)c->nx + 1) * 8 >= (1u << 24) ||
+        (c->vtype == VV_VOXEL_U8 && bytes >= (1ull << 32)))                // u8 sampler: 32-bit offsets
+        return copy_refused(c, CP_ZPAIR);
+    cp.row = rb; cp.slab = sb;
+    return build_copy(c, CP_ZPAIR, bytes, 32, bytes, 0, st, [&](void *p) {
+        launch_build_zpair(c->vtype, c->d_vol, c->row_pitch, c->slice_pitch, p, c->nx, c->ny, c->nz, st); });
+}
+
+// The z-fastest copy of the volume (VolumeView::zfast): rows of nz voxels padded like the linear layout's rows (finalize_layout),
+// ny rows per slice, nx slices + one slice, one row and 16 bytes of zeros behind them (the weight-0 corners of edge samples).
+static bool ensure_zfast(vv_context *c, hipStream_t st)
+{
+    layout_copy &cp = c->copies[CP_ZFAST];
+    if (cp.valid || cp.failed) return cp.valid;
+    const size_t vsz = c->vtype == VV_VOXEL_F32 ? 4 : 1;
+    size_t row = (size_t)c->nz * vsz;
+    if (row % 1024 == 0) row += 32;
+    else if (vsz == 1) row = (row + 3) & ~(size_t)3;                       // (u8 rows are read as aligned dwords)
+    size_t rows = (size_t)c->ny;
+    if (row % 1024 == 32 && (rows * row) % 4096 == 0) rows += 1;
+    const size_t slice = rows * row, bytes = slice * ((size_t)c->nx + 1) + row + 16;
+    if (c->ny > 65535 || (c->nz + 31) / 32 > 65535 || row >= (1u << 24) || slice >= (1ull << 32))     // (launch_build_zfast: one grid layer per row)
+        return copy_refused(c, CP_ZFAST);                                   // the bricked copy serves the view
+    cp.row = (uint32_t)row; cp.slab = slice;
+    return build_copy(c, CP_ZFAST, bytes, 0, 0, 0, st, [&](void *p) {     // (zeroed whole: the padding of every row too)
+        launch_build_zfast(c->vtype, c->d_vol, (uint32_t)c->row_pitch, (uint64_t)c->slice_pitch, p, (uint32_t)row, (uint64_t)slice, c->nx, c->ny, c->nz, st); });
+}
+
+// The x-pair copy (the z-pair copy with x and z exchanged; built from the z-fastest copy): the limits of ensure_zpair with the roles swapped.
+static bool ensure_xpair(vv_context *c, hipStream_t st)
+{
+    layout_copy &cp = c->copies[CP_XPAIR];
+    if (cp.valid || cp.failed) return cp.valid;
+    if (!ensure_zfast(c, st)) return false;
+    uint32_t rb = 0, sb = 0;
+    const size_t bytes = zpair_copy_bytes(c->vtype, c->nz, c->ny, c->nx, &rb, &sb);
+    if ((size_t)(c->ny + 1) * ((size_t)c->nz + 1) * 8 >= (1ull << 32) || ((size_t)c->nz + 1) * 8 >= (1u << 24) ||
+        (c->vtype == VV_VOXEL_U8 && bytes >= (1ull << 32)))                // u8 sampler: 32-bit offsets
+        return copy_refused(c, CP_XPAIR);
+    cp.row = rb; cp.slab = sb;
+    const layout_copy &zf = c->copies[CP_ZFAST];
+    return build_copy(c, CP_XPAIR, bytes, 32, bytes, 1u << CP_ZFAST, st, [&](void *p) {
+        launch_build_xpair(c->vtype, zf.ptr, zf.row, zf.slab, p, c->nx, c->ny, c->nz, st); });
+}
+
+static bool (*const ensure_copy[CP_N])(vv_context *, hipStream_t) = {ensure_bricks, ensure_zpair, ensure_zfast, ensure_xpair};   // indexed by CP_*
+
+// Can the frame being set up (c->frame_no) sample copy k?  Resident, or built now if vv_render may build copies.  If so it counts as used by the frame.
+static bool take_copy(vv_context *c, int k, hipStream_t st)
+{
+    if (!(c->build_in_render ? ensure_copy[k](c, st) : c->copies[k].valid)) return false;
+    c->copies[k].last_used = c->frame_no;
+    return true;
+}
 
 extern "C" {
 
@@ -257,7 +352,7 @@ int vv_shutdown(vv_context *c)
     hipSetDevice(c->device);
     hipStreamSynchronize(c->stream);
     if (c->d_vol) hipFree(c->d_vol);
-    drop_bricks(c);
+    drop_copies(c);
     if (c->d_tf) hipFree(c->d_tf);
     if (c->d_rad) hipFree(c->d_rad);
     if (c->d_order) hipFree(c->d_order);
@@ -316,10 +411,10 @@ static int install_volume(vv_context *c, const void *src, bool src_on_device, in
     // one slice + one row + 16 bytes of zero padding: weight-0 corner fetches of edge
     // samples land here instead of needing index clamps (see vv_device.h VolumeView)
     const size_t pad = (size_t)nx * ny * vsz + 2 * (size_t)nx * vsz + 4096;
-    drop_bricks(c);
+    drop_copies(c);
     if (c->d_vol) { HIPCHK(c, hipFree(c->d_vol)); c->d_vol = nullptr; }   // the reference leaks here
     HIPCHK(c, hipMalloc(&c->d_vol, bytes + pad));
-    hipStream_t st = s ? (s == (hipStream_t)VV_STREAM_DEFAULT_ASYNC ? (hipStream_t)0 : s) : c->stream;
+    hipStream_t st = pick_stream(c, s);
     HIPCHK(c, hipMemsetAsync((char *)c->d_vol + bytes, 0, pad, st));
     if (src_on_device) HIPCHK(c, hipMemcpyAsync(c->d_vol, src, bytes, hipMemcpyDeviceToDevice, st));
     else { HIPCHK(c, hipMemcpyAsync(c->d_vol, src, bytes, hipMemcpyHostToDevice, st)); }
@@ -346,8 +441,6 @@ int vv_load_volume_device(vv_context *c, const void *dev, int vtype, int nx, int
     return install_volume(c, dev, true, vtype, nx, ny, nz, tf, (hipStream_t)stream);
 }
 
-// developer statistics of the last instrumented launch (staged kernel): [0] executed samples,
-// [1] stages, [2] samples served from global memory, [3] bytes staged into LDS, [4] wave compute trips
 int vv_prepare_layouts(vv_context *c, int which, void *stream)
 {
     if (!c) return fail(nullptr, VV_ERR_INVALID, "vv_prepare_layouts: NULL context");
@@ -362,16 +455,21 @@ int vv_prepare_layouts(vv_context *c, int which, void *stream)
         if (pair_ok) which |= VV_LAYOUT_ZPAIR;
     }
     int built = 0;
-    if (which & VV_LAYOUT_BRICKED) c->bricks_failed = false;       // an explicit request retries after an earlier shortage of HBM
-    if (which & VV_LAYOUT_ZFAST) { c->zfast_failed = false; c->xpair_failed = false; }
+    if (which & VV_LAYOUT_BRICKED) c->copies[CP_BRICKS].failed = false;       // an explicit request retries after an earlier shortage of HBM
+    if (which & VV_LAYOUT_ZFAST) c->copies[CP_ZFAST].failed = c->copies[CP_XPAIR].failed = false;
     // (a copy built here counts as just used: the next one must not evict it to make room for itself)
-    if ((which & VV_LAYOUT_BRICKED) && ensure_bricks(c, st)) { built |= VV_LAYOUT_BRICKED; c->last_used[CP_BRICKS] = ++c->frame_no; }
-    if ((which & VV_LAYOUT_ZFAST) && ensure_zfast(c, st)) {
-        built |= VV_LAYOUT_ZFAST; c->last_used[CP_ZFAST] = ++c->frame_no;
+    auto prepare = [&](int k) {
+        if (!ensure_copy[k](c, st)) return false;
+        c->copies[k].last_used = ++c->frame_no;
+        return true;
+    };
+    if ((which & VV_LAYOUT_BRICKED) && prepare(CP_BRICKS)) built |= VV_LAYOUT_BRICKED;
+    if ((which & VV_LAYOUT_ZFAST) && prepare(CP_ZFAST)) {
+        built |= VV_LAYOUT_ZFAST;
         // side views of unshaded frames take the x-pair copy where front views take the z-pair copy: built with the z-fastest copy it is made from
-        if (pair_ok && ensure_xpair(c, st)) c->last_used[CP_XPAIR] = ++c->frame_no;
+        if (pair_ok) prepare(CP_XPAIR);
     }
-    if ((which & VV_LAYOUT_ZPAIR) && ensure_zpair(c, st)) { built |= VV_LAYOUT_ZPAIR; c->last_used[CP_ZPAIR] = ++c->frame_no; }
+    if ((which & VV_LAYOUT_ZPAIR) && prepare(CP_ZPAIR)) built |= VV_LAYOUT_ZPAIR;
     return built;
 }
 
@@ -405,12 +503,14 @@ int vv_device_bytes(const vv_context *c, unsigned long long out[4])
 {
     if (!c || !out) return VV_ERR_INVALID;
     out[0] = c->d_vol ? c->alloc_bytes : 0;
-    out[1] = c->bricks_valid ? c->bricks_bytes : 0;
-    out[2] = (c->zpair_valid ? c->zpair_bytes : 0) + (c->zfast_valid ? c->zfast_bytes : 0) + (c->xpair_valid ? c->xpair_bytes : 0);
+    out[1] = copy_bytes(c, CP_BRICKS);
+    out[2] = copy_bytes(c, CP_ZPAIR) + copy_bytes(c, CP_ZFAST) + copy_bytes(c, CP_XPAIR);
     out[3] = c->rad_cap + c->frame_cap + c->img_cap + c->slice_cap + 4096 + 8 * sizeof(unsigned long long);
     return VV_OK;
 }
 
+// developer statistics of the last instrumented launch (staged kernel): [0] executed samples,
+// [1] stages, [2] samples served from global memory, [3] bytes staged into LDS, [4] wave compute trips
 int vv_debug_counters(vv_context *c, unsigned long long out[16])
 {
     if (!c || !out || !c->counter_valid) return VV_ERR_INVALID;
@@ -434,7 +534,7 @@ int vv_load_volume_stream_begin(vv_context *c, int vtype, int nx, int ny, int nz
     HIPCHK(c, hipSetDevice(c->device));
     c->knobs.read();
     const size_t bytes = (size_t)nx * ny * nz * vsz, pad = (size_t)nx * ny * vsz + 2 * (size_t)nx * vsz + 4096;
-    drop_bricks(c);
+    drop_copies(c);
     if (c->d_vol) { HIPCHK(c, hipFree(c->d_vol)); c->d_vol = nullptr; }
     HIPCHK(c, hipMalloc(&c->d_vol, bytes + pad));
     if (!c->copy_stream) HIPCHK(c, hipStreamCreate(&c->copy_stream));
@@ -565,7 +665,7 @@ int vv_load_volume_t3d(vv_context *c, const char *path, int header, int vtype, c
     int r3 = vv_load_volume_stream_end(c);
     if (rc || r3) {
         // a partly filled volume must not be rendered: drop it, later calls report VV_ERR_NO_VOLUME
-        drop_bricks(c);
+        drop_copies(c);
         if (c->d_vol) { (void)hipFree(c->d_vol); c->d_vol = nullptr; }
         c->nx = c->ny = c->nz = 0; c->vol_bytes = 0; c->streaming = false;
         if (rc == VV_ERR_IO) return fail(c, VV_ERR_IO, "vv_load_volume_t3d: file shorter than its header says");
@@ -620,122 +720,20 @@ static int finalize_layout(vv_context *c, hipStream_t st)
     return VV_OK;
 }
 
-// Builds the bricked / z-pair copy of the loaded volume if it is missing and HBM has room.
-// Returns true when the copy is usable afterwards.  
-static bool ensure_bricks(vv_context *c, hipStream_t st)
+// The volume as the kernels of build `b` see it: the linear layout and the copy that build samples (an x-pair frame carries the z-fastest copy
+// as well, and the x-pair copy in the z-pair fields).
+static VolumeView view_of(const vv_context *c, MarchBuild b)
 {
-    if (c->bricks_valid) return true;
-    if (c->bricks_failed) return false;                                   // (until the next volume load)
-    uint32_t sy = 0, sz64 = 0;
-    const size_t bb = brick_copy_bytes(c->vtype, c->nx, c->ny, c->nz, &sy, &sz64);
-    size_t free_b = 0, total_b = 0;
-    if (!make_room(c, bb, 1u << CP_BRICKS)) { c->bricks_failed = true; return false; }
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < bb + (512ull << 20) || sz64 >= (1u << 24) || sy >= (1u << 24) ||
-        hipMalloc(&c->d_bricks, bb + 16) != hipSuccess) {                  // (the sampler multiplies b_sy and b_sz64 as 24-bit values)
-        (void)hipGetLastError(); c->d_bricks = nullptr; c->bricks_failed = true;
-        return false;                                                     // no room: linear path
-    }
-    launch_build_bricks(c->vtype, c->d_vol, c->row_pitch, c->slice_pitch, c->d_bricks, c->nx, c->ny, c->nz, st);
-    if (hipMemsetAsync((char *)c->d_bricks + bb, 0, 16, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess) {                         // later frames may come on another stream
-        (void)hipGetLastError(); (void)hipFree(c->d_bricks); c->d_bricks = nullptr;
-        return false;
-    }
-    c->b_sy = sy; c->b_sz64 = sz64; c->bricks_bytes = bb; c->bricks_valid = true;
-    return true;
-}
-
-static bool ensure_zpair(vv_context *c, hipStream_t st)
-{
-    if (c->zpair_valid) return true;
-    uint32_t rb = 0, sb = 0;
-    const size_t zb = zpair_copy_bytes(c->vtype, c->nx, c->ny, c->nz, &rb, &sb);
-    size_t free_b = 0, total_b = 0;
-    if (!make_room(c, zb, 1u << CP_ZPAIR)) return false;
-    if ((size_t)(c->ny + 1) * ((size_t)c->nx + 1) * 8 >= (1ull << 32) || ((size_t)c->nx + 1) * 8 >= (1u << 24) ||
-        (c->vtype == VV_VOXEL_U8 && zb >= (1ull << 32)) ||                // u8 sampler: 32-bit offsets
-        hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < zb + (512ull << 20) ||
-        hipMalloc(&c->d_zpair, zb + 32) != hipSuccess) {
-        (void)hipGetLastError(); c->d_zpair = nullptr;
-        return false;
-    }
-    launch_build_zpair(c->vtype, c->d_vol, c->row_pitch, c->slice_pitch, c->d_zpair, c->nx, c->ny, c->nz, st);
-    if (hipMemsetAsync((char *)c->d_zpair + zb, 0, 32, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        (void)hipGetLastError(); (void)hipFree(c->d_zpair); c->d_zpair = nullptr;
-        return false;
-    }
-    c->zp_row = rb; c->zp_slab = sb; c->zpair_bytes = zb; c->zpair_valid = true;
-    return true;
-}
-
-// The z-fastest copy of the volume (VolumeView::zfast): rows of nz voxels padded like the linear layout's rows (finalize_layout),
-// ny rows per slice, nx slices + one slice, one row and 16 bytes of zeros behind them (the weight-0 corners of edge samples).
-static bool ensure_zfast(vv_context *c, hipStream_t st)
-{
-    if (c->zfast_valid) return true;
-    if (c->zfast_failed) return false;
-    const size_t vsz = c->vtype == VV_VOXEL_F32 ? 4 : 1;
-    size_t row = (size_t)c->nz * vsz;
-    if (row % 1024 == 0) row += 32;
-    else if (vsz == 1) row = (row + 3) & ~(size_t)3;                       // (u8 rows are read as aligned dwords)
-    size_t rows = (size_t)c->ny;
-    if (row % 1024 == 32 && (rows * row) % 4096 == 0) rows += 1;
-    const size_t slice = rows * row, bytes = slice * ((size_t)c->nx + 1) + row + 16;
-    size_t free_b = 0, total_b = 0;
-    if (c->ny > 65535 || (c->nz + 31) / 32 > 65535 || !make_room(c, bytes, 1u << CP_ZFAST)) { c->zfast_failed = true; return false; }     // (launch_build_zfast: one grid layer per row)
-    if (row >= (1u << 24) || slice >= (1ull << 32) || hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < bytes + (512ull << 20) ||
-        hipMalloc(&c->d_zfast, bytes) != hipSuccess) {
-        (void)hipGetLastError(); c->d_zfast = nullptr; c->zfast_failed = true;
-        return false;                                                     // no room: the bricked copy serves the view
-    }
-    if (hipMemsetAsync(c->d_zfast, 0, bytes, st) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(c->d_zfast); c->d_zfast = nullptr; c->zfast_failed = true; return false; }
-    launch_build_zfast(c->vtype, c->d_vol, (uint32_t)c->row_pitch, (uint64_t)c->slice_pitch, c->d_zfast, (uint32_t)row, (uint64_t)slice, c->nx, c->ny, c->nz, st);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {      // later frames may come on another stream
-        (void)hipGetLastError(); (void)hipFree(c->d_zfast); c->d_zfast = nullptr; c->zfast_failed = true;
-        return false;
-    }
-    c->zf_row = (uint32_t)row; c->zf_slice = (uint64_t)slice; c->zfast_bytes = bytes; c->zfast_valid = true;
-    return true;
-}
-
-// The x-pair copy (the z-pair copy with x and z exchanged; built from the z-fastest copy): the limits of ensure_zpair with the roles swapped.
-static bool ensure_xpair(vv_context *c, hipStream_t st)
-{
-    if (c->xpair_valid) return true;
-    if (c->xpair_failed || !ensure_zfast(c, st)) return false;
-    uint32_t rb = 0, sb = 0;
-    const size_t xb = zpair_copy_bytes(c->vtype, c->nz, c->ny, c->nx, &rb, &sb);
-    size_t free_b = 0, total_b = 0;
-    if (!make_room(c, xb, (1u << CP_XPAIR) | (1u << CP_ZFAST))) { c->xpair_failed = true; return false; }
-    if ((size_t)(c->ny + 1) * ((size_t)c->nz + 1) * 8 >= (1ull << 32) || ((size_t)c->nz + 1) * 8 >= (1u << 24) ||
-        (c->vtype == VV_VOXEL_U8 && xb >= (1ull << 32)) ||                // u8 sampler: 32-bit offsets
-        hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < xb + (512ull << 20) ||
-        hipMalloc(&c->d_xpair, xb + 32) != hipSuccess) {
-        (void)hipGetLastError(); c->d_xpair = nullptr; c->xpair_failed = true;
-        return false;
-    }
-    launch_build_xpair(c->vtype, c->d_zfast, c->zf_row, c->zf_slice, c->d_xpair, c->nx, c->ny, c->nz, st);
-    if (hipGetLastError() != hipSuccess ||
-        hipMemsetAsync((char *)c->d_xpair + xb, 0, 32, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        (void)hipGetLastError(); (void)hipFree(c->d_xpair); c->d_xpair = nullptr; c->xpair_failed = true;
-        return false;
-    }
-    c->xp_row = rb; c->xp_slab = sb; c->xpair_bytes = xb; c->xpair_valid = true;
-    return true;
-}
-
-static VolumeView view_of(const vv_context *c)
-{
-    VolumeView V;
-    const uint32_t vsz = c->vtype == VV_VOXEL_F32 ? 4 : 1;
+    VolumeView V = {};
     V.data = c->d_vol; V.nx = c->nx; V.ny = c->ny; V.nz = c->nz;
-    (void)vsz;
     V.row_bytes = (uint32_t)c->row_pitch;
     V.slice_bytes = (uint32_t)c->slice_pitch;
     V.big = c->slice_pitch * (size_t)c->nz > (1ull << 32) || V.slice_bytes >= (1u << 24) || c->knobs.force_big;
-    V.bricks = nullptr; V.b_sy = 0; V.b_sz64 = 0;
-    V.zpair = nullptr; V.zp_row_bytes = 0; V.zp_slab_bytes = 0;
-    V.zfast = nullptr; V.zf_row_bytes = 0; V.zf_slice_bytes = 0;
+    const layout_copy *cp = c->copies;
+    if (b == MB_BRICKED || b == MB_BRICKED_CACHED) { V.bricks = cp[CP_BRICKS].ptr; V.b_sy = cp[CP_BRICKS].row; V.b_sz64 = (uint32_t)cp[CP_BRICKS].slab; }
+    if (b == MB_ZFAST || b == MB_XPAIR) { V.zfast = cp[CP_ZFAST].ptr; V.zf_row_bytes = cp[CP_ZFAST].row; V.zf_slice_bytes = cp[CP_ZFAST].slab; }
+    const layout_copy &pc = cp[b == MB_XPAIR ? CP_XPAIR : CP_ZPAIR];
+    if (b == MB_ZPAIR || b == MB_XPAIR) { V.zpair = pc.ptr; V.zp_row_bytes = pc.row; V.zp_slab_bytes = (uint32_t)pc.slab; }
     return V;
 }
 
@@ -774,12 +772,12 @@ static int camera_basis(vv_context *c, FrameParams &P, const camera_params *cam,
 // From what is known about the view (`have_basis`: P.side holds the screen x direction in volume space; `density`: voxels of volume per sample, 1e9 =
 // unknown) it picks the layout the frame samples (building a missing copy when the context allows it), the wave tile and block shape, the samples in
 // flight per lane and the blocks per CU, and fills MarchArgs accordingly.  Every threshold below carries the measurement it comes from; the VV_* knobs
-// override single decisions for A/Bs.  Returns whether the volume is beyond the caches (the callers pick the kernel build by it).
+// override single decisions for A/Bs.  Sets MarchArgs::build, the kernel build the frame runs.  Returns whether the volume is beyond the caches.
 static bool choose_launch(vv_context *c, MarchArgs &A, const camera_params *cam, const vv_ray_source *rays, const shading_params *shading,
                           bool have_basis, float density, int H, hipStream_t st)
 {
     FrameParams &P = A.P;
-    A.V = view_of(c); A.V_type = c->vtype;
+    A.V_type = c->vtype;
     // Wave tile shape (speed only): memory is contiguous along the volume's x axis.  When the
     // screen x direction maps (almost) onto it, a 32x2 tile lets the 32 lanes of a row read one
     // or two cache lines (measured C3, view along z: 1.6 ms vs 2.1 ms for 8x8); otherwise the
@@ -819,16 +817,13 @@ static bool choose_launch(vv_context *c, MarchArgs &A, const camera_params *cam,
     // (1.8 GiB, 2.2 voxels per sample) 12 %: for sparse frames (3.5 ... 8 voxels per sample) of volumes between 2 and 8 GiB.  VV_PHONG_BRICKS=0/1 overrides.
     const bool phong_bricks_fit = K.phong_bricks > 0 || (density > 3.5f && density <= 8.f && c->vol_bytes > (2ull << 30) && c->vol_bytes <= (8ull << 30));
     const bool phong_bricks = phong_bricks_fit && shading->phongShading && c->vol_bytes > (1ull << 30) && c->vtype == VV_VOXEL_F32 && K.bricked != 0 && K.phong_bricks != 0 &&
-                              (c->bricks_valid || (c->build_in_render && !c->bricks_failed));
+                              (c->copies[CP_BRICKS].valid || (c->build_in_render && !c->copies[CP_BRICKS].failed));
     if (phong_bricks && K.zfast < 0) use_zfast = false;
     ++c->frame_no;
-    const unsigned long long builds_before = (unsigned long long)c->bricks_valid + c->zpair_valid + c->zfast_valid + c->xpair_valid;
-    if (use_zfast) use_zfast = c->build_in_render ? ensure_zfast(c, st) : c->zfast_valid;
-    if (use_zfast) {
-        c->last_used[CP_ZFAST] = c->frame_no;
-        A.strips.tile_log2w = 5;
-        A.V.zfast = c->d_zfast; A.V.zf_row_bytes = c->zf_row; A.V.zf_slice_bytes = c->zf_slice;
-    }
+    auto copies_valid = [c] { int n = 0; for (const layout_copy &cp : c->copies) n += cp.valid; return n; };
+    const int valid_before = copies_valid();
+    if (use_zfast) use_zfast = take_copy(c, CP_ZFAST, st);
+    if (use_zfast) A.strips.tile_log2w = 5;
     if (K.tile_log2w >= 3 && K.tile_log2w <= 5 && !use_zfast) A.strips.tile_log2w = K.tile_log2w;
     // Occupancy cap + gathers in flight (speed only; measured on MI355X, profiles/EXPERIMENTS.md part B section 4):
     //   volume beyond the caches (> 1 GiB), aligned view : 2 blocks per CU, 3 samples per trip
@@ -881,10 +876,8 @@ static bool choose_launch(vv_context *c, MarchArgs &A, const camera_params *cam,
     bool use_bricks = (A.strips.tile_log2w == 3 || phong_bricks) && (size_t)c->nx * c->ny * c->nz >= (1ull << 21);
     if (K.bricked >= 0) use_bricks = K.bricked != 0;
     if (use_zfast) use_bricks = false;
-    if (use_bricks) use_bricks = c->build_in_render ? ensure_bricks(c, st) : c->bricks_valid;
+    if (use_bricks) use_bricks = take_copy(c, CP_BRICKS, st);
     if (use_bricks) {
-        c->last_used[CP_BRICKS] = c->frame_no;
-        A.V.bricks = c->d_bricks; A.V.b_sy = c->b_sy; A.V.b_sz64 = c->b_sz64;
         // measured (C3 rotated, 1024^3): 2 blocks per CU and 2 samples per trip: 3.64 -> 1.60 ms
         if (!k_unroll) A.unroll = 2;
         if (!k_reserve) A.lds_reserve = beyond_caches ? big_reserve : 36000;
@@ -900,18 +893,18 @@ static bool choose_launch(vv_context *c, MarchArgs &A, const camera_params *cam,
                      (c->vtype == VV_VOXEL_U8 || c->vol_bytes <= (512ull << 20));
     if (K.zpair >= 0) use_zpair = K.zpair != 0 && !use_bricks;
     if (use_zfast) use_zpair = false;
-    if (use_zpair) use_zpair = c->build_in_render ? ensure_zpair(c, st) : c->zpair_valid;
-    if (use_zpair) { c->last_used[CP_ZPAIR] = c->frame_no; A.V.zpair = c->d_zpair; A.V.zp_row_bytes = c->zp_row; A.V.zp_slab_bytes = c->zp_slab; }
+    if (use_zpair) use_zpair = take_copy(c, CP_ZPAIR, st);
     // x-pair copy (speed only): the same two-gather form for side views -- the z-pair copy with x and z exchanged, handed to the kernel in the
     // z-pair fields of the view -- under the z-pair copy's conditions (unshaded, u8 or f32 up to 512 MiB).  Follows VV_ZPAIR=0.
-    A.xpair = false;
-    if (use_zfast && !shading->phongShading && K.zpair != 0 && (c->vtype == VV_VOXEL_U8 || c->vol_bytes <= (512ull << 20)) &&
-        (c->build_in_render ? ensure_xpair(c, st) : c->xpair_valid)) {
-        A.xpair = true; c->last_used[CP_XPAIR] = c->frame_no;
-        A.V.zpair = c->d_xpair; A.V.zp_row_bytes = c->xp_row; A.V.zp_slab_bytes = c->xp_slab;
-    }
-    c->builds_in_render += ((unsigned long long)c->bricks_valid + c->zpair_valid + c->zfast_valid + c->xpair_valid > builds_before)
-                           ? ((unsigned long long)c->bricks_valid + c->zpair_valid + c->zfast_valid + c->xpair_valid - builds_before) : 0;
+    const bool use_xpair = use_zfast && !shading->phongShading && K.zpair != 0 && (c->vtype == VV_VOXEL_U8 || c->vol_bytes <= (512ull << 20)) &&
+                           take_copy(c, CP_XPAIR, st);
+    const int valid_after = copies_valid();
+    if (valid_after > valid_before) c->builds_in_render += valid_after - valid_before;
+    // The kernel build.  Linear volumes beyond the caches take the 64-bit-addressing build in Phong frames even below 4 GiB: the other one is compiled
+    // for 5 waves per SIMD, which only cache-resident volumes want (1000^3 f32: 1.884 -> 1.817 ms, tools/ab_env.sh VV_FORCE_BIG=1).
+    A.build = use_xpair ? MB_XPAIR : use_zfast ? MB_ZFAST : use_bricks ? (beyond_caches ? MB_BRICKED : MB_BRICKED_CACHED) : use_zpair ? MB_ZPAIR :
+              (view_of(c, MB_LINEAR).big || (shading->phongShading && beyond_caches)) ? MB_LINEAR_BIG : MB_LINEAR;
+    A.V = view_of(c, A.build);
     // Phong kernel: 14.3 KB of LDS per block + this reserve.  Measured (tools/ab_phong.sh): volumes up to
     // 1 GiB like 5 blocks per CU (C2 0.54 -> 0.47 ms against no cap, u8 1024^3 1.88 -> 1.78), the 4 GiB
     // volume of C3 3 blocks (2.77 ms with 2, 2.48 with 3, 2.54 with 4), the 32 GiB volume of C5 2 (18.2 vs 20.2 ms)
@@ -952,6 +945,19 @@ static bool screen_rect(const MarchArgs &A, int W, int H, double *xmin, double *
     if (!std::isfinite(lo[0] + hi[0] + lo[1] + hi[1] + mx + my) || mx > W || my > H) return false;
     *xmin = lo[0] - mx; *xmax = hi[0] + mx; *ymin = lo[1] - my; *ymax = hi[1] + my;
     return true;
+}
+
+static void launch_march(const MarchArgs &A, hipStream_t st)
+{
+    switch (A.build) {
+    case MB_LINEAR:         launch_raymarch(A, st); break;
+    case MB_LINEAR_BIG:     launch_raymarch_big(A, st); break;
+    case MB_BRICKED:        launch_raymarch_bricked(A, st); break;
+    case MB_BRICKED_CACHED: launch_raymarch_bricked_cached(A, st); break;
+    case MB_ZPAIR:          launch_raymarch_zpair(A, st); break;
+    case MB_ZFAST:          launch_raymarch_zfast(A, st); break;
+    case MB_XPAIR:          launch_raymarch_xpair(A, st); break;
+    }
 }
 
 extern "C" {
@@ -1195,25 +1201,18 @@ int vv_render(vv_context *c, int W, int H, const slice_params *slice, const came
 #endif
     c->counter_valid = A.instr;
     {
-        const int layout = A.xpair ? 5 : A.V.zfast ? 4 : (A.V.bricks ? 2 : (A.V.zpair ? 3 : ((A.V.big || (A.phong && beyond_caches)) ? 1 : 0)));
-        const int v[8] = {A.strips.tile_log2w, A.strips.blk_log2w, A.unroll, A.phong ? A.lds_reserve_phong : A.lds_reserve, layout, have_basis ? 1 : 0,
-                          (int)fminf(density * 1000.f, 2e9f), A.phong ? 1 : 0};
+        static const int layout_code[] = {0, 1, 2, 2, 3, 4, 5};        // MarchBuild -> the layout code of vv_debug_last_launch
+        const int v[8] = {A.strips.tile_log2w, A.strips.blk_log2w, A.unroll, A.phong ? A.lds_reserve_phong : A.lds_reserve, layout_code[A.build],
+                          have_basis ? 1 : 0, (int)fminf(density * 1000.f, 2e9f), A.phong ? 1 : 0};
         memcpy(c->last_launch, v, sizeof v);
     }
     if (c->time_frames) HIPCHK(c, hipEventRecord(c->ev0, st));
     if (A.phong) {
         if (A.fill_outside) { A.rad_out = nullptr; launch_rad(A, st); }          // the pixels beside the volume's screen rectangle (rad_kernel writes them; no radii here)
-        // (linear volumes beyond the caches take the 64-bit-addressing build even below 4 GiB: the other one is compiled for 5 waves per SIMD, which only
-        //  cache-resident volumes want -- 1000^3 f32: 1.884 -> 1.817 ms, tools/ab_env.sh VV_FORCE_BIG=1)
-        if (A.xpair) launch_raymarch_xpair(A, st); else if (A.V.zfast) launch_raymarch_zfast(A, st); else if (A.V.bricks) { if (beyond_caches) launch_raymarch_bricked(A, st); else launch_raymarch_bricked_cached(A, st); } else if (A.V.zpair) launch_raymarch_zpair(A, st); else if (A.V.big || beyond_caches) launch_raymarch_big(A, st); else launch_raymarch(A, st);
+        launch_march(A, st);
     } else if (A.strips.n_strips > 0) {
         if (W >= 2 && H >= 2) launch_rad(A, st);
-        if (A.xpair) launch_raymarch_xpair(A, st);
-        else if (A.V.zfast) launch_raymarch_zfast(A, st);
-        else if (A.V.bricks) { if (beyond_caches) launch_raymarch_bricked(A, st); else launch_raymarch_bricked_cached(A, st); }
-        else if (A.V.zpair) launch_raymarch_zpair(A, st);
-        else if (A.V.big) launch_raymarch_big(A, st);
-        else launch_raymarch(A, st);
+        launch_march(A, st);
     }
     if (c->time_frames) HIPCHK(c, hipEventRecord(c->ev1, st));
     HIPCHK(c, hipGetLastError());
@@ -1263,8 +1262,6 @@ int vv_first_pass(vv_context *c, int W, int H, const camera_params *cam, const v
     return VV_OK;
 }
 
-// what vv_render chose for its last frame (developer aid, tests): {wave tile log2 width, block log2 width, samples per trip, LDS reserve,
-// layout (0 linear, 1 linear with 64-bit addressing, 2 bricked, 3 z-pair), 1 if the view was known to the policy, density x 1000, Phong}
 int vv_debug_screen_rect(int W, int H, const camera_params *cam, const vv_ray_source *rays, double out[4])
 {
     if (!cam || !rays || !out || W < 1 || H < 1) return fail(nullptr, VV_ERR_INVALID, "vv_debug_screen_rect: bad argument");
@@ -1277,6 +1274,8 @@ int vv_debug_screen_rect(int W, int H, const camera_params *cam, const vv_ray_so
     return screen_rect(A, W, H, &out[0], &out[1], &out[2], &out[3]) ? 1 : 0;
 }
 
+// what vv_render chose for its last frame (developer aid, tests): {wave tile log2 width, block log2 width, samples per trip, LDS reserve, layout (0 linear,
+// 1 linear with 64-bit addressing, 2 bricked, 3 z-pair, 4 z-fastest, 5 x-pair), 1 if the view was known to the policy, density x 1000, Phong}
 int vv_debug_last_launch(vv_context *c, int out[8])
 {
     if (!c || !out) return VV_ERR_INVALID;
@@ -1322,7 +1321,7 @@ static int run_slice(vv_context *c, SliceArgs &S, float *buffer, int out_on_devi
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = pick_stream(c, stream);
     const size_t bytes = S.height * S.width * sizeof(float);
-    S.V = view_of(c); S.V_type = c->vtype;
+    S.V = view_of(c, MB_LINEAR); S.V_type = c->vtype;
     float *d = buffer;
     if (!out_on_device) {
         // persistent scratch instead of the reference's cudaMalloc/cudaFree per call (kernel.cu:508-518)

@@ -25,12 +25,15 @@ struct SlabMap  { int r0, band, band_stride, n_regular;
                   // volume's screen rectangle, or all of them (gx0 = 0, wg = nbx, gs0 = 0, gs1 = n_regular)
                   int gx0, wg, gs0, gs1; };
 
+// the build of the march kernels a frame runs: one per launch_raymarch_* entry point below
+enum MarchBuild : uint8_t { MB_LINEAR, MB_LINEAR_BIG, MB_BRICKED, MB_BRICKED_CACHED, MB_ZPAIR, MB_ZFAST, MB_XPAIR };
+
 struct MarchArgs {
     FrameParams P;
     VolumeView  V;
     int V_type;                 // vv_voxel_type
     bool tex8, gray, phong, instr;
-    bool xpair;                 // VolumeView::zpair holds the x-pair copy (side views): launch_raymarch_xpair
+    MarchBuild build;           // vv_render's choice (MB_XPAIR: VolumeView::zpair holds the x-pair copy)
     int lds_reserve;            // march_kernel: dynamic LDS bytes reserved only to cap blocks per CU
     int unroll;                 // march_kernel: samples per loop trip (2 or 3)
     int lds_reserve_phong;      // march_phong_kernel: same occupancy cap (its own LDS is 14 KB)
