@@ -213,6 +213,31 @@ int  vv_render(vv_context *ctx, int width, int height,
                const vv_render_options *opts,     /* NULL => reference defaults */
                uint8_t *rgba_out, int out_on_device, void *stream);
 
+/* ---- maximum-intensity projection (no reference counterpart: the reference only composites) ----------------------------------
+ * A MIP frame marches exactly the rays and samples of an unshaded vv_render frame in which no ray ever crosses the early-termination
+ * threshold: same end points, per-slab radius, cut plane (SLICE_PLANE_CUT; SLICE_PLANE marches as SLICE_NONE: its highlight is a
+ * compositing effect), 30-sample chunks, step, object scale, filter and 8-bit classification index.  opts->ert_threshold and
+ * opts->ert_mode are ignored.  Per pixel, M = the largest index over the executed samples, 0 when none is executed (a ray that misses
+ * the volume, the cut plane's early return).
+ *   index_out : W*H bytes, row 0 = bottom, holding M                                       (or NULL)
+ *   rgba_out  : W*H*4 bytes; channel c = (uint8)(clamp(tf[M][c], 0, 1) * 255), the conversion vv_render applies to its sums, for every
+ *               pixel the frame writes, M = 0 included                                      (or NULL; at least one of the two)
+ * Column W-1, row H-1 and the rows of other shards (slab_row_begin / _end, shard_*) stay untouched in both images; count_samples and the
+ * touched_* instruments work as in vv_render, as do `stream`, out_on_device (both images), the layout policy of vv_set_layout_policy,
+ * vv_last_frame_ms, vv_last_sample_count and vv_debug_last_launch.  The context's state (volume, table, copies) is not changed.   */
+int  vv_render_mip(vv_context *ctx, int width, int height,
+                   const struct slice_params *slice,
+                   const struct camera_params *camera,
+                   const vv_ray_source *rays,
+                   const vv_render_options *opts,     /* NULL => defaults */
+                   uint8_t *rgba_out, uint8_t *index_out, int out_on_device, void *stream);
+/* The same conversion over an index image of n bytes (one vv_render_mip wrote, or any other): rgba_out[i] = RGBA8 of tf[index[i]].
+ * tf: 256 RGBA float entries in host memory, finite, or NULL = the context's table.  index and rgba_out (n*4 bytes, 4-byte aligned) are
+ * both host or both device pointers (on_device).  Needs no volume: after a table edit a 2-megapixel look-up replaces a march of the
+ * volume.  An enqueue-only call with an explicit table copies it through one buffer of the context: keep such calls on one stream.  */
+int  vv_classify_indices(vv_context *ctx, const uint8_t *index, size_t n, const float tf[1024],
+                         uint8_t *rgba_out, int on_device, void *stream);
+
 /* ---- slice view: replaces invoke_slice_kernel (kernel.cuh:59, kernel.cu:506-519)
  * and invoke_advanced_slice_kernel (kernel.cuh:61, kernel.cu:522-541).
  * buffer: height*width floats; element (j,i) is stored at j*height+i exactly as
@@ -350,7 +375,7 @@ int  vv_layout_state(const vv_context *ctx, unsigned long long out[8]);
 int  vv_device_bytes(const vv_context *ctx, unsigned long long out[4]);
 
 /* ---- metrics (the reference only has a clock() overlay) ---------------- */
-float              vv_last_frame_ms(const vv_context *ctx);      /* hipEvent time of the last vv_render (-1: not timed) */
+float              vv_last_frame_ms(const vv_context *ctx);      /* hipEvent time of the last vv_render / vv_render_mip (-1: not timed) */
 /* Every vv_render brackets its kernels with two hipEventRecord (what vv_last_frame_ms reads): two more packets the stream has to retire per
  * frame, ~2-4 us each back to back.  A host that times whole runs itself (bench.py) or does not time at all switches them off (on = 0);
  * vv_last_frame_ms then returns -1.  Default: on, the reference's lastRenderTime overlay (glwidget.cpp:288-293) wants it. */
@@ -358,7 +383,7 @@ int                vv_set_frame_timing(vv_context *ctx, int on);
 unsigned long long vv_last_sample_count(vv_context *ctx);        /* executed samples, if count_samples */
 int                vv_debug_last_launch(vv_context *ctx, int out[8]);  /* what the launch policy chose for the last vv_render (developer aid): wave tile log2 width,
                                                                        * block log2 width, samples per trip, LDS reserve, layout (0 linear, 1 linear/64-bit, 2 bricked,
-                                                                       * 3 z-pair, 4 z-fastest, 5 x-pair), view known to the policy (0 / 1), density x 1000, Phong (0 / 1) */
+                                                                       * 3 z-pair, 4 z-fastest, 5 x-pair), view known to the policy (0 / 1), density x 1000, kernel family (0 unshaded, 1 Phong, 2 MIP: vv_render_mip) */
 /* The rectangle of pixel coordinates (x_min, x_max, y_min, y_max, margin included) outside of which vv_render lets its pre-pass write (0,0,0,0) instead of
  * marching (analytic ray sources): returns 1 and fills out[4], or 0 when this camera gets no rectangle (a cube corner at or behind the eye's plane, a
  * margin wider than the frame).  Needs no device and no context: tests/test_host.py checks it against the oracle's ray-box test pixel by pixel. */

@@ -71,6 +71,8 @@ struct vv_context {
     float *d_rad = nullptr; size_t rad_cap = 0;
     uint32_t *d_order = nullptr; size_t order_cap = 0;      // StripMap::order of the frame in flight
     uint8_t *d_frame = nullptr; size_t frame_cap = 0;
+    uint8_t *d_index = nullptr; size_t index_cap = 0;       // MIP: index image of a host-buffer frame / of vv_classify_indices
+    float4 *d_tf_arg = nullptr;                             // vv_classify_indices: the caller's table
     uint8_t *d_img = nullptr; size_t img_cap = 0;
     float *d_slice = nullptr; size_t slice_cap = 0;
     float *d_gen = nullptr; size_t gen_cap = 0;       // per-axis tables of the ellipsoid generator
@@ -357,6 +359,8 @@ int vv_shutdown(vv_context *c)
     if (c->d_rad) hipFree(c->d_rad);
     if (c->d_order) hipFree(c->d_order);
     if (c->d_frame) hipFree(c->d_frame);
+    if (c->d_index) hipFree(c->d_index);
+    if (c->d_tf_arg) hipFree(c->d_tf_arg);
     if (c->d_img) hipFree(c->d_img);
     if (c->d_slice) hipFree(c->d_slice);
     if (c->d_gen) hipFree(c->d_gen);
@@ -505,7 +509,7 @@ int vv_device_bytes(const vv_context *c, unsigned long long out[4])
     out[0] = c->d_vol ? c->alloc_bytes : 0;
     out[1] = copy_bytes(c, CP_BRICKS);
     out[2] = copy_bytes(c, CP_ZPAIR) + copy_bytes(c, CP_ZFAST) + copy_bytes(c, CP_XPAIR);
-    out[3] = c->rad_cap + c->frame_cap + c->img_cap + c->slice_cap + 4096 + 8 * sizeof(unsigned long long);
+    out[3] = c->rad_cap + c->frame_cap + c->index_cap + (c->d_tf_arg ? 4096 : 0) + c->img_cap + c->slice_cap + 4096 + 8 * sizeof(unsigned long long);
     return VV_OK;
 }
 
@@ -960,14 +964,25 @@ static void launch_march(const MarchArgs &A, hipStream_t st)
     }
 }
 
-extern "C" {
-
-int vv_render(vv_context *c, int W, int H, const slice_params *slice, const camera_params *cam,
-              const shading_params *shading, const vv_ray_source *rays, const vv_render_options *opts,
-              uint8_t *rgba_out, int out_on_device, void *stream)
+static void launch_mip_build(const MarchArgs &A, hipStream_t st)
 {
-    if (!c) return fail(nullptr, VV_ERR_INVALID, "vv_render: NULL context");
-    if (!slice || !cam || !shading || !rays || !rgba_out) return fail(c, VV_ERR_INVALID, "vv_render: NULL argument");
+    switch (A.build) {
+    case MB_LINEAR:         launch_mip(A, st); break;
+    case MB_LINEAR_BIG:     launch_mip_big(A, st); break;
+    case MB_BRICKED:        launch_mip_bricked(A, st); break;
+    case MB_BRICKED_CACHED: launch_mip_bricked_cached(A, st); break;
+    case MB_ZPAIR:          launch_mip_zpair(A, st); break;
+    case MB_ZFAST:          launch_mip_zfast(A, st); break;
+    case MB_XPAIR:          launch_mip_xpair(A, st); break;
+    }
+}
+
+// One frame: vv_render (mip = false: rgba_out, shading) and vv_render_mip (mip = true: rgba_out and / or index_out, never Phong).  Both share the
+// argument checks, the frame and shard set-up, the launch policy, the screen rectangle and the output staging; only the kernels differ.
+static int render_frame(vv_context *c, int W, int H, const slice_params *slice, const camera_params *cam,
+                        const shading_params *shading, const vv_ray_source *rays, const vv_render_options *opts,
+                        uint8_t *rgba_out, uint8_t *index_out, bool mip, int out_on_device, void *stream)
+{
     if (W < 1 || H < 1) return fail(c, VV_ERR_INVALID, "vv_render: width/height must be >= 1");
     if (!c->d_vol || !c->have_tf) return fail(c, VV_ERR_NO_VOLUME, "vv_render: no volume / transfer function loaded");
     if (slice->type != SLICE_NONE && slice->type != SLICE_PLANE && slice->type != SLICE_PLANE_CUT)
@@ -1042,7 +1057,7 @@ int vv_render(vv_context *c, int W, int H, const slice_params *slice, const came
         A.slabs.r0 = r_lo; A.slabs.band = 1 << 28; A.slabs.band_stride = 0;
         A.slabs.n_regular = r_hi > r_lo ? r_hi - r_lo : 0;
     }
-    P.slice_type = slice->type;
+    P.slice_type = (mip && slice->type == SLICE_PLANE) ? SLICE_NONE : slice->type;      // (a MIP frame has no highlight to draw: SLICE_PLANE marches as SLICE_NONE)
     for (int a = 0; a < 3; ++a) {
         P.slice_point[a] = slice->params[a]; P.slice_normal[a] = slice->params[3 + a];   // kernel.cu:224-225
         P.cam_pos[a] = cam->origin[a]; P.scale[a] = cam->scale[a];
@@ -1117,6 +1132,7 @@ int vv_render(vv_context *c, int W, int H, const slice_params *slice, const came
     density = c->last_density;
     A.gray = c->tf_gray; A.phong = shading->phongShading;
     // march_kernel's tiles: those under the volume's screen rectangle (screen_rect), or all of them
+    bool rect_limits = false;
     {
         StripMap &M = A.strips;
         const int bw = 1 << M.blk_log2w, bh = 256 >> M.blk_log2w;
@@ -1154,8 +1170,13 @@ int vv_render(vv_context *c, int W, int H, const slice_params *slice, const came
             A.rect.x0 = M.tx0 * bw; A.rect.x1 = (M.tx0 + M.wr) * bw;
             if (s_count <= 1) { A.rect.y0 = M.y0 + M.s0 * bh; A.rect.y1 = M.y0 + M.s1 * bh; }
             if (M.wr == 0 || M.s1 == M.s0) { A.rect.x0 = A.rect.x1 = A.rect.y0 = A.rect.y1 = 0; }       // (the cube is off the screen: every pixel is rad_kernel's)
+            rect_limits = true;
         }
     }
+    // A MIP frame's pixels beside the rectangle hold the table's entry 0, not rad_kernel's (0,0,0,0), and there is the index image: mip_fill_kernel
+    // writes them, and rad_kernel gets no rectangle (it then writes no pixel and computes every slab's radius).
+    const PixelRect mip_rect = A.rect;
+    if (mip) { A.rect.x0 = 0; A.rect.y0 = 0; A.rect.x1 = INT_MAX; A.rect.y1 = INT_MAX; }
     A.tf = c->d_tf;
     int rc = ensure(c, (void **)&c->d_rad, &c->rad_cap, (size_t)P.nbx * P.nby * sizeof(float));
     if (rc) return rc;
@@ -1180,19 +1201,25 @@ int vv_render(vv_context *c, int W, int H, const slice_params *slice, const came
     A.rad = c->d_rad; A.rad_out = c->d_rad;
     A.counter = c->d_counter;
 
-    const size_t fb = (size_t)W * H * 4;
-    uint8_t *d_out = rgba_out;
+    const size_t fb = (size_t)W * H * 4, ib = (size_t)W * H;
+    uint8_t *d_out = rgba_out, *d_idx = index_out;
     // Pixels the frame does not write (column W-1, row H-1, rows of other shards) must keep the caller's bytes.  A whole
     // frame is read back as the (W-1) x (H-1) rectangle it writes; a sharded / row-limited frame goes through a staged
     // copy of the caller's buffer (rare path).
     const bool whole = s_count <= 1 && rb == 0 && re == P.nby && W >= 2 && H >= 2;
-    if (!out_on_device) {
+    if (!out_on_device && rgba_out) {
         rc = ensure(c, (void **)&c->d_frame, &c->frame_cap, fb);
         if (rc) return rc;
         d_out = c->d_frame;
         if (!whole) HIPCHK(c, hipMemcpyAsync(d_out, rgba_out, fb, hipMemcpyHostToDevice, st));
     }
-    A.pixels = (uint32_t *)d_out;
+    if (!out_on_device && index_out) {
+        rc = ensure(c, (void **)&c->d_index, &c->index_cap, ib);
+        if (rc) return rc;
+        d_idx = c->d_index;
+        if (!whole) HIPCHK(c, hipMemcpyAsync(d_idx, index_out, ib, hipMemcpyHostToDevice, st));
+    }
+    A.pixels = (uint32_t *)d_out; A.index = d_idx;
     if (((uintptr_t)d_out & 3) != 0) return fail(c, VV_ERR_INVALID, "vv_render: output buffer must be 4-byte aligned");
 
     if (A.instr) HIPCHK(c, hipMemsetAsync(c->d_counter, 0, 16 * sizeof(unsigned long long), st));
@@ -1203,11 +1230,17 @@ int vv_render(vv_context *c, int W, int H, const slice_params *slice, const came
     {
         static const int layout_code[] = {0, 1, 2, 2, 3, 4, 5};        // MarchBuild -> the layout code of vv_debug_last_launch
         const int v[8] = {A.strips.tile_log2w, A.strips.blk_log2w, A.unroll, A.phong ? A.lds_reserve_phong : A.lds_reserve, layout_code[A.build],
-                          have_basis ? 1 : 0, (int)fminf(density * 1000.f, 2e9f), A.phong ? 1 : 0};
+                          have_basis ? 1 : 0, (int)fminf(density * 1000.f, 2e9f), mip ? 2 : (A.phong ? 1 : 0)};
         memcpy(c->last_launch, v, sizeof v);
     }
     if (c->time_frames) HIPCHK(c, hipEventRecord(c->ev0, st));
-    if (A.phong) {
+    if (mip) {
+        if (A.strips.n_strips > 0) {
+            if (W >= 2 && H >= 2) launch_rad(A, st);
+            if (rect_limits) launch_mip_fill(A, mip_rect, st);
+            launch_mip_build(A, st);
+        }
+    } else if (A.phong) {
         if (A.fill_outside) { A.rad_out = nullptr; launch_rad(A, st); }          // the pixels beside the volume's screen rectangle (rad_kernel writes them; no radii here)
         launch_march(A, st);
     } else if (A.strips.n_strips > 0) {
@@ -1218,8 +1251,75 @@ int vv_render(vv_context *c, int W, int H, const slice_params *slice, const came
     HIPCHK(c, hipGetLastError());
     c->timed = c->time_frames;
     if (!out_on_device) {
-        if (whole) HIPCHK(c, hipMemcpy2DAsync(rgba_out, (size_t)W * 4, d_out, (size_t)W * 4, (size_t)(W - 1) * 4, (size_t)(H - 1), hipMemcpyDeviceToHost, st));
-        else HIPCHK(c, hipMemcpyAsync(rgba_out, d_out, fb, hipMemcpyDeviceToHost, st));
+        if (rgba_out) {
+            if (whole) HIPCHK(c, hipMemcpy2DAsync(rgba_out, (size_t)W * 4, d_out, (size_t)W * 4, (size_t)(W - 1) * 4, (size_t)(H - 1), hipMemcpyDeviceToHost, st));
+            else HIPCHK(c, hipMemcpyAsync(rgba_out, d_out, fb, hipMemcpyDeviceToHost, st));
+        }
+        if (index_out) {
+            if (whole) HIPCHK(c, hipMemcpy2DAsync(index_out, (size_t)W, d_idx, (size_t)W, (size_t)(W - 1), (size_t)(H - 1), hipMemcpyDeviceToHost, st));
+            else HIPCHK(c, hipMemcpyAsync(index_out, d_idx, ib, hipMemcpyDeviceToHost, st));
+        }
+        HIPCHK(c, hipStreamSynchronize(st));
+    } else if (!stream) {
+        HIPCHK(c, hipStreamSynchronize(st));
+    }
+    return VV_OK;
+}
+
+extern "C" {
+
+int vv_render(vv_context *c, int W, int H, const slice_params *slice, const camera_params *cam,
+              const shading_params *shading, const vv_ray_source *rays, const vv_render_options *opts,
+              uint8_t *rgba_out, int out_on_device, void *stream)
+{
+    if (!c) return fail(nullptr, VV_ERR_INVALID, "vv_render: NULL context");
+    if (!slice || !cam || !shading || !rays || !rgba_out) return fail(c, VV_ERR_INVALID, "vv_render: NULL argument");
+    return render_frame(c, W, H, slice, cam, shading, rays, opts, rgba_out, nullptr, false, out_on_device, stream);
+}
+
+// ---- maximum-intensity projection (no reference counterpart) ---------------------------------
+int vv_render_mip(vv_context *c, int W, int H, const slice_params *slice, const camera_params *cam,
+                  const vv_ray_source *rays, const vv_render_options *opts,
+                  uint8_t *rgba_out, uint8_t *index_out, int out_on_device, void *stream)
+{
+    if (!c) return fail(nullptr, VV_ERR_INVALID, "vv_render_mip: NULL context");
+    if (!slice || !cam || !rays) return fail(c, VV_ERR_INVALID, "vv_render_mip: NULL argument");
+    if (!rgba_out && !index_out) return fail(c, VV_ERR_INVALID, "vv_render_mip: rgba_out and index_out are both NULL");
+    shading_params unshaded;
+    memset(&unshaded, 0, sizeof unshaded);
+    unshaded.transferPreset = -1; unshaded.phongShading = false;
+    return render_frame(c, W, H, slice, cam, &unshaded, rays, opts, rgba_out, index_out, true, out_on_device, stream);
+}
+
+int vv_classify_indices(vv_context *c, const uint8_t *index, size_t n, const float tf[1024], uint8_t *rgba_out, int on_device, void *stream)
+{
+    if (!c) return fail(nullptr, VV_ERR_INVALID, "vv_classify_indices: NULL context");
+    if (!index || !rgba_out) return fail(c, VV_ERR_INVALID, "vv_classify_indices: NULL argument");
+    if (!tf && !c->have_tf) return fail(c, VV_ERR_NO_VOLUME, "vv_classify_indices: no transfer function loaded");
+    if (tf) for (int i = 0; i < 1024; ++i) if (!std::isfinite(tf[i])) return fail(c, VV_ERR_INVALID, "vv_classify_indices: transfer function must be finite");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = pick_stream(c, stream);
+    const float4 *d_tf = c->d_tf;
+    if (tf) {
+        if (!c->d_tf_arg) HIPCHK(c, hipMalloc((void **)&c->d_tf_arg, 1024 * sizeof(float)));
+        HIPCHK(c, hipMemcpyAsync(c->d_tf_arg, tf, 1024 * sizeof(float), hipMemcpyHostToDevice, st));
+        d_tf = c->d_tf_arg;
+    }
+    const uint8_t *d_idx = index;
+    uint8_t *d_out = rgba_out;
+    if (!on_device && n) {
+        int rc = ensure(c, (void **)&c->d_index, &c->index_cap, n);
+        if (rc) return rc;
+        rc = ensure(c, (void **)&c->d_frame, &c->frame_cap, n * 4);
+        if (rc) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->d_index, index, n, hipMemcpyHostToDevice, st));
+        d_idx = c->d_index; d_out = c->d_frame;
+    }
+    if (((uintptr_t)d_out & 3) != 0) return fail(c, VV_ERR_INVALID, "vv_classify_indices: output buffer must be 4-byte aligned");
+    launch_mip_classify(d_idx, n, d_tf, (uint32_t *)d_out, st);
+    HIPCHK(c, hipGetLastError());
+    if (!on_device) {
+        if (n) HIPCHK(c, hipMemcpyAsync(rgba_out, d_out, n * 4, hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));
     } else if (!stream) {
         HIPCHK(c, hipStreamSynchronize(st));

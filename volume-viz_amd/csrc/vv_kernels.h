@@ -45,7 +45,8 @@ struct MarchArgs {
     const float4 *tf;           // device, 256 entries
     const float *rad;           // device, nbx*nby (read by march_kernel)
     float *rad_out;             // same buffer (written by rad_kernel)
-    uint32_t *pixels;           // device RGBA8 frame
+    uint32_t *pixels;           // device RGBA8 frame (MIP frames: may be null)
+    uint8_t *index;             // MIP frames: device image of the per-pixel maxima, W * H bytes, or null
     unsigned long long *counter;
     InstrArgs I;                // bitmaps of an instrumented frame (vv_render_options::touched_bricks / touched_lines)
 };
@@ -58,6 +59,17 @@ void launch_raymarch_bricked_cached(const MarchArgs &a, hipStream_t s);  // ... 
 void launch_raymarch_zpair(const MarchArgs &a, hipStream_t s);    // same kernels on VolumeView::zpair
 void launch_raymarch_zfast(const MarchArgs &a, hipStream_t s);    // same kernels on VolumeView::zfast
 void launch_raymarch_xpair(const MarchArgs &a, hipStream_t s);    // same kernels on the x-pair copy (handed over in VolumeView::zpair)
+// maximum-intensity projection (vv_mip.hip): one build per layout like the march kernels; rad_kernel is its pre-pass too
+constexpr int kMipTableBytes = 4096;      // march_kernel's LDS table, which mip_kernel does not have: added to lds_reserve so that the blocks per CU stay what the policy measured
+void launch_mip(const MarchArgs &a, hipStream_t s);
+void launch_mip_big(const MarchArgs &a, hipStream_t s);
+void launch_mip_bricked(const MarchArgs &a, hipStream_t s);
+void launch_mip_bricked_cached(const MarchArgs &a, hipStream_t s);
+void launch_mip_zpair(const MarchArgs &a, hipStream_t s);
+void launch_mip_zfast(const MarchArgs &a, hipStream_t s);
+void launch_mip_xpair(const MarchArgs &a, hipStream_t s);
+void launch_mip_fill(const MarchArgs &a, const PixelRect &rect, hipStream_t s);      // M = 0 for the owned pixels outside `rect` (both images)
+void launch_mip_classify(const uint8_t *index, size_t n, const float4 *tf, uint32_t *pixels, hipStream_t s);   // pixels[i] = RGBA8 of tf[index[i]]
 void launch_build_xpair(int vtype, const void *zfast, uint32_t zf_row_bytes, uint64_t zf_slice_bytes, void *xpair, int nx, int ny, int nz, hipStream_t s);
 void launch_build_zfast(int vtype, const void *vol, uint32_t row_pitch, uint64_t slice_pitch, void *out, uint32_t zf_row_bytes, uint64_t zf_slice_bytes, int nx, int ny, int nz, hipStream_t s);
 size_t zpair_copy_bytes(int vtype, int nx, int ny, int nz, uint32_t *row_bytes, uint32_t *slab_bytes);

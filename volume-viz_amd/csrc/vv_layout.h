@@ -1,0 +1,93 @@
+// vv_layout.h -- the volume layout a march translation unit is compiled for (internal; included once per unit, after vv_device.h).
+//
+// vv_raymarch.hip and vv_mip.hip are each compiled seven times (their *_big / *_brick / *_brick_cached / *_zpair / *_zfast / *_xpair
+// wrappers define VV_BIG_VOLUME / VV_BRICKED (+ VV_BRICKED_CACHED) / VV_ZPAIR / VV_ZFAST / VV_ZPAIR + VV_XPAIR).  This header turns those
+// macros into the unit's namespace (VV_BIG_NS), its layout constant, its corner registers and fetch, and the line marking of instrumented frames.
+#pragma once
+#include "vv_device.h"
+
+#if defined(VV_ZPAIR) && defined(VV_XPAIR)
+#define VV_BIG_NS xpair
+constexpr int kLayout = vv::LAYOUT_ZPAIR;
+#elif defined(VV_ZPAIR)
+#define VV_BIG_NS zpair
+constexpr int kLayout = vv::LAYOUT_ZPAIR;
+#elif defined(VV_BRICKED) && defined(VV_BRICKED_CACHED)
+#define VV_BIG_NS brickc
+constexpr int kLayout = vv::LAYOUT_BRICKED;
+#elif defined(VV_BRICKED)
+#define VV_BIG_NS brick
+constexpr int kLayout = vv::LAYOUT_BRICKED;
+#elif defined(VV_ZFAST)
+#define VV_BIG_NS zfast
+constexpr int kLayout = vv::LAYOUT_ZFAST;
+#elif defined(VV_BIG_VOLUME)
+#define VV_BIG_NS big
+constexpr int kLayout = vv::LAYOUT_LINEAR_BIG;
+#else
+#define VV_BIG_NS small
+constexpr int kLayout = vv::LAYOUT_LINEAR;
+#endif
+
+namespace vv {
+namespace VV_BIG_NS {
+
+// corner registers and fetch of the layout this translation unit is compiled for
+template <int VOXEL> struct CornerSel { using type = Corners<VOXEL>; };
+#ifdef VV_ZPAIR
+template <> struct CornerSel<VV_VOXEL_F32> { using type = CornersZ; };
+template <> struct CornerSel<VV_VOXEL_U8>  { using type = CornersZ8; };
+#endif
+template <int VOXEL, bool TEX8, class CT>
+__device__ __forceinline__ void fetch_any(const VolumeView &V, float px, float py, float pz, CT &C)
+{
+#ifdef VV_ZPAIR
+    fetch_corners_zpair<TEX8>(V, px, py, pz, C);
+#else
+    fetch_corners<VOXEL, TEX8, kLayout>(V, px, py, pz, C);
+#endif
+}
+
+// Instrumented frames only: the 128-byte lines (offsets from the sampled layout's base) the gathers of one sample touch -- the address
+// arithmetic of fetch_any() for this translation unit's layout, restated (InstrArgs::lines).
+template <int VOXEL, bool TEX8>
+__device__ __noinline__ void mark_sample_lines(const InstrArgs &I, const VolumeView &V, float px, float py, float pz)
+{
+    uint32_t ix, iy, iz;
+    (void)axis_coord<TEX8>(px, (float)V.nx, (float)(V.nx - 1), ix);
+    (void)axis_coord<TEX8>(py, (float)V.ny, (float)(V.ny - 1), iy);
+    (void)axis_coord<TEX8>(pz, (float)V.nz, (float)(V.nz - 1), iz);
+    constexpr bool F = VOXEL == VV_VOXEL_F32;
+#if defined(VV_ZPAIR)
+    const uint32_t rec = F ? 8u : 2u, bytes = F ? 16u : 4u;
+#ifdef VV_XPAIR
+    const uint64_t off = (uint64_t)ix * V.zp_slab_bytes + (uint64_t)iy * V.zp_row_bytes + (uint64_t)iz * rec;
+#else
+    const uint64_t off = (uint64_t)iz * V.zp_slab_bytes + (uint64_t)iy * V.zp_row_bytes + (uint64_t)ix * rec;
+#endif
+    mark_line_range(I, off, bytes); mark_line_range(I, off + V.zp_row_bytes, bytes);
+#else
+    if constexpr (kLayout == LAYOUT_LINEAR || kLayout == LAYOUT_LINEAR_BIG) {
+        const uint64_t o = (uint64_t)iz * V.slice_bytes + (uint64_t)iy * V.row_bytes + (F ? ix * 4u : (ix & ~3u));
+        mark_line_range(I, o, 8); mark_line_range(I, o + V.row_bytes, 8);
+        mark_line_range(I, o + V.slice_bytes, 8); mark_line_range(I, o + V.slice_bytes + V.row_bytes, 8);
+    } else if constexpr (kLayout == LAYOUT_ZFAST) {
+        const uint64_t o = (uint64_t)ix * V.zf_slice_bytes + (uint64_t)iy * V.zf_row_bytes + (F ? iz * 4u : (iz & ~3u));
+        mark_line_range(I, o, 8); mark_line_range(I, o + V.zf_row_bytes, 8);
+        mark_line_range(I, o + V.zf_slice_bytes, 8); mark_line_range(I, o + V.zf_slice_bytes + V.zf_row_bytes, 8);
+    } else {
+        using G = BrickGeom<VOXEL>;
+        uint64_t a[4];
+        brick_offsets<VOXEL>(V, ix, iy, iz, a);
+        if constexpr (F && G::halo == 0) {
+            const uint32_t dx = (ix & (G::bx - 1u)) == G::bx - 1u ? G::brick - (G::bx - 1u) * 4u : 4u;
+            for (int k = 0; k < 4; ++k) { mark_line_range(I, a[k], 4); mark_line_range(I, a[k] + dx, 4); }
+        } else {
+            for (int k = 0; k < 4; ++k) mark_line_range(I, a[k], 8);
+        }
+    }
+#endif
+}
+
+} // namespace VV_BIG_NS
+} // namespace vv

@@ -1,0 +1,234 @@
+// vv_mip.hip -- maximum-intensity projection kernels for gfx950 (MI355X).  No reference counterpart: the reference composites only.
+//
+// A MIP frame marches the rays of an unshaded vv_render frame -- same end points, same per-slab sphere radius (rad_kernel), same
+// setup_ray with its cut plane, same 30-sample chunks, same (pos - .5) / scale + .5 mapping, same filter, same 8-bit classification
+// index -- and keeps, per pixel, the largest index M over the samples it executes (0 when it executes none).  No table look-up, no
+// blend, no early-termination state: the ray state and the U samples in flight live in registers, the per-sample work behind the
+// trilinear reconstruction is one v_max_u32, and the transfer table is read once per pixel, in the epilogue.
+//   * mip_kernel           the march: wave tiles, block order and trip structure of march_kernel (vv_raymarch.hip);
+//   * mip_fill_kernel      the pixels beside the volume's screen rectangle (M = 0), which mip_kernel's tiles do not cover;
+//   * mip_classify_kernel  index image -> RGBA through a table (vv_classify_indices).
+// Like vv_raymarch.hip this file is compiled once per volume layout (vv_layout.h), through the vv_mip_*.hip wrappers.
+#include "vv_device.h"
+#include "vv_kernels.h"
+#include "vv_layout.h"
+
+namespace vv {
+namespace VV_BIG_NS {
+
+// channel c of an RGBA pixel = sat_u8(clamp(tf[M][c], 0, 1) * 255): pack_rgba's conversion of a table entry
+__device__ __forceinline__ uint32_t classify_entry(const float4 e) { return pack_rgba(e.x, e.y, e.z, e.w); }
+
+// blockDim = 256 = 4 waves; block -> (strip, tile) and wave -> pixels exactly as in march_kernel (StripMap).  `pixels` and `index`
+// may each be null (vv_render_mip wants at least one).  Uninstrumented frames drop a ray once its maximum is 255 (nothing can raise
+// it); instrumented frames march every ray to its end so that the count is the full executed count.
+template <int VOXEL, bool TEX8, bool INSTR, int U>
+__global__ __launch_bounds__(256) void mip_kernel(FrameParams P, VolumeView V,
+                                                  const float4 *__restrict__ tf,
+                                                  const float *__restrict__ rad,
+                                                  uint32_t *__restrict__ pixels,
+                                                  uint8_t *__restrict__ index,
+                                                  unsigned long long *__restrict__ counter,
+                                                  InstrArgs I, StripMap M)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int bl = M.blk_log2w, ntx = M.wr;
+    int strip, tile_x;
+    if (M.order) {
+        const int L = blockIdx.x, xcd = L & 7, j = L >> 3, pos = ((j / M.order_run) * 8 + xcd) * M.order_run + j % M.order_run;
+        const uint32_t t = M.order[pos];                              // (the grid is exactly the table)
+        if (t == ~0u) return;
+        strip = M.s0 + (int)t / ntx; tile_x = M.tx0 + (int)t % ntx;
+    } else if (M.xcd_band > 0) {
+        const int L = blockIdx.x, per_band = ntx * M.xcd_band;
+        const int xcd = L & 7, j = L >> 3;
+        const int band = (j / per_band) * 8 + xcd, w = j % per_band;
+        strip = M.s0 + band * M.xcd_band + w / ntx; tile_x = M.tx0 + w % ntx;
+    } else { strip = M.s0 + blockIdx.x / ntx; tile_x = M.tx0 + blockIdx.x % ntx; }
+    const int tw = M.tile_log2w, th = 6 - tw;
+    const int wx = wave & (((1 << bl) >> tw) - 1), wy = wave >> (bl - tw);
+    const int x = (tile_x << bl) + (wx << tw) + (lane & ((1 << tw) - 1));
+    const int y = M.y0 + (strip / M.strips_per_band) * M.band_stride_px + (strip % M.strips_per_band) * (256 >> bl) + (wy << th) + (lane >> tw);
+    if (strip >= M.s1) return;
+    // pixels no frame writes: column W-1 / row H-1 (W,H >= 2), rows of other shards
+    const int xmax = P.W >= 2 ? P.W - 2 : 0, ymax = P.H >= 2 ? P.H - 2 : 0;
+    const bool in_frame = x <= xmax && y <= ymax && row_owned(P, y);
+
+    uint32_t m = 0;
+    unsigned long long executed = 0, slots = 0;
+
+    Ray r;
+    int alive = 0;
+    if (in_frame) {
+        f3 front, back;
+        ray_endpoints(P, x, y, front, back);
+        float length = vlen3(back.x - front.x, back.y - front.y, back.z - front.z);
+        if (!(length < 0.001f)) {                                    // (a zero-length ray executes nothing: M = 0)
+            float rd;
+            if (P.W < 2 || P.H < 2) {
+                rd = vlen3(front.x - P.cam_pos[0], front.y - P.cam_pos[1], front.z - P.cam_pos[2]);
+            } else {
+                int ox = owner_slab(x, P.W, P.nbx, P.conflict_x), oy = owner_slab(y, P.H, P.nby, P.conflict_y);
+                rd = rad[oy * P.nbx + ox];
+            }
+            setup_ray(P, front, back, rd, r);
+            alive = r.cut_return ? 0 : 1;
+        }
+    }
+    if (!alive) { r.upper = -1.f; r.dist0 = 0.f; r.sstep = 1.f; r.origin = mk3(0, 0, 0); r.dir = r.origin; r.sdir = r.origin; }
+
+    float dist = r.dist0;
+    for (int chunk = 0; chunk < P.max_chunks && __any(dist < r.upper); ++chunk) {
+        const int n = chunk_count(dist, r.upper, r.sstep);
+        float px, py, pz;
+        {
+#pragma clang fp contract(off)
+            px = r.origin.x + r.dir.x * dist;
+            py = r.origin.y + r.dir.y * dist;
+            pz = r.origin.z + r.dir.z * dist;
+        }
+        // wave-uniform trip count (5 ballots: n <= 30); lanes with fewer samples are predicated, not branched
+        int nmax = 0;
+#pragma unroll
+        for (int bit = 16; bit > 0; bit >>= 1)
+            if (__any(n >= (nmax | bit))) nmax |= bit;
+        if (INSTR) slots += (unsigned long long)((nmax + U - 1) / U * U) * 64ull;
+        for (int i0 = 1; i0 <= nmax; i0 += U) {
+            float tx[U], ty[U], tz[U];
+            typename CornerSel<VOXEL>::type C[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                px += r.sdir.x; py += r.sdir.y; pz += r.sdir.z;
+                tx[u] = __builtin_fmaf(px - 0.5f, P.inv_scale[0], 0.5f);
+                ty[u] = __builtin_fmaf(py - 0.5f, P.inv_scale[1], 0.5f);
+                tz[u] = __builtin_fmaf(pz - 0.5f, P.inv_scale[2], 0.5f);
+                fetch_any<VOXEL, TEX8>(V, tx[u], ty[u], tz[u], C[u]);
+            }
+            __builtin_amdgcn_sched_barrier(0);           // all gathers of the trip are issued before the first is consumed
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const bool live = i0 + u <= n;
+                const uint32_t k = classify_index<VOXEL>(C[u], tx[u], ty[u], tz[u]);
+                m = max(m, live ? k : 0u);
+                if (INSTR) {
+                    const bool inv = bounds_check(tx[u], ty[u], tz[u]);
+                    if (live) {
+                        executed++;
+                        if (I.bricks && inv) mark_bricks(I.bricks, V, tx[u], ty[u], tz[u]);
+                    }
+                    if ((I.lines || I.pairs) && (I.lines_all || (live && inv))) mark_sample_lines<VOXEL, TEX8>(I, V, tx[u], ty[u], tz[u]);
+                }
+            }
+        }
+        if (!INSTR && m == 255u) r.upper = -1.f;
+        {
+#pragma clang fp contract(off)
+            dist += r.sstep * kChunkSteps;
+        }
+    }
+
+    if (in_frame) {
+        const size_t p = (size_t)y * P.W + x;
+        if (index) index[p] = (uint8_t)m;
+        if (pixels) pixels[p] = classify_entry(tf[m]);
+    }
+    if (INSTR) {
+        for (int o = 32; o > 0; o >>= 1) executed += __shfl_down(executed, o);
+        if (lane == 0 && executed) atomicAdd(counter, executed);
+        if (lane == 0 && slots) atomicAdd(counter + 1, slots);
+        if (kLayout == LAYOUT_BRICKED && lane == 0 && executed) atomicAdd(counter + 2, 1ull);
+        if (kLayout == LAYOUT_ZPAIR && lane == 0 && executed) atomicAdd(counter + 3, 1ull);
+    }
+}
+
+template <int VOXEL, bool TEX8, bool INSTR>
+static void launch_mip_t(const MarchArgs &a, hipStream_t s)
+{
+    const int ntx = a.strips.wr, ns = a.strips.s1 - a.strips.s0;
+    if (ntx <= 0 || ns <= 0) return;
+    unsigned nblocks = (unsigned)(ns * ntx);
+    if (a.strips.order) {
+        const int nseg = (ntx + a.strips.order_run - 1) / a.strips.order_run, units = ns * nseg;
+        nblocks = (unsigned)((units + 7) / 8 * 8 * a.strips.order_run);
+    } else if (a.strips.xcd_band > 0) {
+        const int nbands = (ns + a.strips.xcd_band - 1) / a.strips.xcd_band;
+        nblocks = (unsigned)(((nbands + 7) / 8) * 8 * a.strips.xcd_band * ntx);
+    }
+    // Blocks per CU: the launch policy's lds_reserve values were measured on march_kernel, whose blocks hold a 4 KB table in LDS besides
+    // the reserve.  mip_kernel has no LDS of its own, so the table's 4 KB are added to the reserve here: the same LDS per block, the same
+    // number of resident blocks per CU (and waves on its L1) as the march frame of the same view.
+    const size_t lds = (size_t)a.lds_reserve + kMipTableBytes;
+    dim3 grid(nblocks);
+    if (a.unroll == 3)
+        hipLaunchKernelGGL((mip_kernel<VOXEL, TEX8, INSTR, 3>), grid, dim3(256), lds, s,
+                           a.P, a.V, a.tf, a.rad, a.pixels, a.index, a.counter, a.I, a.strips);
+    else
+        hipLaunchKernelGGL((mip_kernel<VOXEL, TEX8, INSTR, 2>), grid, dim3(256), lds, s,
+                           a.P, a.V, a.tf, a.rad, a.pixels, a.index, a.counter, a.I, a.strips);
+}
+
+static void launch_mip_impl(const MarchArgs &a, hipStream_t s)
+{
+    const bool f32 = a.V_type == VV_VOXEL_F32;
+    if (a.instr) {
+        if (f32) { if (a.tex8) launch_mip_t<VV_VOXEL_F32, true, true>(a, s); else launch_mip_t<VV_VOXEL_F32, false, true>(a, s); }
+        else     { if (a.tex8) launch_mip_t<VV_VOXEL_U8,  true, true>(a, s); else launch_mip_t<VV_VOXEL_U8,  false, true>(a, s); }
+    } else {
+        if (f32) { if (a.tex8) launch_mip_t<VV_VOXEL_F32, true, false>(a, s); else launch_mip_t<VV_VOXEL_F32, false, false>(a, s); }
+        else     { if (a.tex8) launch_mip_t<VV_VOXEL_U8,  true, false>(a, s); else launch_mip_t<VV_VOXEL_U8,  false, false>(a, s); }
+    }
+}
+
+#if !defined(VV_ZPAIR) && !defined(VV_BRICKED) && !defined(VV_ZFAST) && !defined(VV_BIG_VOLUME)       // (once: the build for the linear layout)
+// The owned pixels outside the rectangle mip_kernel's tiles cover: their rays miss the volume (vv_render: screen_rect), so M = 0.
+// One thread per pixel of the frame; threads inside the rectangle, in column W-1 / row H-1 or in another shard's rows leave at once.
+__global__ __launch_bounds__(256) void mip_fill_kernel(FrameParams P, PixelRect R, const float4 *__restrict__ tf,
+                                                       uint32_t *__restrict__ pixels, uint8_t *__restrict__ index)
+{
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x > P.W - 2 || y > P.H - 2 || !row_owned(P, y)) return;
+    if (x >= R.x0 && x < R.x1 && y >= R.y0 && y < R.y1) return;
+    const size_t p = (size_t)y * P.W + x;
+    if (index) index[p] = 0;
+    if (pixels) pixels[p] = classify_entry(tf[0]);
+}
+
+__global__ __launch_bounds__(256) void mip_classify_kernel(const uint8_t *__restrict__ index, size_t n, const float4 *__restrict__ tf,
+                                                           uint32_t *__restrict__ pixels)
+{
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
+        pixels[i] = classify_entry(tf[index[i]]);
+}
+#endif
+
+} // namespace VV_BIG_NS
+
+#if defined(VV_ZPAIR) && defined(VV_XPAIR)
+void launch_mip_xpair(const MarchArgs &a, hipStream_t s) { xpair::launch_mip_impl(a, s); }
+#elif defined(VV_ZPAIR)
+void launch_mip_zpair(const MarchArgs &a, hipStream_t s) { zpair::launch_mip_impl(a, s); }
+#elif defined(VV_BRICKED) && defined(VV_BRICKED_CACHED)
+void launch_mip_bricked_cached(const MarchArgs &a, hipStream_t s) { brickc::launch_mip_impl(a, s); }
+#elif defined(VV_BRICKED)
+void launch_mip_bricked(const MarchArgs &a, hipStream_t s) { brick::launch_mip_impl(a, s); }
+#elif defined(VV_ZFAST)
+void launch_mip_zfast(const MarchArgs &a, hipStream_t s) { zfast::launch_mip_impl(a, s); }
+#elif defined(VV_BIG_VOLUME)
+void launch_mip_big(const MarchArgs &a, hipStream_t s) { big::launch_mip_impl(a, s); }
+#else
+void launch_mip(const MarchArgs &a, hipStream_t s) { small::launch_mip_impl(a, s); }
+void launch_mip_fill(const MarchArgs &a, const PixelRect &rect, hipStream_t s)
+{
+    if (a.P.W < 2 || a.P.H < 2) return;
+    dim3 grid((unsigned)((a.P.W - 1 + 63) / 64), (unsigned)((a.P.H - 1 + 3) / 4));
+    hipLaunchKernelGGL(small::mip_fill_kernel, grid, dim3(256), 0, s, a.P, rect, a.tf, a.pixels, a.index);
+}
+void launch_mip_classify(const uint8_t *index, size_t n, const float4 *tf, uint32_t *pixels, hipStream_t s)
+{
+    if (!n) return;
+    const size_t blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(small::mip_classify_kernel, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, s, index, n, tf, pixels);
+}
+#endif
+
+} // namespace vv

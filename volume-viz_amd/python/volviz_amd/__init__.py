@@ -83,7 +83,10 @@ EXPORTS = [
     "vv_prepare_layouts", "vv_set_layout_policy", "vv_layout_state", "vv_device_bytes", "vv_reread_env",
     "vv_load_volume_stream_begin", "vv_load_volume_stream_slices", "vv_load_volume_stream_end", "vv_load_volume_t3d",
     "vv_load_volume_stream_slices_async", "vv_load_volume_stream_wait_source", "vv_dataset_preset", "vv_debug_last_launch", "vv_set_frame_timing", "vv_debug_screen_rect",
+    "vv_render_mip", "vv_classify_indices",
 ]
+# entry points a variant library built from an earlier tree (A/B tools, load_library(path)) may lack
+_NEWER_EXPORTS = ("vv_render_mip", "vv_classify_indices")
 
 _lib = None
 _libs = {}
@@ -118,6 +121,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.vv_render.argtypes = [vp, i, i, C.POINTER(slice_params), C.POINTER(camera_params),
                               C.POINTER(shading_params), C.POINTER(vv_ray_source),
                               C.POINTER(vv_render_options), vp, i, vp]
+    if hasattr(lib, "vv_render_mip"):
+        lib.vv_render_mip.argtypes = [vp, i, i, C.POINTER(slice_params), C.POINTER(camera_params), C.POINTER(vv_ray_source),
+                                      C.POINTER(vv_render_options), vp, vp, i, vp]
+        lib.vv_classify_indices.argtypes = [vp, vp, sz, vp, vp, i, vp]
     lib.vv_slice.argtypes = [vp, vp, sz, sz, f, f, f, i, C.POINTER(f * 3), i, i, i, vp]
     lib.vv_slice_advanced.argtypes = [vp, vp, sz, sz, C.POINTER(f * 16), C.POINTER(f * 3), i, i, vp]
     lib.vv_generate_ellipsoids.argtypes = [vp, vp, i, i, i, i, i, vp, vp, vp, vp]
@@ -153,6 +160,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.vv_layout_state.argtypes = [vp, vp]
     lib.vv_volume_dims.argtypes = [vp, C.POINTER(i * 3), C.POINTER(i)]
     for name in EXPORTS:
+        if path is not None and name in _NEWER_EXPORTS and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)
         if name not in ("vv_last_error", "vv_last_frame_ms", "vv_last_sample_count"):
             fn.restype = i
@@ -393,6 +402,46 @@ class Context:
                                      C.byref(options) if options is not None else None,
                                      out_ptr, 1, stream))
 
+    # vv_render_mip / vv_classify_indices (no reference counterpart)
+    def render_mip(self, width: int, height: int, cam: Camera, *, slice: Optional[slice_params] = None,
+                   rays: Optional[vv_ray_source] = None, options: Optional[vv_render_options] = None,
+                   fill: int = 0, return_index: bool = False):
+        """Host-buffer maximum-intensity projection; returns rgba uint8 [H, W, 4] (row 0 = bottom), or (rgba, index uint8 [H, W])
+        with return_index.  Pixels the frame does not write keep `fill` in both images."""
+        out = np.full((height, width, 4), fill, np.uint8)
+        idx = np.full((height, width), fill, np.uint8) if return_index else None
+        sp = slice if slice is not None else make_slice_params()
+        cp = cam.params(width, height)
+        rs = rays if rays is not None else analytic_rays(cam)
+        self._chk(self.lib.vv_render_mip(self.h, width, height, C.byref(sp), C.byref(cp), C.byref(rs),
+                                         C.byref(options) if options is not None else None,
+                                         out.ctypes.data, idx.ctypes.data if return_index else None, 0, None))
+        return (out, idx) if return_index else out
+
+    def render_mip_device(self, width: int, height: int, cam: Camera, rgba_ptr: int = 0, index_ptr: int = 0, *, slice=None,
+                          rays=None, options=None, stream: int = 0):
+        """Device-buffer MIP frame enqueued on `stream` (a hipStream_t as int): rgba_ptr (W*H*4 bytes) and / or index_ptr (W*H bytes), 0 = not wanted."""
+        sp = slice if slice is not None else make_slice_params()
+        cp = cam.params(width, height)
+        rs = rays if rays is not None else analytic_rays(cam)
+        self._chk(self.lib.vv_render_mip(self.h, width, height, C.byref(sp), C.byref(cp), C.byref(rs),
+                                         C.byref(options) if options is not None else None,
+                                         rgba_ptr or None, index_ptr or None, 1, stream))
+
+    def classify_indices(self, index: np.ndarray, tf: Optional[np.ndarray] = None) -> np.ndarray:
+        """vv_classify_indices on a host index image (uint8, any shape): uint8 [..., 4] through `tf` (float32[1024]) or the context's table."""
+        index = np.ascontiguousarray(index, np.uint8)
+        out = np.zeros(index.shape + (4,), np.uint8)
+        t = None if tf is None else np.ascontiguousarray(tf, np.float32).reshape(1024)
+        self._chk(self.lib.vv_classify_indices(self.h, index.ctypes.data, index.size, None if t is None else t.ctypes.data,
+                                               out.ctypes.data, 0, None))
+        return out
+
+    def classify_indices_device(self, index_ptr: int, n: int, rgba_ptr: int, tf: Optional[np.ndarray] = None, stream: int = 0):
+        """vv_classify_indices on device buffers (n index bytes -> n * 4 RGBA bytes), enqueued on `stream`."""
+        t = None if tf is None else np.ascontiguousarray(tf, np.float32).reshape(1024)
+        self._chk(self.lib.vv_classify_indices(self.h, index_ptr, n, None if t is None else t.ctypes.data, rgba_ptr, 1, stream))
+
     def first_pass(self, img_w: int, img_h: int, cam: Camera):
         """vv_first_pass: the two RGBA8 FBO images of glwidget.cpp:200-228 for this camera."""
         front = np.zeros((img_h, img_w, 4), np.uint8); back = np.zeros((img_h, img_w, 4), np.uint8)
@@ -421,7 +470,7 @@ class Context:
         """vv_debug_last_launch: what the launch policy chose for the last render."""
         out = (C.c_int * 8)()
         self._chk(self.lib.vv_debug_last_launch(self.h, out))
-        k = ("tile_log2w", "blk_log2w", "unroll", "lds_reserve", "layout", "view_known", "density_x1000", "phong")
+        k = ("tile_log2w", "blk_log2w", "unroll", "lds_reserve", "layout", "view_known", "density_x1000", "phong")     # phong: 0 unshaded, 1 Phong, 2 MIP
         return dict(zip(k, list(out)))
 
     def reread_env(self):
