@@ -10,6 +10,9 @@ in 1..255 whose frame has alpha 255 at that pixel -- no pixel of the oracle has 
 in k); `assert_not_vacuous` adds the two conditions that keep a comparison against M from passing on an empty image."""
 from __future__ import annotations
 
+import contextlib
+import os
+
 import numpy as np
 
 import oracle_lib as O
@@ -64,3 +67,57 @@ def executed_samples(vol, W, H, cam, *, slice=None, rays=None, options_kw=None) 
     """What a frame executes when no ray ever terminates early: the oracle's count under an all-zero-opacity table."""
     _, n = O.render(vol, np.zeros(1024, np.float32), W, H, cam, slice=slice, rays=rays, options=vv.make_options(**dict(options_kw or {})))
     return n
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# helpers of the GPU comparisons (tests/test_mip_geometry.py)
+# ---------------------------------------------------------------------------------------------------------------------
+# every VV_* knob the library reads (vv_api.cpp: vv_knobs::read and the pitch knobs of the volume load)
+ALL_KNOBS = ("VV_TILE_LOG2W", "VV_XCD_BAND", "VV_UNROLL", "VV_LDS_RESERVE", "VV_LDS_RESERVE_PHONG", "VV_BRICKED", "VV_ZPAIR", "VV_BLOCK_W", "VV_TAIL",
+             "VV_ZFAST", "VV_FORCE_BIG", "VV_RECT", "VV_LPT", "VV_LPT_RUN", "VV_PHONG_BRICKS", "VV_PITCH_PAD", "VV_PITCH_FORCE", "VV_PITCH_ROWS")
+
+
+@contextlib.contextmanager
+def knobs(ctx, env):
+    """The VV_* knobs of `env` and no others, picked up by `ctx` (the knobs are read at volume load and by vv_reread_env, never per frame); the
+    environment the block found is put back at its end and re-read, so that no later test inherits a knob."""
+    saved = {k: os.environ.get(k) for k in ALL_KNOBS}
+    try:
+        for k in ALL_KNOBS:
+            os.environ.pop(k, None)
+        os.environ.update(env)
+        ctx.reread_env()
+        yield
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+        ctx.reread_env()
+
+
+def expect(M, written, tf, fill):
+    """The two images (rgba [H, W, 4], index [H, W]) a MIP frame over `fill` bytes must hold."""
+    idx = np.where(written, M, np.uint8(fill)).astype(np.uint8)
+    rgba = np.where(written[..., None], rgba_of(tf, M), np.uint8(fill)).astype(np.uint8)
+    return rgba, idx
+
+
+def assert_same(got, want, what):
+    assert got.shape == want.shape and got.dtype == want.dtype, what
+    bad = np.argwhere(got != want)
+    assert len(bad) == 0, f"{what}: {len(bad)} entries differ, first at {tuple(bad[0])}: {got[tuple(bad[0])]} vs {want[tuple(bad[0])]}"
+
+
+def assert_frame(ctx, M, written, tf, fill, W, H, cam, what, **kw):
+    """One GPU frame over `fill`, both images against the expectation, every pixel; returns (rgba, index)."""
+    rgba, idx = ctx.render_mip(W, H, cam, fill=fill, return_index=True, **kw)
+    want_rgba, want_idx = expect(M, written, tf, fill)
+    assert_same(idx, want_idx, f"{what}: index image")
+    assert_same(rgba, want_rgba, f"{what}: rgba")
+    return rgba, idx
+
+
+def share_and_levels(M):
+    return float((M > 0).mean()), len(np.unique(M))

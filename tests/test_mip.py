@@ -16,8 +16,17 @@ CAM_B = vv.Camera.orbit(1.2, 1.3, 2.0)
 CUT = dict(point=(.5, .5, .5), normal=(.3, .2, 1.))
 LAYOUT_KNOBS = ("VV_BRICKED", "VV_ZPAIR", "VV_ZFAST", "VV_FORCE_BIG", "VV_UNROLL")
 ENVS = ({}, {"VV_BRICKED": "1"}, {"VV_ZPAIR": "1"}, {"VV_ZFAST": "1"}, {"VV_FORCE_BIG": "1"}, {"VV_UNROLL": "2"})
-# the layout code vv_debug_last_launch reports for a forced knob on a view off the memory axes
-FORCED_LAYOUT = {"VV_BRICKED": (2,), "VV_ZPAIR": (3,), "VV_ZFAST": (4, 5), "VV_FORCE_BIG": (1,)}
+ZFAST_ONLY = {"VV_ZFAST": "1", "VV_ZPAIR": "0"}            # the z-fastest build itself: VV_ZFAST=1 alone takes the x-pair copy built from it
+
+
+def _forced_layout(env, default):
+    """The layout code vv_debug_last_launch must report for a knob set on a view off the memory axes; `default` is the policy's own choice."""
+    if env.get("VV_ZFAST") == "1":
+        return 4 if env.get("VV_ZPAIR") == "0" else 5
+    for knob, code in (("VV_BRICKED", 2), ("VV_ZPAIR", 3), ("VV_FORCE_BIG", 1)):
+        if env.get(knob) == "1":
+            return code
+    return default
 
 
 def _volume(name):
@@ -94,23 +103,23 @@ def _assert_same(got, want, what):
     assert len(bad) == 0, f"{what}: {len(bad)} entries differ, first at {tuple(bad[0])}: {got[tuple(bad[0])]} vs {want[tuple(bad[0])]}"
 
 
-# (name, volume, camera, W, H, filter, step, envs, check forced layouts)
+# (name, volume, camera, W, H, filter, step, envs, the layout the policy itself picks (None: forced layouts are not checked))
 PARITY = [
-    ("u8-tex8",        "noise_u8",  CAM_A, 99, 71, vv.FILTER_TEX8,  None,   ENVS, True),
-    ("f32-exact",      "noise_f32", CAM_B, 99, 71, vv.FILTER_EXACT, None,   ENVS, True),
+    ("u8-tex8",        "noise_u8",  CAM_A, 99, 71, vv.FILTER_TEX8,  None,   ENVS + (ZFAST_ONLY,), 0),
+    ("f32-exact",      "noise_f32", CAM_B, 99, 71, vv.FILTER_EXACT, None,   ENVS + (ZFAST_ONLY,), 0),
     # W, H == 1 (mod 14); 2 M voxels: the default policy itself takes the bricked copy for this view
-    ("brain128-1mod14", "brain128", CAM_A, 113, 85, vv.FILTER_TEX8, None,   ({}, {"VV_BRICKED": "1"}, {"VV_ZFAST": "1"}), True),
+    ("brain128-1mod14", "brain128", CAM_A, 113, 85, vv.FILTER_TEX8, None,   ({}, {"VV_BRICKED": "1"}, {"VV_ZFAST": "1"}, ZFAST_ONLY), 2),
     # along the memory axis (32 x 2 wave tiles, 3 samples per trip), a step that is not 1 / dims, an object scale != 1, a ragged frame
     ("f32-axis-step-scale", "noise_f32", vv.Camera(origin=(0.0, 0.0, -3.0), scale=(1.0, 0.8, 1.2)), 101, 67, vv.FILTER_TEX8, 1 / 50,
-     ({}, {"VV_ZPAIR": "1"}, {"VV_ZPAIR": "0", "VV_FORCE_BIG": "1"}, {"VV_ZPAIR": "0", "VV_UNROLL": "2"}, {"VV_BRICKED": "1"}), False),
-    ("u8-axis-exact",  "noise_u8",  vv.Camera(origin=(0.3, 0.2, -3.0)), 86, 57, vv.FILTER_EXACT, (1 / 40, 1 / 70, 1 / 33), ({}, {"VV_ZPAIR": "0"}, {"VV_FORCE_BIG": "1", "VV_ZPAIR": "0"}), False),
+     ({}, {"VV_ZPAIR": "1"}, {"VV_ZPAIR": "0", "VV_FORCE_BIG": "1"}, {"VV_ZPAIR": "0", "VV_UNROLL": "2"}, {"VV_BRICKED": "1"}), None),
+    ("u8-axis-exact",  "noise_u8",  vv.Camera(origin=(0.3, 0.2, -3.0)), 86, 57, vv.FILTER_EXACT, (1 / 40, 1 / 70, 1 / 33), ({}, {"VV_ZPAIR": "0"}, {"VV_FORCE_BIG": "1", "VV_ZPAIR": "0"}), None),
 ]
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", PARITY, ids=[c[0] for c in PARITY])
 def test_mip_matches_oracle_sweep(ctx, case, monkeypatch):
-    _, name, cam, W, H, filt, step, envs, check_layout = case
+    _, name, cam, W, H, filt, step, envs, policy_layout = case
     vol = _volume(name)
     okw = dict(filter=filt)
     if step is not None:
@@ -131,17 +140,17 @@ def test_mip_matches_oracle_sweep(ctx, case, monkeypatch):
             _assert_same(rgba, want_rgba, f"{case[0]} {env}: rgba")
             assert lay["phong"] == 2, lay                 # a MIP launch was reported
             layouts.add(lay["layout"])
-            if check_layout:
-                for k, codes in FORCED_LAYOUT.items():
-                    if env.get(k) == "1":
-                        assert lay["layout"] in codes, (env, lay)
+            if policy_layout is not None:
+                assert lay["layout"] == _forced_layout(env, policy_layout), (env, lay)
             if "VV_UNROLL" in env:
                 assert lay["unroll"] == int(env["VV_UNROLL"]), lay
             # one image at a time
             only_rgba = ctx.render_mip(W, H, cam, options=vv.make_options(**okw), fill=0x5A)
             _assert_same(only_rgba, want_rgba, f"{case[0]} {env}: rgba alone")
     if case[0] == "brain128-1mod14":
-        assert 2 in layouts and (4 in layouts or 5 in layouts), layouts
+        assert layouts == {2, 4, 5}, layouts
+    elif policy_layout is not None:
+        assert layouts == {0, 1, 2, 3, 4, 5}, layouts           # every kernel build, for this voxel type
 
 
 @pytest.mark.gpu
