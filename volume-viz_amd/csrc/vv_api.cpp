@@ -53,6 +53,7 @@ struct vv_context {
     vv_knobs knobs;
     hipStream_t stream = nullptr;          // used when the caller passes no stream
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipEvent_t ev_count = nullptr;               // recorded behind the last kernel of every instrumented frame: what the counter read-backs wait on
     bool timed = false, time_frames = true;      // vv_set_frame_timing
     // volume
     void *d_vol = nullptr; size_t vol_bytes = 0; int vtype = VV_VOXEL_U8; int nx = 0, ny = 0, nz = 0;
@@ -338,7 +339,7 @@ int vv_init(int device, vv_context **out)
     c->device = device;
     c->knobs.read();
     if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&c->stream) != hipSuccess ||
-        hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
+        hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess || hipEventCreateWithFlags(&c->ev_count, hipEventDisableTiming) != hipSuccess ||
         hipMalloc((void **)&c->d_counter, 16 * sizeof(unsigned long long)) != hipSuccess ||
         hipMalloc((void **)&c->d_tf, 256 * sizeof(float4)) != hipSuccess) {
         delete c;
@@ -375,6 +376,7 @@ int vv_shutdown(vv_context *c)
     if (c->promo_stream) hipStreamDestroy(c->promo_stream);
     if (c->ev0) hipEventDestroy(c->ev0);
     if (c->ev1) hipEventDestroy(c->ev1);
+    if (c->ev_count) hipEventDestroy(c->ev_count);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
     return VV_OK;
@@ -518,7 +520,7 @@ int vv_device_bytes(const vv_context *c, unsigned long long out[4])
 int vv_debug_counters(vv_context *c, unsigned long long out[16])
 {
     if (!c || !out || !c->counter_valid) return VV_ERR_INVALID;
-    if (hipEventSynchronize(c->ev1) != hipSuccess) return VV_ERR_DEVICE;
+    if (hipEventSynchronize(c->ev_count) != hipSuccess) return VV_ERR_DEVICE;
     if (hipMemcpy(out, c->d_counter, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return VV_ERR_DEVICE;
     return VV_OK;
 }
@@ -1248,6 +1250,7 @@ static int render_frame(vv_context *c, int W, int H, const slice_params *slice, 
         launch_march(A, st);
     }
     if (c->time_frames) HIPCHK(c, hipEventRecord(c->ev1, st));
+    if (A.instr) HIPCHK(c, hipEventRecord(c->ev_count, st));      // frame timing may be off, and the read-back's null-stream copy does not order behind a non-blocking stream
     HIPCHK(c, hipGetLastError());
     c->timed = c->time_frames;
     if (!out_on_device) {
@@ -1405,7 +1408,7 @@ unsigned long long vv_last_sample_count(vv_context *c)
     if (!c || !c->counter_valid) return 0;
     unsigned long long v = 0;
     hipSetDevice(c->device);
-    if (hipEventSynchronize(c->ev1) != hipSuccess) return 0;
+    if (hipEventSynchronize(c->ev_count) != hipSuccess) return 0;
     if (hipMemcpy(&v, c->d_counter, sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return 0;
     return v;
 }
