@@ -156,6 +156,17 @@ def test_product_does_not_reference_the_oracle():
                 assert "vvo_" not in txt and "libvvoracle" not in txt and "libvvref" not in txt, os.path.join(root, f)
 
 
+def test_tile_grid_walk():
+    """bin/tile_grid_check walks the tile grid of march_kernel / mip_kernel on the CPU through the functions of csrc/vv_tiles.h that the kernels, their launchers
+    and rad_kernel's table writer use: over small launches (1 ... 17 tile columns, 1 ... 9 strips, every block and wave-tile shape choose_launch reaches, XCD
+    bands, order tables of unit length 1, 5 and 64, sharded bands) every tile of the launch is marched by exactly one block, no block reads beyond the
+    order table, and the 256 threads of a block own 256 distinct pixels inside the block's rectangle."""
+    import subprocess
+    r = subprocess.run([os.path.join(REPO, "volume-viz_amd", "bin", "tile_grid_check")], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert " 0 failures" in r.stdout, r.stdout
+
+
 def _qt_perspective(fov_deg, aspect, n, f):
     c = 1.0 / np.tan(np.radians(fov_deg) / 2.0)
     return np.array([[c / aspect, 0, 0, 0], [0, c, 0, 0], [0, 0, -(f + n) / (f - n), -2 * f * n / (f - n)], [0, 0, -1, 0]])

@@ -210,7 +210,7 @@ def test_block_to_pixel_mapping_preconditions(ci):
 @pytest.mark.gpu
 @pytest.mark.parametrize("ci", range(len(MAP_CAMS)))
 def test_mip_block_to_pixel_mapping(ctx, ci):
-    """mip_kernel's own copy of the block -> (strip, tile) -> pixel mapping: the balanced tile order with several unit lengths, XCD bands, every block
+    """mip_kernel on the block -> (strip, tile) -> pixel mapping it shares with march_kernel (csrc/vv_tiles.h): the balanced tile order with several unit lengths, XCD bands, every block
     and wave-tile shape the knobs reach, with shards and row ranges; both images, the executed-sample count and the launch record."""
     vol, cam = _map_volume(), MAP_CAMS[ci]
     M, counts = _map_case(ci)

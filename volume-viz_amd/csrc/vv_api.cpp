@@ -7,6 +7,7 @@
 #include "../../include/volviz.h"
 #include "vv_kernels.h"
 
+#include <cassert>
 #include <hip/hip_runtime.h>
 #include <climits>
 #include <cmath>
@@ -953,31 +954,8 @@ static bool screen_rect(const MarchArgs &A, int W, int H, double *xmin, double *
     return true;
 }
 
-static void launch_march(const MarchArgs &A, hipStream_t st)
-{
-    switch (A.build) {
-    case MB_LINEAR:         launch_raymarch(A, st); break;
-    case MB_LINEAR_BIG:     launch_raymarch_big(A, st); break;
-    case MB_BRICKED:        launch_raymarch_bricked(A, st); break;
-    case MB_BRICKED_CACHED: launch_raymarch_bricked_cached(A, st); break;
-    case MB_ZPAIR:          launch_raymarch_zpair(A, st); break;
-    case MB_ZFAST:          launch_raymarch_zfast(A, st); break;
-    case MB_XPAIR:          launch_raymarch_xpair(A, st); break;
-    }
-}
-
-static void launch_mip_build(const MarchArgs &A, hipStream_t st)
-{
-    switch (A.build) {
-    case MB_LINEAR:         launch_mip(A, st); break;
-    case MB_LINEAR_BIG:     launch_mip_big(A, st); break;
-    case MB_BRICKED:        launch_mip_bricked(A, st); break;
-    case MB_BRICKED_CACHED: launch_mip_bricked_cached(A, st); break;
-    case MB_ZPAIR:          launch_mip_zpair(A, st); break;
-    case MB_ZFAST:          launch_mip_zfast(A, st); break;
-    case MB_XPAIR:          launch_mip_xpair(A, st); break;
-    }
-}
+static void launch_march(const MarchArgs &A, hipStream_t st) { assert(A.build < MB_COUNT); kLaunchRaymarch[A.build](A, st); }
+static void launch_mip_build(const MarchArgs &A, hipStream_t st) { assert(A.build < MB_COUNT); kLaunchMip[A.build](A, st); }
 
 // One frame: vv_render (mip = false: rgba_out, shading) and vv_render_mip (mip = true: rgba_out and / or index_out, never Phong).  Both share the
 // argument checks, the frame and shard set-up, the launch policy, the screen rectangle and the output staging; only the kernels differ.
@@ -1184,21 +1162,21 @@ static int render_frame(vv_context *c, int W, int H, const slice_params *slice, 
     if (rc) return rc;
     // Balanced, heaviest-first tile order (StripMap::order, built by rad_kernel's extra block): analytic rays (the weights are the centre rays' chords),
     // 8 ... 1024 units of at most 16 x-adjacent tiles.  VV_LPT=0 switches it off, VV_LPT_RUN sets the unit length.
-    A.strips.order = nullptr; A.order_out = nullptr; A.strips.order_run = 1;
+    // (units, their number and the table's size: vv_tiles.h)
+    A.strips.order = nullptr; A.order_out = nullptr;
     {
         const int wr = A.strips.wr, ns = A.strips.s1 - A.strips.s0;
-        int run = wr > 0 ? (wr + (wr + 15) / 16 - 1) / ((wr + 15) / 16) : 1;                  // the strip in ceil(wr / 16) equal runs
-        if (c->knobs.lpt_run > 0 && c->knobs.lpt_run <= 256) run = c->knobs.lpt_run;
-        const long long units = wr > 0 ? (long long)ns * ((wr + run - 1) / run) : 0;
+        A.strips.order_run = wr > 0 ? (wr + (wr + 15) / 16 - 1) / ((wr + 15) / 16) : 1;                  // the strip in ceil(wr / 16) equal runs
+        if (c->knobs.lpt_run > 0 && c->knobs.lpt_run <= 256) A.strips.order_run = c->knobs.lpt_run;
+        const int units = wr > 0 ? order_units(A.strips) : 0;
         // Measured (tools/ab_rep.sh, profiles/EXPERIMENTS.md part A5): aligned views of volumes up to 1 GiB gain 4 % (C2, 512^3, u8 1024^3); volumes beyond the
         // caches lose 1-6 % (the heaviest tiles marching together move more bytes), oblique views gain or lose up to 15 % with the camera: there the strips stay.
         const bool want = c->knobs.lpt > 0 ? true : (A.strips.tile_log2w == 5 && !beyond_caches && (long long)wr * ns >= 1024);      // (C1's 576 tiles: +2 %, the sort outlasts the rad pre-pass)
-        if (c->knobs.lpt != 0 && want && !A.phong && rays->mode == VV_RAYS_ANALYTIC && W >= 2 && H >= 2 && units >= 8 && units <= 1024 && (long long)(wr + 1) * (ns + 1) <= 24576) {
-            const size_t words = (size_t)((units + 7) / 8 * 8) * run;
-            rc = ensure(c, (void **)&c->d_order, &c->order_cap, std::max(words, (size_t)65536) * sizeof(uint32_t));
+        if (c->knobs.lpt != 0 && want && !A.phong && rays->mode == VV_RAYS_ANALYTIC && W >= 2 && H >= 2 && units >= 8 && units <= 1024 && (long long)(wr + 1) * (ns + 1) <= 24576) {     // (rad_kernel: kMaxUnits, kMaxPoints)
+            rc = ensure(c, (void **)&c->d_order, &c->order_cap, std::max((size_t)order_words(A.strips), (size_t)65536) * sizeof(uint32_t));
             if (rc) return rc;
-            A.strips.order = c->d_order; A.order_out = c->d_order; A.strips.order_run = run;
-        }
+            A.strips.order = c->d_order; A.order_out = c->d_order;
+        } else A.strips.order_run = 1;
     }
     A.rad = c->d_rad; A.rad_out = c->d_rad;
     A.counter = c->d_counter;

@@ -2,31 +2,27 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "vv_device.h"
+#include "vv_tiles.h"       // StripMap and the tile grid of march_kernel / mip_kernel
 
 namespace vv {
 
-// blockIdx.y -> pixel strip (march_kernel) / slab row (march_phong_kernel) of a shard
-struct StripMap { int y0, strips_per_band, band_stride_px, tile_log2w, n_strips, xcd_band;
-                  int tail_batch;     // march_kernel: chunks that hold at most one sample per lane (rays past the ERT threshold) are taken U at a time
-                  int blk_log2w;      // a block covers 2^blk_log2w x (256 >> blk_log2w) pixels (5: 32 x 8; 32 x 2 tiles also 64 x 4 / 128 x 2, 8 x 8 tiles 16 x 16 / 8 x 32); strips are that high
-                  // march_kernel launches the tiles of columns [tx0, tx0 + wr) of strips [s0, s1) only: the tiles under the volume's screen rectangle
-                  // (vv_render: screen_rect) -- or all of them: tx0 = 0, wr = tile columns of the frame, s0 = 0, s1 = n_strips
-                  int tx0, wr, s0, s1;
-                  // order != nullptr: block L marches the tile in slot ((j / order_run) * 8 + L % 8) * order_run + j % order_run, j = L / 8, of a table that
-                  // rad_kernel's extra block writes (see there): runs of order_run x-adjacent tiles, sorted by the time their rays spend in the cube and dealt
-                  // to the XCDs so that all of them carry the same load and end on their lightest runs (speed only).
-                  const uint32_t *order; int order_run; };
-// the same rectangle in pixels: [x0, x1) x [y0, y1).  Every owned pixel outside it is a pixel whose ray misses the volume: rad_kernel writes its 0,
+// the rectangle of a StripMap / SlabMap launch in pixels: [x0, x1) x [y0, y1).  Every owned pixel outside it is a pixel whose ray misses the volume: rad_kernel writes its 0,
 // and computes no radius for slabs that do not meet the rectangle (march_kernel, which reads them, is not launched there).  No rectangle: x1 = y1 = INT_MAX.
 struct PixelRect { int x0, x1, y0, y1; };
 
+// blockIdx.x -> slab of a shard (march_phong_kernel)
 struct SlabMap  { int r0, band, band_stride, n_regular;
                   // march_phong_kernel launches slab columns [gx0, gx0 + wg) of the grid rows [gs0, gs1) and the extra row n_regular (pin 10): the slabs under the
                   // volume's screen rectangle, or all of them (gx0 = 0, wg = nbx, gs0 = 0, gs1 = n_regular)
                   int gx0, wg, gs0, gs1; };
 
-// the build of the march kernels a frame runs: one per launch_raymarch_* entry point below
-enum MarchBuild : uint8_t { MB_LINEAR, MB_LINEAR_BIG, MB_BRICKED, MB_BRICKED_CACHED, MB_ZPAIR, MB_ZFAST, MB_XPAIR };
+// the build of the march kernels a frame runs: vv_raymarch.hip and vv_mip.hip are compiled once for each (vv_layout.h: kBuild)
+// (the list generates the enum and the launcher tables below, so their orders cannot part: MB_LINEAR_BIG volumes above 4 GiB, MB_BRICKED on VolumeView::bricks,
+//  MB_BRICKED_CACHED the same for volumes up to 1 GiB, MB_ZPAIR on VolumeView::zpair, MB_ZFAST on VolumeView::zfast, MB_XPAIR on the x-pair copy, handed over in VolumeView::zpair)
+#define VV_FOR_EACH_BUILD(X) X(MB_LINEAR) X(MB_LINEAR_BIG) X(MB_BRICKED) X(MB_BRICKED_CACHED) X(MB_ZPAIR) X(MB_ZFAST) X(MB_XPAIR)
+#define VV_X(B) B,
+enum MarchBuild : uint8_t { VV_FOR_EACH_BUILD(VV_X) MB_COUNT };
+#undef VV_X
 
 struct MarchArgs {
     FrameParams P;
@@ -51,23 +47,23 @@ struct MarchArgs {
     InstrArgs I;                // bitmaps of an instrumented frame (vv_render_options::touched_bricks / touched_lines)
 };
 
+// The march and MIP launchers, one explicit specialisation per build, each defined by the unit compiled for that build; kLaunchRaymarch[b] / kLaunchMip[b]
+// is the launcher of MarchBuild b.  rad_kernel (the pre-pass of both), mip_fill_kernel and mip_classify_kernel live in the linear build's units.
+template <MarchBuild B> void launch_raymarch(const MarchArgs &a, hipStream_t s);
+template <MarchBuild B> void launch_mip(const MarchArgs &a, hipStream_t s);
+#define VV_X(B) template <> void launch_raymarch<B>(const MarchArgs &, hipStream_t); template <> void launch_mip<B>(const MarchArgs &, hipStream_t);
+VV_FOR_EACH_BUILD(VV_X)
+#undef VV_X
+using MarchLauncher = void (*)(const MarchArgs &, hipStream_t);
+#define VV_X(B) launch_raymarch<B>,
+constexpr MarchLauncher kLaunchRaymarch[] = { VV_FOR_EACH_BUILD(VV_X) };
+#undef VV_X
+#define VV_X(B) launch_mip<B>,
+constexpr MarchLauncher kLaunchMip[] = { VV_FOR_EACH_BUILD(VV_X) };
+#undef VV_X
+static_assert(sizeof(kLaunchRaymarch) / sizeof(MarchLauncher) == MB_COUNT && sizeof(kLaunchMip) / sizeof(MarchLauncher) == MB_COUNT, "one launcher per build");
 void launch_rad(const MarchArgs &a, hipStream_t s);
-void launch_raymarch(const MarchArgs &a, hipStream_t s);
-void launch_raymarch_big(const MarchArgs &a, hipStream_t s);      // same kernels, volumes above 4 GiB
-void launch_raymarch_bricked(const MarchArgs &a, hipStream_t s);  // same kernels on VolumeView::bricks
-void launch_raymarch_bricked_cached(const MarchArgs &a, hipStream_t s);  // ... the build for volumes up to 1 GiB
-void launch_raymarch_zpair(const MarchArgs &a, hipStream_t s);    // same kernels on VolumeView::zpair
-void launch_raymarch_zfast(const MarchArgs &a, hipStream_t s);    // same kernels on VolumeView::zfast
-void launch_raymarch_xpair(const MarchArgs &a, hipStream_t s);    // same kernels on the x-pair copy (handed over in VolumeView::zpair)
-// maximum-intensity projection (vv_mip.hip): one build per layout like the march kernels; rad_kernel is its pre-pass too
 constexpr int kMipTableBytes = 4096;      // march_kernel's LDS table, which mip_kernel does not have: added to lds_reserve so that the blocks per CU stay what the policy measured
-void launch_mip(const MarchArgs &a, hipStream_t s);
-void launch_mip_big(const MarchArgs &a, hipStream_t s);
-void launch_mip_bricked(const MarchArgs &a, hipStream_t s);
-void launch_mip_bricked_cached(const MarchArgs &a, hipStream_t s);
-void launch_mip_zpair(const MarchArgs &a, hipStream_t s);
-void launch_mip_zfast(const MarchArgs &a, hipStream_t s);
-void launch_mip_xpair(const MarchArgs &a, hipStream_t s);
 void launch_mip_fill(const MarchArgs &a, const PixelRect &rect, hipStream_t s);      // M = 0 for the owned pixels outside `rect` (both images)
 void launch_mip_classify(const uint8_t *index, size_t n, const float4 *tf, uint32_t *pixels, hipStream_t s);   // pixels[i] = RGBA8 of tf[index[i]]
 void launch_build_xpair(int vtype, const void *zfast, uint32_t zf_row_bytes, uint64_t zf_slice_bytes, void *xpair, int nx, int ny, int nz, hipStream_t s);

@@ -2,30 +2,41 @@
 //
 // vv_raymarch.hip and vv_mip.hip are each compiled seven times (their *_big / *_brick / *_brick_cached / *_zpair / *_zfast / *_xpair
 // wrappers define VV_BIG_VOLUME / VV_BRICKED (+ VV_BRICKED_CACHED) / VV_ZPAIR / VV_ZFAST / VV_ZPAIR + VV_XPAIR).  This header turns those
-// macros into the unit's namespace (VV_BIG_NS), its layout constant, its corner registers and fetch, and the line marking of instrumented frames.
+// macros -- here and nowhere else -- into the unit's namespace (VV_BIG_NS), its build (kBuild: the launcher specialisation it defines), its layout constant
+// (kLayout; two builds share the bricked layout), its corner registers and fetch, and the instrumentation of instrumented frames.  The unit for the
+// linear layout, which also holds the kernels that exist once (rad_kernel, mip_fill_kernel, mip_classify_kernel), sees VV_BUILD_LINEAR.
 #pragma once
 #include "vv_device.h"
+#include "vv_kernels.h"
 
 #if defined(VV_ZPAIR) && defined(VV_XPAIR)
 #define VV_BIG_NS xpair
+constexpr vv::MarchBuild kBuild = vv::MB_XPAIR;
 constexpr int kLayout = vv::LAYOUT_ZPAIR;
 #elif defined(VV_ZPAIR)
 #define VV_BIG_NS zpair
+constexpr vv::MarchBuild kBuild = vv::MB_ZPAIR;
 constexpr int kLayout = vv::LAYOUT_ZPAIR;
 #elif defined(VV_BRICKED) && defined(VV_BRICKED_CACHED)
 #define VV_BIG_NS brickc
+constexpr vv::MarchBuild kBuild = vv::MB_BRICKED_CACHED;
 constexpr int kLayout = vv::LAYOUT_BRICKED;
 #elif defined(VV_BRICKED)
 #define VV_BIG_NS brick
+constexpr vv::MarchBuild kBuild = vv::MB_BRICKED;
 constexpr int kLayout = vv::LAYOUT_BRICKED;
 #elif defined(VV_ZFAST)
 #define VV_BIG_NS zfast
+constexpr vv::MarchBuild kBuild = vv::MB_ZFAST;
 constexpr int kLayout = vv::LAYOUT_ZFAST;
 #elif defined(VV_BIG_VOLUME)
 #define VV_BIG_NS big
+constexpr vv::MarchBuild kBuild = vv::MB_LINEAR_BIG;
 constexpr int kLayout = vv::LAYOUT_LINEAR_BIG;
 #else
 #define VV_BIG_NS small
+#define VV_BUILD_LINEAR
+constexpr vv::MarchBuild kBuild = vv::MB_LINEAR;
 constexpr int kLayout = vv::LAYOUT_LINEAR;
 #endif
 
@@ -87,6 +98,31 @@ __device__ __noinline__ void mark_sample_lines(const InstrArgs &I, const VolumeV
         }
     }
 #endif
+}
+
+// Instrumented frames only: one sample of march_kernel / mip_kernel, `live` when its lane executes it.  Counts it, marks its 8^3 bricks when it lies in
+// the volume, and the lines its gathers touch (InstrArgs::lines_all: those of idle lanes and out-of-volume samples too).
+template <int VOXEL, bool TEX8>
+__device__ __forceinline__ void instrument_sample(const InstrArgs &I, const VolumeView &V, float tx, float ty, float tz, bool live, unsigned long long &executed)
+{
+    const bool inv = bounds_check(tx, ty, tz);
+    if (live) {
+        executed++;
+        if (I.bricks && inv) mark_bricks(I.bricks, V, tx, ty, tz);
+    }
+    if ((I.lines || I.pairs) && (I.lines_all || (live && inv))) mark_sample_lines<VOXEL, TEX8>(I, V, tx, ty, tz);
+}
+
+// Instrumented frames only, at the end of a kernel: counter[0] += the wave's executed samples, counter[1] += its lane slots (developer statistic: lane
+// utilisation; march_phong_kernel has none), counter[2] / counter[3] += 1 per wave that sampled the bricked / the z-pair copy.
+__device__ __forceinline__ void flush_counters(unsigned long long *__restrict__ counter, unsigned long long executed, unsigned long long slots)
+{
+    const bool first = (threadIdx.x & 63) == 0;
+    for (int o = 32; o > 0; o >>= 1) executed += __shfl_down(executed, o);
+    if (first && executed) atomicAdd(counter, executed);
+    if (first && slots) atomicAdd(counter + 1, slots);
+    if (kLayout == LAYOUT_BRICKED && first && executed) atomicAdd(counter + 2, 1ull);
+    if (kLayout == LAYOUT_ZPAIR && first && executed) atomicAdd(counter + 3, 1ull);
 }
 
 } // namespace VV_BIG_NS

@@ -5,10 +5,10 @@
 // index -- and keeps, per pixel, the largest index M over the samples it executes (0 when it executes none).  No table look-up, no
 // blend, no early-termination state: the ray state and the U samples in flight live in registers, the per-sample work behind the
 // trilinear reconstruction is one v_max_u32, and the transfer table is read once per pixel, in the epilogue.
-//   * mip_kernel           the march: wave tiles, block order and trip structure of march_kernel (vv_raymarch.hip);
+//   * mip_kernel           the march: trip structure of march_kernel (vv_raymarch.hip), on the tile grid both share (vv_tiles.h: block order, wave tiles, launch size);
 //   * mip_fill_kernel      the pixels beside the volume's screen rectangle (M = 0), which mip_kernel's tiles do not cover;
 //   * mip_classify_kernel  index image -> RGBA through a table (vv_classify_indices).
-// Like vv_raymarch.hip this file is compiled once per volume layout (vv_layout.h), through the vv_mip_*.hip wrappers.
+// Like vv_raymarch.hip this file is compiled once per volume layout (vv_layout.h), through the vv_mip_*.hip wrappers; each unit defines launch_mip<kBuild>.
 #include "vv_device.h"
 #include "vv_kernels.h"
 #include "vv_layout.h"
@@ -19,7 +19,7 @@ namespace VV_BIG_NS {
 // channel c of an RGBA pixel = sat_u8(clamp(tf[M][c], 0, 1) * 255): pack_rgba's conversion of a table entry
 __device__ __forceinline__ uint32_t classify_entry(const float4 e) { return pack_rgba(e.x, e.y, e.z, e.w); }
 
-// blockDim = 256 = 4 waves; block -> (strip, tile) and wave -> pixels exactly as in march_kernel (StripMap).  `pixels` and `index`
+// blockDim = 256 = 4 waves; block -> (strip, tile) and wave -> pixels through vv_tiles.h, as in march_kernel.  `pixels` and `index`
 // may each be null (vv_render_mip wants at least one).  Uninstrumented frames drop a ray once its maximum is 255 (nothing can raise
 // it); instrumented frames march every ray to its end so that the count is the full executed count.
 template <int VOXEL, bool TEX8, bool INSTR, int U>
@@ -31,25 +31,11 @@ __global__ __launch_bounds__(256) void mip_kernel(FrameParams P, VolumeView V,
                                                   unsigned long long *__restrict__ counter,
                                                   InstrArgs I, StripMap M)
 {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int bl = M.blk_log2w, ntx = M.wr;
-    int strip, tile_x;
-    if (M.order) {
-        const int L = blockIdx.x, xcd = L & 7, j = L >> 3, pos = ((j / M.order_run) * 8 + xcd) * M.order_run + j % M.order_run;
-        const uint32_t t = M.order[pos];                              // (the grid is exactly the table)
-        if (t == ~0u) return;
-        strip = M.s0 + (int)t / ntx; tile_x = M.tx0 + (int)t % ntx;
-    } else if (M.xcd_band > 0) {
-        const int L = blockIdx.x, per_band = ntx * M.xcd_band;
-        const int xcd = L & 7, j = L >> 3;
-        const int band = (j / per_band) * 8 + xcd, w = j % per_band;
-        strip = M.s0 + band * M.xcd_band + w / ntx; tile_x = M.tx0 + w % ntx;
-    } else { strip = M.s0 + blockIdx.x / ntx; tile_x = M.tx0 + blockIdx.x % ntx; }
-    const int tw = M.tile_log2w, th = 6 - tw;
-    const int wx = wave & (((1 << bl) >> tw) - 1), wy = wave >> (bl - tw);
-    const int x = (tile_x << bl) + (wx << tw) + (lane & ((1 << tw) - 1));
-    const int y = M.y0 + (strip / M.strips_per_band) * M.band_stride_px + (strip % M.strips_per_band) * (256 >> bl) + (wy << th) + (lane >> tw);
+    int strip, tile_x, x, y;
+    if (!block_tile(M, blockIdx.x, strip, tile_x)) return;
+    tile_pixel(M, strip, tile_x, threadIdx.x, x, y);
     if (strip >= M.s1) return;
+
     // pixels no frame writes: column W-1 / row H-1 (W,H >= 2), rows of other shards
     const int xmax = P.W >= 2 ? P.W - 2 : 0, ymax = P.H >= 2 ? P.H - 2 : 0;
     const bool in_frame = x <= xmax && y <= ymax && row_owned(P, y);
@@ -110,14 +96,7 @@ __global__ __launch_bounds__(256) void mip_kernel(FrameParams P, VolumeView V,
                 const bool live = i0 + u <= n;
                 const uint32_t k = classify_index<VOXEL>(C[u], tx[u], ty[u], tz[u]);
                 m = max(m, live ? k : 0u);
-                if (INSTR) {
-                    const bool inv = bounds_check(tx[u], ty[u], tz[u]);
-                    if (live) {
-                        executed++;
-                        if (I.bricks && inv) mark_bricks(I.bricks, V, tx[u], ty[u], tz[u]);
-                    }
-                    if ((I.lines || I.pairs) && (I.lines_all || (live && inv))) mark_sample_lines<VOXEL, TEX8>(I, V, tx[u], ty[u], tz[u]);
-                }
+                if (INSTR) instrument_sample<VOXEL, TEX8>(I, V, tx[u], ty[u], tz[u], live, executed);
             }
         }
         if (!INSTR && m == 255u) r.upper = -1.f;
@@ -132,28 +111,14 @@ __global__ __launch_bounds__(256) void mip_kernel(FrameParams P, VolumeView V,
         if (index) index[p] = (uint8_t)m;
         if (pixels) pixels[p] = classify_entry(tf[m]);
     }
-    if (INSTR) {
-        for (int o = 32; o > 0; o >>= 1) executed += __shfl_down(executed, o);
-        if (lane == 0 && executed) atomicAdd(counter, executed);
-        if (lane == 0 && slots) atomicAdd(counter + 1, slots);
-        if (kLayout == LAYOUT_BRICKED && lane == 0 && executed) atomicAdd(counter + 2, 1ull);
-        if (kLayout == LAYOUT_ZPAIR && lane == 0 && executed) atomicAdd(counter + 3, 1ull);
-    }
+    if (INSTR) flush_counters(counter, executed, slots);
 }
 
 template <int VOXEL, bool TEX8, bool INSTR>
 static void launch_mip_t(const MarchArgs &a, hipStream_t s)
 {
-    const int ntx = a.strips.wr, ns = a.strips.s1 - a.strips.s0;
-    if (ntx <= 0 || ns <= 0) return;
-    unsigned nblocks = (unsigned)(ns * ntx);
-    if (a.strips.order) {
-        const int nseg = (ntx + a.strips.order_run - 1) / a.strips.order_run, units = ns * nseg;
-        nblocks = (unsigned)((units + 7) / 8 * 8 * a.strips.order_run);
-    } else if (a.strips.xcd_band > 0) {
-        const int nbands = (ns + a.strips.xcd_band - 1) / a.strips.xcd_band;
-        nblocks = (unsigned)(((nbands + 7) / 8) * 8 * a.strips.xcd_band * ntx);
-    }
+    const unsigned nblocks = grid_blocks(a.strips);
+    if (!nblocks) return;
     // Blocks per CU: the launch policy's lds_reserve values were measured on march_kernel, whose blocks hold a 4 KB table in LDS besides
     // the reserve.  mip_kernel has no LDS of its own, so the table's 4 KB are added to the reserve here: the same LDS per block, the same
     // number of resident blocks per CU (and waves on its L1) as the march frame of the same view.
@@ -179,7 +144,7 @@ static void launch_mip_impl(const MarchArgs &a, hipStream_t s)
     }
 }
 
-#if !defined(VV_ZPAIR) && !defined(VV_BRICKED) && !defined(VV_ZFAST) && !defined(VV_BIG_VOLUME)       // (once: the build for the linear layout)
+#ifdef VV_BUILD_LINEAR       // (once: the build for the linear layout)
 // The owned pixels outside the rectangle mip_kernel's tiles cover: their rays miss the volume (vv_render: screen_rect), so M = 0.
 // One thread per pixel of the frame; threads inside the rectangle, in column W-1 / row H-1 or in another shard's rows leave at once.
 __global__ __launch_bounds__(256) void mip_fill_kernel(FrameParams P, PixelRect R, const float4 *__restrict__ tf,
@@ -203,20 +168,8 @@ __global__ __launch_bounds__(256) void mip_classify_kernel(const uint8_t *__rest
 
 } // namespace VV_BIG_NS
 
-#if defined(VV_ZPAIR) && defined(VV_XPAIR)
-void launch_mip_xpair(const MarchArgs &a, hipStream_t s) { xpair::launch_mip_impl(a, s); }
-#elif defined(VV_ZPAIR)
-void launch_mip_zpair(const MarchArgs &a, hipStream_t s) { zpair::launch_mip_impl(a, s); }
-#elif defined(VV_BRICKED) && defined(VV_BRICKED_CACHED)
-void launch_mip_bricked_cached(const MarchArgs &a, hipStream_t s) { brickc::launch_mip_impl(a, s); }
-#elif defined(VV_BRICKED)
-void launch_mip_bricked(const MarchArgs &a, hipStream_t s) { brick::launch_mip_impl(a, s); }
-#elif defined(VV_ZFAST)
-void launch_mip_zfast(const MarchArgs &a, hipStream_t s) { zfast::launch_mip_impl(a, s); }
-#elif defined(VV_BIG_VOLUME)
-void launch_mip_big(const MarchArgs &a, hipStream_t s) { big::launch_mip_impl(a, s); }
-#else
-void launch_mip(const MarchArgs &a, hipStream_t s) { small::launch_mip_impl(a, s); }
+template <> void launch_mip<kBuild>(const MarchArgs &a, hipStream_t s) { VV_BIG_NS::launch_mip_impl(a, s); }
+#ifdef VV_BUILD_LINEAR
 void launch_mip_fill(const MarchArgs &a, const PixelRect &rect, hipStream_t s)
 {
     if (a.P.W < 2 || a.P.H < 2) return;

@@ -21,7 +21,7 @@
 // that live in the caches), through vv_raymarch_zpair.hip with VV_ZPAIR (volume sampled from the z-pair copy) and through
 // vv_raymarch_zfast.hip with VV_ZFAST (volume sampled from the z-fastest copy: side views) and through vv_raymarch_xpair.hip with
 // VV_ZPAIR + VV_XPAIR (the z-pair build on the x-pair copy: side views of small / u8 volumes),
-// so that each path pays only for itself.  The builds for cache-resident volumes (this file as is, z-pair, brick_cached)
+// so that each path pays only for itself (vv_layout.h names the build; each unit defines launch_raymarch<kBuild>).  The builds for cache-resident volumes (this file as is, z-pair, brick_cached)
 // are compiled with -fno-slp-vectorize: the packed-f32 code the SLP vectoriser makes of the lerps costs a v_mov per
 // operand pair, which VALU-bound frames pay for (C2 -6 %, C1 -4 %, 512^3 -4 %, C2 rotated -6.5 %, Phong -3 ... -6 %),
 // while the builds for volumes beyond the caches are 0.5-3 % (rotated + Phong 9 %) faster with it (Makefile).
@@ -40,9 +40,7 @@ namespace VV_BIG_NS {
 // edge made by a face seen at a grazing angle the chord jumps from 0 to the face's length, and a tile whose centre misses the cube can hold the frame's longest rays.)
 __device__ __forceinline__ int point_life_class(const FrameParams &P, const StripMap &M, int gx, int gy)
 {
-    const int bl = M.blk_log2w, bh = 256 >> bl;
-    const int strip = M.s0 + gy, tile_x = M.tx0 + gx;
-    const float x = (float)(tile_x << bl) - 0.5f, y = (float)(M.y0 + (strip / M.strips_per_band) * M.band_stride_px + (strip % M.strips_per_band) * bh) - 0.5f;
+    const float x = (float)((M.tx0 + gx) << M.blk_log2w) - 0.5f, y = (float)strip_row(M, M.s0 + gy) - 0.5f;
     const float sx = ((2.0f * (x + 0.5f)) / (float)P.W - 1.0f) * P.tan_half_x, sy = ((2.0f * (y + 0.5f)) / (float)P.H - 1.0f) * P.tan_half_y;
     float tmin = 0.f, tmax = INFINITY, d2 = 0.f, s2 = 0.f;
     bool miss = false;
@@ -66,21 +64,20 @@ __global__ __launch_bounds__(256) void rad_kernel(FrameParams P, float *__restri
         // The extra block: StripMap::order.  Units = runs of order_run x-adjacent tiles of a strip (the tiles that share cache lines stay together, on one
         // XCD); a unit weighs what its tiles' centre rays spend inside the cube.  Units sorted by weight (heaviest first; rank sort, ties in raster order)
         // are dealt to the XCDs to and fro (0..7, 7..0, ...): every XCD gets the same load to within one light unit and ends on its lightest ones.
-        // Table slot ((r * 8 + xcd) * run + i) holds tile i of the r-th unit of that XCD, or ~0 (a unit shorter than a run, the last round).
+        // Units, the table's slots and its size are defined in vv_tiles.h (order_*); render_frame asks for the table only where the units and corners fit below.
         __shared__ uint32_t w[kMaxUnits];
         __shared__ uint8_t pts[kMaxPoints];
-        const int run = M.order_run, nseg = (M.wr + run - 1) / run, ns = M.s1 - M.s0, U = ns * nseg, n = M.wr * ns;
-        const int rounds = (U + 7) / 8;
+        const int cols = M.wr, rows = M.s1 - M.s0, run = M.order_run, nseg = order_units_per_row(M), U = order_units(M), n = cols * rows;
         for (int i = threadIdx.x; i < U; i += 256) w[i] = 0;
-        for (int i = threadIdx.x; i < rounds * 8 * run; i += 256) order[i] = ~0u;
+        for (int i = threadIdx.x; i < order_words(M); i += 256) order[i] = ~0u;
         __syncthreads();
         {
             // a tile weighs what the longest of its four corner rays spends in the cube
-            const int gw = M.wr + 1, np = gw * (ns + 1);
+            const int gw = cols + 1, np = gw * (rows + 1);
             for (int i = threadIdx.x; i < np; i += 256) pts[i] = (uint8_t)point_life_class(P, M, i % gw, i / gw);
             __syncthreads();
             for (int t = threadIdx.x; t < n; t += 256) {
-                const int tx = t % M.wr, ty = t / M.wr;
+                const int tx = t % cols, ty = t / cols;
                 const int c = min(min((int)pts[ty * gw + tx], (int)pts[ty * gw + tx + 1]), min((int)pts[(ty + 1) * gw + tx], (int)pts[(ty + 1) * gw + tx + 1]));
                 atomicAdd(&w[ty * nseg + tx / run], 64u - (uint32_t)c);
             }
@@ -91,9 +88,9 @@ __global__ __launch_bounds__(256) void rad_kernel(FrameParams P, float *__restri
             int rank = 0;
             for (int v = 0; v < U; ++v) { const uint32_t wv = w[v]; rank += (wv > wu || (wv == wu && v < u)) ? 1 : 0; }
             const int c = rank & 7, r = rank >> 3, xcd = (r & 1) ? 7 - c : c;
-            const int strip_l = u / nseg, x0 = (u % nseg) * run, size = min(run, M.wr - x0);
-            uint32_t *dst = order + (size_t)(r * 8 + xcd) * run;
-            for (int i = 0; i < size; ++i) dst[i] = (uint32_t)(strip_l * M.wr + x0 + i);
+            const int row = u / nseg, x0 = (u % nseg) * run, size = min(run, cols - x0);
+            uint32_t *dst = order + order_slot(M, r, xcd, 0);
+            for (int i = 0; i < size; ++i) dst[i] = (uint32_t)(row * cols + x0 + i);
         }
         return;
     }
@@ -152,7 +149,8 @@ __device__ __forceinline__ void stage_tf(float4 *lds_tf, const float4 *__restric
 // march_kernel: no Phong.  blockDim = 256 = 4 waves; a block owns a 32x8 pixel strip (64x4 / 128x2 with StripMap::blk_log2w 6 / 7), each
 // wave a 2^tw x 2^(6-tw) tile of it (32x2 when screen x runs along the volume's x axis, so
 // that the lanes of a gather walk one memory row; 8x8 otherwise).  blockIdx.x enumerates
-// (strip, tile) pairs of the shard (StripMap).
+// (strip, tile) pairs of the shard: the grid -- plain raster, XCD bands or rad_kernel's order table (order_run) -- is defined in vv_tiles.h,
+// which mip_kernel (vv_mip.hip) shares.
 //
 // Tuning (MI355X, measured, profiles/EXPERIMENTS.md part B section 4): the kernel lives off the 32 KB L1 of its CU
 // (lanes of one gather share sectors, consecutive rows of a wave share lines), so FEWER resident
@@ -172,29 +170,11 @@ __global__ __launch_bounds__(256) void march_kernel(FrameParams P, VolumeView V,
 #ifdef VV_TIMELINE
     const unsigned long long tl0 = wall_clock64();
 #endif
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int bl = M.blk_log2w, ntx = M.wr;                               // block = 2^bl x (256 >> bl) pixels; the launch covers ntx tile columns from M.tx0 on
-    int strip, tile_x;
-    if (M.order) {
-        // runs of order_run consecutive tiles of the list go to one XCD (block L runs on XCD L % 8): x-neighbours share an L2 as in the strip order below
-        const int L = blockIdx.x, xcd = L & 7, j = L >> 3, pos = ((j / M.order_run) * 8 + xcd) * M.order_run + j % M.order_run;
-        const uint32_t t = M.order[pos];                              // (the grid is exactly the table)
-        if (t == ~0u) return;                                         // block-uniform, before any barrier
-        strip = M.s0 + (int)t / ntx; tile_x = M.tx0 + (int)t % ntx;
-    } else if (M.xcd_band > 0) {
-        // XCD-aware order (speed only): linear block L runs on XCD L % 8 (round-robin dispatch);
-        // XCD k walks bands k, k+8, ... of xcd_band strips so that neighbouring tiles share an L2
-        const int L = blockIdx.x, per_band = ntx * M.xcd_band;
-        const int xcd = L & 7, j = L >> 3;
-        const int band = (j / per_band) * 8 + xcd, w = j % per_band;
-        strip = M.s0 + band * M.xcd_band + w / ntx; tile_x = M.tx0 + w % ntx;
-    } else { strip = M.s0 + blockIdx.x / ntx; tile_x = M.tx0 + blockIdx.x % ntx; }
-    // wave tile = 2^tw x 2^(6-tw) pixels; the 4 waves of a block tile a 32x8 strip
-    const int tw = M.tile_log2w, th = 6 - tw;
-    const int wx = wave & (((1 << bl) >> tw) - 1), wy = wave >> (bl - tw);
-    const int x = (tile_x << bl) + (wx << tw) + (lane & ((1 << tw) - 1));
-    const int y = M.y0 + (strip / M.strips_per_band) * M.band_stride_px + (strip % M.strips_per_band) * (256 >> bl) + (wy << th) + (lane >> tw);
-    if (strip >= M.s1) return;                             // block-uniform, before any barrier
+    // block -> (strip, tile column) -> pixel: vv_tiles.h
+    int strip, tile_x, x, y;
+    if (!block_tile(M, blockIdx.x, strip, tile_x)) return;            // block-uniform, before any barrier
+    tile_pixel(M, strip, tile_x, threadIdx.x, x, y);
+    if (strip >= M.s1) return;                                        // block-uniform, before any barrier
     // The table entry this thread stages is loaded now and parked in LDS behind the ray set-up (which needs no table): its latency hides behind
     // the set-up's divisions instead of standing in front of them (blockDim.x == 256 == entries: every launch of this kernel).  C3 -0.6 %, C2 -1.1 %.
     const float4 tf_entry = tf[threadIdx.x];
@@ -303,14 +283,7 @@ __global__ __launch_bounds__(256) void march_kernel(FrameParams P, VolumeView V,
                     float d = fabsf(sn.x * (vx - sp.x) + sn.y * (vy - sp.y) + sn.z * (vz - sp.z));
                     if (d < .01f) cr = fmaxf(0.f, fminf(cr + (.01f - d) * 100.f, 1.f));
                 }
-                if (INSTR) {
-                    const bool inv = bounds_check(tx[u], ty[u], tz[u]);
-                    if (live) {
-                        executed++;
-                        if (I.bricks && inv) mark_bricks(I.bricks, V, tx[u], ty[u], tz[u]);
-                    }
-                    if ((I.lines || I.pairs) && (I.lines_all || (live && inv))) mark_sample_lines<VOXEL, TEX8>(I, V, tx[u], ty[u], tz[u]);
-                }
+                if (INSTR) instrument_sample<VOXEL, TEX8>(I, V, tx[u], ty[u], tz[u], live, executed);
                 {
 #pragma clang fp contract(off)
                     const float bf = (live && ca > kEps) ? ca * (1.f - res_a) : 0.f;
@@ -365,14 +338,7 @@ __global__ __launch_bounds__(256) void march_kernel(FrameParams P, VolumeView V,
                     float d = fabsf(sn.x * (vx - sp.x) + sn.y * (vy - sp.y) + sn.z * (vz - sp.z));
                     if (d < .01f) cr = fmaxf(0.f, fminf(cr + (.01f - d) * 100.f, 1.f));
                 }
-                if (INSTR) {
-                    const bool inv = bounds_check(tx[u], ty[u], tz[u]);
-                    if (live) {
-                        executed++;
-                        if (I.bricks && inv) mark_bricks(I.bricks, V, tx[u], ty[u], tz[u]);
-                    }
-                    if ((I.lines || I.pairs) && (I.lines_all || (live && inv))) mark_sample_lines<VOXEL, TEX8>(I, V, tx[u], ty[u], tz[u]);
-                }
+                if (INSTR) instrument_sample<VOXEL, TEX8>(I, V, tx[u], ty[u], tz[u], live, executed);
                 {
                     // :268-270 + blend :107-118, predicated: with bf == 0 the sums are unchanged
                     // bit for bit (the table is finite: vv_set_transfer_function rejects NaN/Inf)
@@ -408,13 +374,7 @@ __global__ __launch_bounds__(256) void march_kernel(FrameParams P, VolumeView V,
         }
     }
 #endif
-    if (INSTR) {
-        for (int o = 32; o > 0; o >>= 1) executed += __shfl_down(executed, o);
-        if (lane == 0 && executed) atomicAdd(counter, executed);
-        if (lane == 0 && slots) atomicAdd(counter + 1, slots);      // developer statistic: lane utilisation
-        if (kLayout == LAYOUT_BRICKED && lane == 0 && executed) atomicAdd(counter + 2, 1ull);   // waves that sampled the bricked copy
-        if (kLayout == LAYOUT_ZPAIR && lane == 0 && executed) atomicAdd(counter + 3, 1ull);     // ... the z-pair copy
-    }
+    if (INSTR) flush_counters(counter, executed, slots);
 }
 
 // x / d and sqrt(x), IEEE-exact, without their range handling.  The compiler's expansion of `/` and sqrtf is a fixed core (v_rcp + one
@@ -718,12 +678,7 @@ __global__ __launch_bounds__(256) VV_PHONG_OCC void march_phong_kernel(FramePara
         t[3] = (__builtin_amdgcn_s_getreg((3 << 11) | 20) & 15u) | 256u | ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) << 16);
     }
 #endif
-    if (INSTR) {
-        for (int o = 32; o > 0; o >>= 1) executed += __shfl_down(executed, o);
-        if ((threadIdx.x & 63) == 0 && executed) atomicAdd(counter, executed);
-        if (kLayout == LAYOUT_BRICKED && (threadIdx.x & 63) == 0 && executed) atomicAdd(counter + 2, 1ull);
-        if (kLayout == LAYOUT_ZPAIR && (threadIdx.x & 63) == 0 && executed) atomicAdd(counter + 3, 1ull);
-    }
+    if (INSTR) flush_counters(counter, executed, 0ull);
 }
 
 // ---------------------------------------------------------------------------
@@ -732,16 +687,8 @@ __global__ __launch_bounds__(256) VV_PHONG_OCC void march_phong_kernel(FramePara
 template <int SLICE, int VOXEL, bool TEX8, bool GRAY, bool INSTR>
 static void launch_march(const MarchArgs &a, hipStream_t s)
 {
-    const int ntx = a.strips.wr, ns = a.strips.s1 - a.strips.s0;          // the tiles under the volume's screen rectangle (StripMap)
-    if (ntx <= 0 || ns <= 0) return;
-    unsigned nblocks = (unsigned)(ns * ntx);
-    if (a.strips.order) {
-        const int nseg = (ntx + a.strips.order_run - 1) / a.strips.order_run, units = ns * nseg;
-        nblocks = (unsigned)((units + 7) / 8 * 8 * a.strips.order_run);          // (rad_kernel's table: rounds of 8 units)
-    } else if (a.strips.xcd_band > 0) {
-        const int nbands = (ns + a.strips.xcd_band - 1) / a.strips.xcd_band;
-        nblocks = (unsigned)(((nbands + 7) / 8) * 8 * a.strips.xcd_band * ntx);
-    }
+    const unsigned nblocks = grid_blocks(a.strips);                       // the tiles under the volume's screen rectangle (vv_tiles.h)
+    if (!nblocks) return;
     dim3 grid(nblocks);
     // a.lds_reserve bytes of (unused) dynamic LDS cap the number of resident blocks per CU:
     // fewer waves share the 32 KB L1, which this gather kernel needs more than latency hiding
@@ -799,21 +746,9 @@ static void launch_raymarch_impl(const MarchArgs &a, hipStream_t s)
 
 } // namespace VV_BIG_NS
 
-#if defined(VV_ZPAIR) && defined(VV_XPAIR)
-void launch_raymarch_xpair(const MarchArgs &a, hipStream_t s) { xpair::launch_raymarch_impl(a, s); }
-#elif defined(VV_ZPAIR)
-void launch_raymarch_zpair(const MarchArgs &a, hipStream_t s) { zpair::launch_raymarch_impl(a, s); }
-#elif defined(VV_BRICKED) && defined(VV_BRICKED_CACHED)
-void launch_raymarch_bricked_cached(const MarchArgs &a, hipStream_t s) { brickc::launch_raymarch_impl(a, s); }
-#elif defined(VV_BRICKED)
-void launch_raymarch_bricked(const MarchArgs &a, hipStream_t s) { brick::launch_raymarch_impl(a, s); }
-#elif defined(VV_ZFAST)
-void launch_raymarch_zfast(const MarchArgs &a, hipStream_t s) { zfast::launch_raymarch_impl(a, s); }
-#elif defined(VV_BIG_VOLUME)
-void launch_raymarch_big(const MarchArgs &a, hipStream_t s) { big::launch_raymarch_impl(a, s); }
-#else
+template <> void launch_raymarch<kBuild>(const MarchArgs &a, hipStream_t s) { VV_BIG_NS::launch_raymarch_impl(a, s); }
+#ifdef VV_BUILD_LINEAR
 void launch_rad(const MarchArgs &a, hipStream_t s) { small::launch_rad_impl(a, s); }
-void launch_raymarch(const MarchArgs &a, hipStream_t s) { small::launch_raymarch_impl(a, s); }
 #endif
 
 } // namespace vv
