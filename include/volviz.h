@@ -170,12 +170,21 @@ const char *vv_last_error(const vv_context *ctx);   /* ctx may be NULL (global e
 
 /* ---- volume + transfer function: replaces cudaLoadVolume (kernel.cuh:53, kernel.cu:456-498).
  * texels: host pointer, nx*ny*nz voxels, x fastest.  tf: 256 RGBA float entries.
- * Reloading frees the previous volume (the reference leaks it).                 */
+ * Reloading frees the previous volume (the reference leaks it).
+ *
+ * Value domain of f32 voxels (every call below that takes or produces VV_VOXEL_F32 data: vv_load_volume_f32,
+ * vv_load_volume_device, the vv_load_volume_stream_* calls, vv_load_volume_t3d): finite, |v| <= 2^126.  Inside it every
+ * difference the trilinear lerps form is finite, so the weight-0 corner the kernels fetch beside an edge texel contributes
+ * exactly nothing and results do not depend on the layout (bit-exact, tests/test_witness.py).  The library does not scan
+ * the volume.  An out-of-domain voxel (Inf, NaN, |v| > 2^126) makes unspecified the samples that lie within one voxel of
+ * it and, on the linear layouts, the samples in the outer half-voxel shell of the row or slice that ends just before it in
+ * memory; no other sample is affected, and no access leaves the allocation: addresses come from coordinates, never
+ * from voxel values.                                                            */
 int  vv_load_volume_u8 (vv_context *ctx, const uint8_t *texels, size_t size,
                         int nx, int ny, int nz, const float tf[1024]);
 int  vv_load_volume_f32(vv_context *ctx, const float *texels, size_t size,
                         int nx, int ny, int nz, const float tf[1024]);
-/* Same, from a buffer already resident in HBM (e.g. written by vv_generate_*). */
+/* Same, from a buffer already resident in HBM (e.g. written by vv_generate_*); f32 voxels: the value domain above. */
 int  vv_load_volume_device(vv_context *ctx, const void *dev_texels, int voxel_type,
                            int nx, int ny, int nz, const float tf[1024], void *stream);
 int  vv_set_transfer_function(vv_context *ctx, const float tf[1024]);
@@ -186,7 +195,8 @@ int  vv_set_transfer_function(vv_context *ctx, const float tf[1024]);
  * memory, through a pinned double buffer otherwise) and returns; src_type may be VV_VOXEL_U8
  * while the volume is VV_VOXEL_F32, in which case the slices are promoted (v/255) on the
  * device.  end waits for the copies.  Slices may arrive in any order.  A slices call returns once the source
- * buffer has been read (pinned sources are copied from directly), so the caller may refill it at once.          */
+ * buffer has been read (pinned sources are copied from directly), so the caller may refill it at once.
+ * f32 slices: the value domain above (promoted u8 slices are inside it by construction).                            */
 int  vv_load_volume_stream_begin(vv_context *ctx, int voxel_type, int nx, int ny, int nz,
                                  const float tf[1024]);
 int  vv_load_volume_stream_slices(vv_context *ctx, const void *src, int src_type, int z0, int nslices);
@@ -198,7 +208,8 @@ int  vv_load_volume_stream_slices(vv_context *ctx, const void *src, int src_type
 int  vv_load_volume_stream_slices_async(vv_context *ctx, const void *src, int src_type, int z0, int nslices);
 int  vv_load_volume_stream_wait_source(vv_context *ctx);
 int  vv_load_volume_stream_end(vv_context *ctx);
-/* .t3d file -> device volume in chunks (never holds the file in memory); voxel_type F32 promotes. */
+/* .t3d file -> device volume in chunks (never holds the file in memory); voxel_type F32 promotes (v/255: inside the
+ * f32 value domain above). */
 int  vv_load_volume_t3d(vv_context *ctx, const char *path, int header, int voxel_type,
                         const float tf[1024]);
 

@@ -5,7 +5,11 @@ CPU half (unmarked): the oracle against the witness, byte for byte, on one list 
 arithmetic models must differ from the witness on the same cases, or the list is too tame to catch a subtly wrong kernel.
 
 GPU half (`gpu`): the HIP kernels against the witness directly, on every layout build.  The oracle appears in no assertion
-there."""
+there.
+
+The value domain of f32 voxels (include/volviz.h: finite, |v| <= 2^126) is held from both sides: cases on volumes at the ends of the domain and a
+table of edge values must be bit-exact like every other case; a planted block of out-of-domain voxels must leave every pixel that cannot see it
+unchanged (CPU twin: test_planted_block_leaves_enough_pixels)."""
 from __future__ import annotations
 
 import ast
@@ -21,6 +25,8 @@ import pytest
 import oracle_lib as O
 import volviz_amd as vv
 import witness as Wt
+
+f32 = np.float32
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden")
@@ -41,7 +47,66 @@ def volume(name):
         return (rng.random((12, 12, 12), dtype=np.float32) * np.float32(1.3) - np.float32(0.1)).astype(np.float32)
     if name == "thin":                                          # 1 x 7 x 5: both texels of the x axis clamp to one
         return rng.integers(0, 256, (5, 7, 1), dtype=np.uint8)
+    if name in ("ends9", "ends20", "clean20", "planted20a", "planted20b"):
+        return ends_volume(name)
     raise KeyError(name)
+
+
+# f32 voxels at the ends of binary32 (include/volviz.h: finite, |v| <= 2^126).  The kernels fetch the memory neighbour of an edge texel and give it
+# weight 0 where this model (and the oracle) clamp the index: with every difference of two voxels finite, fma(0, b - a, a) is a and the two agree.
+BIG = [f32(1e30), f32(-1e30), f32(2.0 ** 126), f32(-2.0 ** 126)]
+
+
+def value_pool():
+    q = lambda k: f32(k) / f32(255)
+    pool = [f32(0.0), f32(-0.0), np.uint32(1).view(f32), np.uint32(0x007FFFFF).view(f32), np.finfo(f32).tiny,
+            f32(1.0), f32(256) / f32(255), f32(-1e-30)] + BIG
+    for k in (1, 127, 128, 254, 255):
+        pool += [np.nextafter(q(k), f32(-np.inf)), np.nextafter(q(k), f32(np.inf))]
+    pool += [q(1)]
+    return np.array(pool, f32)
+
+
+def boundary_parts(shape):
+    """Every face, edge and corner of a [nz, ny, nx] volume as a boolean mask."""
+    idx = np.indices(shape)
+    lo = [idx[a] == 0 for a in range(3)]; hi = [idx[a] == shape[a] - 1 for a in range(3)]
+    side = lambda a, s: hi[a] if s else lo[a]
+    parts = {}
+    for a in range(3):
+        for sa in (0, 1):
+            parts[f"face{a}{sa}"] = side(a, sa)
+            for b in range(a + 1, 3):
+                for sb in (0, 1):
+                    parts[f"edge{a}{sa}{b}{sb}"] = side(a, sa) & side(b, sb)
+    for c in range(8):
+        parts[f"corner{c}"] = side(0, c & 1) & side(1, (c >> 1) & 1) & side(2, c >> 2)
+    return parts
+
+
+def ends_volume(name):
+    rng = np.random.default_rng({"ends9": 9, "ends20": 20}.get(name, 2020))
+    shape = (6, 7, 9) if name == "ends9" else (5, 9, 20)
+    if name in ("clean20", "planted20a", "planted20b"):         # in-domain noise; planted: a 2 x 2 x 1 block of out-of-domain voxels, two voxels or more from every face
+        v = (rng.random(shape, dtype=np.float32) * f32(1.3) - f32(0.1)).astype(f32)
+        if name != "clean20":
+            v[PLANT_Z, PLANT_Y:PLANT_Y + 2, PLANT_X:PLANT_X + 2] = np.array(PLANTED[name[-1]], f32)
+        return v
+    pool = value_pool()
+    v = pool[rng.integers(0, len(pool), shape)]
+    big = np.array(BIG, f32)[rng.integers(0, len(BIG), shape)]
+    parts = boundary_parts(shape)
+    surface = parts["face00"] | parts["face01"] | parts["face10"] | parts["face11"] | parts["face20"] | parts["face21"]
+    corners = np.zeros(shape, bool)
+    for k, m in parts.items():
+        if k.startswith("corner"):
+            corners |= m
+    put = (surface & (rng.random(shape) < 0.5)) | corners       # at least a quarter of every face, edge and corner: test_extreme_volumes_are_as_described
+    return np.where(put, big, v).astype(f32)
+
+
+PLANT_X, PLANT_Y, PLANT_Z = 9, 4, 2                             # the block's lowest voxel
+PLANTED = {"a": [[np.inf, -np.inf], [np.nan, 3e38]], "b": [[-3e38, 3e38], [-np.inf, np.nan]]}       # (+-3e38 side by side: their difference overflows)
 
 
 @functools.lru_cache(maxsize=None)
@@ -57,6 +122,15 @@ def table(name):
     if name == "wild":                                          # opacities outside [0, 1] (-0.1 .. 1.5): no one-sample shortcut (pin 4)
         t = rng.random((256, 4), dtype=np.float32) * np.float32(1.6) - np.float32(0.3)
         t[:, 3] = rng.random(256, dtype=np.float32) ** 4 * np.float32(1.6) - np.float32(0.1)
+        return t.astype(np.float32).reshape(1024)
+    if name == "edge":                                          # denormal, -0.0 and > 1 colours; opacities at the threshold 1e-6 (binary32) and one ulp to either side
+        t = rng.random((256, 4), dtype=np.float32)
+        t[:, 3] = t[:, 3] ** 4
+        kind = rng.integers(0, 6, (256, 3))
+        t[:, :3] = np.select([kind == 0, kind == 1, kind == 2], [f32(1e-40), f32(-0.0), f32(1.5)], t[:, :3])
+        eps = f32(1e-6)
+        ak = rng.integers(0, 6, 256)
+        t[:, 3] = np.select([ak == 0, ak == 1, ak == 2], [eps, np.nextafter(eps, f32(1)), np.nextafter(eps, f32(0))], t[:, 3])
         return t.astype(np.float32).reshape(1024)
     raise KeyError(name)
 
@@ -96,9 +170,22 @@ CASES = [
     case("white", 1, 9, "axis", (1, 1, 1), N, None, EX, TRUE, .5, "wild"),
     case("noise", 30, 17, "axis", (1, 1, 1), N, None, T8, REF, .95, "random", phong=True),
 ]
+# f32 voxels at the range ends (in domain: the kernels must equal the witness bit for bit) ...
+N_PLAIN = len(CASES)
+for _vi, _vol in enumerate(("ends9", "ends20")):
+    for _ci, _cam in enumerate(("axis", "orbit", "side")):
+        for _fi, _filt in enumerate((T8, EX)):
+            _W, _H = ((30, 17), (16, 15))[(_vi + _ci + _fi) % 2]
+            CASES.append(case(_vol, _W, _H, _cam, (1, 1, .8) if _ci == 1 else (1, 1, 1), (N, P, C)[(_ci + _fi) % 3], None, _filt, REF, .95, "random", phong=True))
+ENDS = list(range(N_PLAIN, len(CASES)))
+# ... and the same frames through a transfer table with denormal, -0.0 and > 1 colours and opacities at kEps +- 1 ulp (unshaded and MIP)
+for _i in ENDS:
+    CASES.append(dict(CASES[_i], tf="edge", phong=False))
+EDGE_TF = list(range(ENDS[-1] + 1, len(CASES)))
 IDS = [f"{i}-{c['vol']}-{c['W']}x{c['H']}-{c['cam']}" for i, c in enumerate(CASES)]
 PHONG = [i for i, c in enumerate(CASES) if c["phong"]]
 MIP = [1, 6, 7, 14]
+MIP_ENDS = ENDS + EDGE_TF
 FILL = 0x5A
 
 
@@ -238,6 +325,30 @@ def test_oracle_equals_witness_phong(i):
     assert (want != witness_frame(i)[0]).any(), "Phong changes nothing on this case"
 
 
+def test_extreme_volumes_are_as_described():
+    """The f32 volumes at the range ends: big enough for interior and edge bricks on every layout build, every value finite and within 2^126, every pool
+    value present, and at least a quarter of the voxels of every face, edge and corner of magnitude >= 1e30."""
+    for name, shape in (("ends9", (6, 7, 9)), ("ends20", (5, 9, 20))):
+        v = volume(name)
+        assert v.shape == shape and v.dtype == np.float32
+        assert np.isfinite(v).all() and np.abs(v).max() == f32(2.0 ** 126)
+        for part, mask in boundary_parts(shape).items():
+            assert (np.abs(v[mask]) >= f32(1e30)).mean() >= 0.25, (name, part)
+    both = np.concatenate([volume("ends9").ravel(), volume("ends20").ravel()])
+    assert set(value_pool().view(np.uint32).tolist()) <= set(both.view(np.uint32).tolist())
+    t = table("edge").reshape(256, 4)
+    eps = f32(1e-6)
+    for a in (eps, np.nextafter(eps, f32(1)), np.nextafter(eps, f32(0))):
+        assert (t[:, 3] == a).sum() >= 8
+    assert (t[:, :3] > 1).any() and (t[:, :3].view(np.uint32) == 0x80000000).any() and ((t[:, :3] > 0) & (t[:, :3] < np.finfo(f32).tiny)).any()
+    assert len(ENDS) == 12 and len(EDGE_TF) == 12
+    for want in ("axis", "orbit", "side"):
+        for filt in (T8, EX):
+            for vol in ("ends9", "ends20"):
+                assert any(CASES[i]["cam"] == want and CASES[i]["filt"] == filt and CASES[i]["vol"] == vol for i in ENDS)
+    assert {(CASES[i]["W"], CASES[i]["H"]) for i in ENDS} == {(30, 17), (16, 15)}
+
+
 def test_phong_cases_are_at_least_six():
     assert len(PHONG) >= 6
 
@@ -255,7 +366,7 @@ def test_integer_texture_path_equals_the_fma_path():
     assert samples > 100000
 
 
-@pytest.mark.parametrize("i", MIP, ids=[IDS[i] for i in MIP])
+@pytest.mark.parametrize("i", MIP + MIP_ENDS, ids=[IDS[i] for i in MIP + MIP_ENDS])
 def test_mip_oracle_equals_witness(i):
     import mip_oracle as MO
     c = CASES[i]; cam, kw = product_args(i)
@@ -268,7 +379,7 @@ def test_mip_oracle_equals_witness(i):
     same(idx, want_idx, IDS[i] + ": index image")
     same(rgba, want_rgba, IDS[i] + ": rgba")
     assert n == MO.executed_samples(volume(c["vol"]), c["W"], c["H"], cam, slice=sl, rays=kw["rays"], options_kw=okw)
-    assert len(np.unique(idx)) >= 20
+    assert len(np.unique(idx)) >= (20 if i in MIP else 3)         # (voxels at the range ends mostly saturate the index)
 
 
 def test_slices_oracle_equals_witness():
@@ -307,6 +418,86 @@ def test_other_arithmetic_models_differ_from_the_witness():
         if c["vol"] in ("noise", "white") and c["filt"] == T8:
             assert differ["textrunc"][i] > 0, f"textrunc does not show on {IDS[i]}"
     assert max(differ["fmad"]) > 0 and max(differ["fast"]) > 0, differ
+
+
+# Out-of-domain voxels stay local (include/volviz.h: an Inf, a NaN or a |v| > 2^126 makes unspecified the samples within one voxel of it and nothing else).
+# Which pixels cannot see the planted block, from the witness's rays in binary64: every sample position of every chunk the ray starts (entries 0 and 31,
+# which only a gradient reads, included) lies more than two voxels from each planted voxel along at least one axis -- the trilinear footprint of such a
+# sample, the weight-0 neighbour the kernels fetch included, cannot contain the voxel.  (Read as "along all three axes at once" the rule would keep no
+# sample of a volume five voxels deep; two voxels along one axis is twice what the footprint needs.)
+LOCAL = [dict(cam="axis", filt=T8, scale=(1, 1, 1)), dict(cam="orbit", filt=EX, scale=(1, 1, .8))]
+LOCAL_W, LOCAL_H = 30, 17
+
+
+@functools.lru_cache(maxsize=None)
+def far_pixels(k, phong):
+    """(kept [H, W], meets [H, W]): pixels whose ray meets the volume, and those of them held to equality."""
+    c = LOCAL[k]; kc = CAMS[c["cam"]]
+    cam = vv.Camera(origin=kc.origin, look_at=kc.look_at, up=kc.up, fov_y=kc.fov_y, scale=c["scale"])
+    W, H = LOCAL_W, LOCAL_H
+    nz, ny, nx = volume("clean20").shape
+    R = Wt.frame_rays(W, H)
+    front, back = Wt.analytic_endpoints(W, H, R["x"], R["y"], cam.origin, cam.look(), cam.up, cam.fov_y, cam.scale)
+    step = f32(1) / np.array([nx, ny, nz], f32)
+    Wt.setup(R, front, back, cam.origin, step, N, (*PLANE["point"], *PLANE["normal"]))
+    o, d, sd = (R[key].astype(np.float64) for key in ("origin", "dir", "sdir"))
+    sstep, upper = R["sstep"].astype(np.float64), R["upper"].astype(np.float64)
+    inv_scale = 1.0 / np.asarray(c["scale"], np.float64)
+    planted = [(PLANT_X + dx, PLANT_Y + dy, PLANT_Z) for dx in (0, 1) for dy in (0, 1)]
+    n = len(R["x"])
+    with np.errstate(all="ignore"):
+        meets = ~R["dead"] & (0.0 < upper) & np.isfinite(d).all(axis=1)
+        safe = np.ones(n, bool)
+        dist = np.zeros(n)
+        while (meets & (dist < upper)).any():
+            run = meets & (dist < upper)
+            for i in range(32):
+                pos = o + d * dist[:, None] + sd * i
+                vox = ((pos - 0.5) * inv_scale + 0.5) * np.array([nx, ny, nz], np.float64) - 0.5
+                for pv in planted:
+                    near = (np.abs(vox - np.array(pv, np.float64)) <= 2.0).all(axis=1)
+                    safe &= ~(run & near)
+            dist = dist + sstep * 30.0
+    if phong:                                                   # the four neighbour rays of the same slab's footprint, held to the same rule
+        base = np.arange(n) - (R["sy"] * R["fw"] + R["sx"])
+        all_safe = safe.copy()
+        for dx, dy in ((-1, 0), (1, 0), (0, 1), (0, -1)):
+            sx = np.clip(R["sx"] + dx, 0, R["fw"] - 1); sy = np.clip(R["sy"] + dy, 0, R["fh"] - 1)
+            all_safe &= safe[base + sy * R["fw"] + sx]
+        safe = all_safe
+    own = R["owned"]
+    kept = np.zeros((H, W), bool); met = np.zeros((H, W), bool)
+    met[R["y"][own], R["x"][own]] = meets[own]
+    kept[R["y"][own], R["x"][own]] = meets[own] & safe[own]
+    return kept, met
+
+
+@functools.lru_cache(maxsize=None)
+def clean_frame(k, phong=False, mip=False):
+    c = LOCAL[k]; kc = CAMS[c["cam"]]
+    out = Wt.render(volume("clean20"), table("random"), LOCAL_W, LOCAL_H, cam_origin=kc.origin, look=vv.Camera(origin=kc.origin, look_at=kc.look_at).look(),
+                    up=kc.up, fov_y=kc.fov_y, scale=c["scale"], phong=phong, filt=c["filt"], fill=FILL, mip=mip)
+    for a in out[:-1]:
+        a.setflags(write=False)
+    return out
+
+
+@pytest.mark.parametrize("phong", [False, True])
+@pytest.mark.parametrize("k", range(len(LOCAL)))
+def test_planted_block_leaves_enough_pixels(k, phong):
+    """Precondition of the GPU tests below, from the witness alone: the block is two voxels or more from every face, the kept pixels are at least 30 % of
+    the pixels whose rays meet the volume, some pixels are NOT kept (the block is in view), and the clean frame is not flat on the kept ones."""
+    nz, ny, nx = volume("clean20").shape
+    assert 2 <= PLANT_X and PLANT_X + 1 <= nx - 3 and 2 <= PLANT_Y and PLANT_Y + 1 <= ny - 3 and 2 <= PLANT_Z <= nz - 3
+    for name in ("planted20a", "planted20b"):
+        bad = ~np.isfinite(volume(name)) | (np.abs(volume(name)) > f32(2.0 ** 126))
+        assert bad.sum() == 4 and bad[PLANT_Z, PLANT_Y:PLANT_Y + 2, PLANT_X:PLANT_X + 2].all()
+        assert np.array_equal(volume(name)[~bad], volume("clean20")[~bad])
+    kept, met = far_pixels(k, phong)
+    assert met.sum() >= 100
+    assert kept.sum() >= 0.3 * met.sum(), (int(kept.sum()), int(met.sum()))
+    assert (met & ~kept).sum() >= 10
+    assert len(np.unique(clean_frame(k, phong=phong)[0][kept], axis=0)) >= 20
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -367,7 +558,7 @@ def test_phong_kernel_equals_witness(ctx, monkeypatch, knobs_restored, i, build)
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("build", list(BUILDS))
-@pytest.mark.parametrize("i", MIP, ids=[IDS[i] for i in MIP])
+@pytest.mark.parametrize("i", MIP + MIP_ENDS, ids=[IDS[i] for i in MIP + MIP_ENDS])
 def test_mip_kernel_equals_witness(ctx, monkeypatch, knobs_restored, i, build):
     c = CASES[i]; cam, kw = product_args(i)
     want_rgba, want_idx, n_want, _ = witness_frame(i, mip=True)
@@ -436,3 +627,54 @@ def test_sample_count_waits_for_an_enqueued_frame_without_frame_timing(ctx):
         s.synchronize()
         ctx.set_frame_timing(True)
     assert n == n_want
+
+
+def local_camera(k):
+    c = LOCAL[k]; kc = CAMS[c["cam"]]
+    return vv.Camera(origin=kc.origin, look_at=kc.look_at, up=kc.up, fov_y=kc.fov_y, scale=c["scale"])
+
+
+def written_everywhere(frame, met, what):
+    assert not (frame[met] == FILL).all(axis=-1).any(), f"{what}: a pixel whose ray meets the volume was not written"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("build", list(BUILDS))
+@pytest.mark.parametrize("variant", ["a", "b"])
+@pytest.mark.parametrize("k", range(len(LOCAL)))
+def test_out_of_domain_voxels_stay_local(ctx, monkeypatch, knobs_restored, k, variant, build):
+    """+-Inf, NaN and +-3e38 planted in a 2 x 2 x 1 block: every pixel that cannot see the block (far_pixels) is byte for byte the clean volume's, unshaded
+    and MIP, on every layout build; the clean frame is the witness's.  The other pixels are written, nothing more is asked of them."""
+    cam = local_camera(k); kept, met = far_pixels(k, False)
+    kw = dict(options=vv.make_options(filter=LOCAL[k]["filt"]))
+    forced(ctx, monkeypatch, build)
+    frames = {}
+    for name in ("clean20", "planted20" + variant):
+        ctx.load_volume(volume(name), table("random"))
+        rgba = ctx.render(LOCAL_W, LOCAL_H, cam, fill=FILL, **kw)
+        mip_rgba, mip_idx = ctx.render_mip(LOCAL_W, LOCAL_H, cam, fill=FILL, return_index=True, **kw)
+        frames[name] = (rgba, mip_rgba, mip_idx)
+    clean, planted = frames["clean20"], frames["planted20" + variant]
+    same(clean[0], clean_frame(k)[0], f"clean [{build}]")
+    same(clean[2], clean_frame(k, mip=True)[1], f"clean [{build}]: index image")
+    for a, b, what in zip(planted, clean, ("rgba", "MIP rgba", "MIP index")):
+        same(a[kept], b[kept], f"{what} [{build}] on the pixels that cannot see the block")
+    written_everywhere(planted[0], met, f"rgba [{build}]"); written_everywhere(planted[1], met, f"MIP rgba [{build}]")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("build", ["default", "bricked", "big"])
+@pytest.mark.parametrize("variant", ["a", "b"])
+@pytest.mark.parametrize("k", range(len(LOCAL)))
+def test_out_of_domain_voxels_stay_local_phong(ctx, monkeypatch, knobs_restored, k, variant, build):
+    """The same with Phong shading: a pixel is held to equality when neither its own ray nor one of its four neighbour rays can see the block."""
+    cam = local_camera(k); kept, met = far_pixels(k, True)
+    kw = dict(options=vv.make_options(filter=LOCAL[k]["filt"]))
+    forced(ctx, monkeypatch, build)
+    frames = {}
+    for name in ("clean20", "planted20" + variant):
+        ctx.load_volume(volume(name), table("random"))
+        frames[name] = ctx.render(LOCAL_W, LOCAL_H, cam, fill=FILL, phong=True, **kw)
+    same(frames["clean20"], clean_frame(k, phong=True)[0], f"clean [{build}]")
+    same(frames["planted20" + variant][kept], frames["clean20"][kept], f"Phong [{build}] on the pixels that cannot see the block")
+    written_everywhere(frames["planted20" + variant], met, f"Phong [{build}]")

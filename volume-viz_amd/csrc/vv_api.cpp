@@ -6,6 +6,7 @@
 // fails with VV_ERR_DEVICE otherwise.
 #include "../../include/volviz.h"
 #include "vv_kernels.h"
+#include "vv_gate.h"
 
 #include <cassert>
 #include <hip/hip_runtime.h>
@@ -718,7 +719,7 @@ static int finalize_layout(vv_context *c, hipStream_t st)
     void *nv = nullptr;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < bytes + pad + (512ull << 20) ||
         hipMalloc(&nv, bytes + pad) != hipSuccess) { (void)hipGetLastError(); return VV_OK; }
-    HIPCHK(c, hipMemsetAsync(nv, 0, bytes + pad, st));           // padding must be finite (weight-0 corners)
+    HIPCHK(c, hipMemsetAsync(nv, 0, bytes + pad, st));           // padding must be finite (weight-0 corners); so must the data: include/volviz.h, value domain of f32 voxels
     launch_repitch(c->d_vol, nv, dense_row, (size_t)c->ny, (size_t)c->nz, row, slice, st);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(st));
@@ -1008,7 +1009,7 @@ static int render_frame(vv_context *c, int W, int H, const slice_params *slice, 
     }
     float min_step = INFINITY;
     for (int a = 0; a < 3; ++a) {
-        if (!(P.step[a] >= 1e-5f) || !std::isfinite(P.step[a]))
+        if (!(P.step[a] >= kStepMin) || !std::isfinite(P.step[a]))
             return fail(c, VV_ERR_INVALID, "vv_render: step must be finite and >= 1e-5 per axis");
         min_step = fminf(min_step, P.step[a]);
     }
@@ -1047,9 +1048,9 @@ static int render_frame(vv_context *c, int W, int H, const slice_params *slice, 
     P.tan_fov_x = (float)tan((double)cam->fovX * M_PI / (double)(180.f * (float)(unsigned)W));
     P.tan_fov_y = (float)tan((double)cam->fovY * M_PI / (double)(180.f * (float)(unsigned)H));
     {
-        const float lo = 0x1p-24f, hi = 0x1p8f;
+        const float lo = kSafeDivTanLo, hi = kSafeDivTanHi;                                 // (vv_gate.h: host/device_math_check.hip sweeps the cores over these ranges)
         P.safe_div = P.tan_fov_x >= lo && P.tan_fov_x <= hi && P.tan_fov_y >= lo && P.tan_fov_y <= hi &&
-                     P.step[0] <= 16.f && P.step[1] <= 16.f && P.step[2] <= 16.f;          // (>= 1e-5 and finite: checked above)
+                     P.step[0] <= kSafeDivStepMax && P.step[1] <= kSafeDivStepMax && P.step[2] <= kSafeDivStepMax;          // (>= kStepMin and finite: checked above)
     }
     P.ray_mode = rays->mode; P.quantize8 = rays->quantize8;
     // What the launch policy below knows about the view (speed only): the camera basis -- given (analytic rays), hinted (an image

@@ -564,20 +564,23 @@ template <int VOXEL> __device__ __forceinline__ float corner_value(const Corners
 template <int VOXEL> __device__ __forceinline__ float corner_value(const CornersZ &C) { return finish_corners(C); }
 template <int VOXEL> __device__ __forceinline__ float corner_value(const CornersZ8 &C) { return finish_corners(C); }
 
+// trilinear value in storage units -> table index (the conversion of classify_raw / classify_index)
+template <int VOXEL>
+__device__ __forceinline__ uint32_t index_of(float L)
+{
+    float s = (VOXEL == VV_VOXEL_F32) ? L * 255.0f : L;
+    return min((uint32_t)s, 255u);                  // v_cvt_u32_f32 saturates; NaN -> 0
+}
 // ... without the bounds test (the caller applies it)
 template <int VOXEL, class CT>
 __device__ __forceinline__ uint32_t classify_raw(const CT &C)
 {
-    float L = corner_value<VOXEL>(C);
-    float s = (VOXEL == VV_VOXEL_F32) ? L * 255.0f : L;
-    return min((uint32_t)s, 255u);                  // v_cvt_u32_f32 saturates; NaN -> 0
+    return index_of<VOXEL>(corner_value<VOXEL>(C));
 }
 template <int VOXEL, class CT>
 __device__ __forceinline__ uint32_t classify_index(const CT &C, float px, float py, float pz)
 {
-    float L = corner_value<VOXEL>(C);
-    float s = (VOXEL == VV_VOXEL_F32) ? L * 255.0f : L;
-    uint32_t idx = min((uint32_t)s, 255u);          // v_cvt_u32_f32 saturates; NaN -> 0
+    uint32_t idx = index_of<VOXEL>(corner_value<VOXEL>(C));
     return bounds_check(px, py, pz) ? idx : 0u;
 }
 template <int VOXEL, bool TEX8, bool BIG = false>
@@ -597,6 +600,36 @@ __device__ __forceinline__ uint32_t pack_rgba(float r, float g, float b, float a
     uint32_t A = (uint32_t)(fmaxf(0.f, fminf(a, 1.f)) * 255.0f);
     return R | (G << 8) | (B << 16) | (A << 24);
 }
+
+// x / d and sqrt(x), IEEE-exact, without their range handling.  The compiler's expansion of `/` and sqrtf is a fixed core (v_rcp + one
+// Newton step, quotient + two residual corrections; v_sqrt + a test of the two neighbouring floats) wrapped in v_div_scale x 2 + v_div_fixup
+// resp. a 2^32 pre-scale and a class test: 11 and 14 instructions.  With operands known to be normal and far from the ends of the range --
+// decided per frame on the host (FrameParams::safe_div, limits in vv_gate.h: pixel tangents in [2^-24, 2^8], steps in [1e-5, 16]; numerators are 0 or differences
+// of q / 255, so quotients lie in [2^-26, 2^42] and their squares' sum in [2^-52, 2^86]) -- the wrappers do nothing (v_div_scale returns its
+// operand, v_div_fmas is a plain fma, v_div_fixup passes normal quotients through) and the cores alone give the same bits: 8 and 8 instructions,
+// 18 fewer per lit sample.  Round 4: C3 + Phong -4 %, C2 + Phong -11 %, u8 -9 %, the 3840 x 2160 frame -11 % (profiles/r04_phong_forms.txt F).
+__device__ __forceinline__ float ph_div_core(float n, float d)
+{
+    const float y0 = __builtin_amdgcn_rcpf(d);
+    const float e = __builtin_fmaf(-d, y0, 1.0f);
+    const float y = __builtin_fmaf(e, y0, y0);
+    const float q0 = n * y;
+    const float r0 = __builtin_fmaf(-d, q0, n);
+    const float q1 = __builtin_fmaf(r0, y, q0);
+    const float r1 = __builtin_fmaf(-d, q1, n);
+    return __builtin_fmaf(r1, y, q1);
+}
+__device__ __forceinline__ float ph_sqrt_core(float x)
+{
+    const float s0 = __builtin_amdgcn_sqrtf(x);
+    const float sm = __uint_as_float(__float_as_uint(s0) - 1u), sp = __uint_as_float(__float_as_uint(s0) + 1u);
+    const float t1 = __builtin_fmaf(-sm, s0, x);
+    float s = (0.f >= t1) ? sm : s0;
+    const float t2 = __builtin_fmaf(-sp, s0, x);
+    s = (0.f < t2) ? sp : s;
+    return s;
+}
+// (both swept against binary64 over these ranges on the GPU: host/device_math_check.hip)
 
 // Instrumentation of a (never timed) frame: what the roofline's byte model is counted from.
 struct InstrArgs {

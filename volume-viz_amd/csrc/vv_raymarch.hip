@@ -377,34 +377,6 @@ __global__ __launch_bounds__(256) void march_kernel(FrameParams P, VolumeView V,
     if (INSTR) flush_counters(counter, executed, slots);
 }
 
-// x / d and sqrt(x), IEEE-exact, without their range handling.  The compiler's expansion of `/` and sqrtf is a fixed core (v_rcp + one
-// Newton step, quotient + two residual corrections; v_sqrt + a test of the two neighbouring floats) wrapped in v_div_scale x 2 + v_div_fixup
-// resp. a 2^32 pre-scale and a class test: 11 and 14 instructions.  With operands known to be normal and far from the ends of the range --
-// decided per frame on the host (FrameParams::safe_div: pixel tangents in [2^-24, 2^8], steps in [1e-5, 16]; numerators are 0 or differences
-// of q / 255, so quotients lie in [2^-26, 2^42] and their squares' sum in [2^-52, 2^86]) -- the wrappers do nothing (v_div_scale returns its
-// operand, v_div_fmas is a plain fma, v_div_fixup passes normal quotients through) and the cores alone give the same bits: 8 and 8 instructions,
-// 18 fewer per lit sample.  Round 4: C3 + Phong -4 %, C2 + Phong -11 %, u8 -9 %, the 3840 x 2160 frame -11 % (profiles/r04_phong_forms.txt F).
-__device__ __forceinline__ float ph_div_core(float n, float d)
-{
-    const float y0 = __builtin_amdgcn_rcpf(d);
-    const float e = __builtin_fmaf(-d, y0, 1.0f);
-    const float y = __builtin_fmaf(e, y0, y0);
-    const float q0 = n * y;
-    const float r0 = __builtin_fmaf(-d, q0, n);
-    const float q1 = __builtin_fmaf(r0, y, q0);
-    const float r1 = __builtin_fmaf(-d, q1, n);
-    return __builtin_fmaf(r1, y, q1);
-}
-__device__ __forceinline__ float ph_sqrt_core(float x)
-{
-    const float s0 = __builtin_amdgcn_sqrtf(x);
-    const float sm = __uint_as_float(__float_as_uint(s0) - 1u), sp = __uint_as_float(__float_as_uint(s0) + 1u);
-    const float t1 = __builtin_fmaf(-sm, s0, x);
-    float s = (0.f >= t1) ? sm : s0;
-    const float t2 = __builtin_fmaf(-sp, s0, x);
-    s = (0.f < t2) ? sp : s;
-    return s;
-}
 // ---------------------------------------------------------------------------
 // march_phong_kernel: one block per reference slab (14x14 interior + apron),
 // 32-deep byte cache in LDS exactly as kernel.cu:125-145 lays it out, but indexed
