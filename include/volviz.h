@@ -249,6 +249,40 @@ int  vv_render_mip(vv_context *ctx, int width, int height,
 int  vv_classify_indices(vv_context *ctx, const uint8_t *index, size_t n, const float tf[1024],
                          uint8_t *rgba_out, int on_device, void *stream);
 
+/* ---- isosurface frames: the first sample at or above a level (no reference counterpart) -----------------------------------------
+ * An isosurface frame marches exactly the rays and samples of a vv_render_mip frame: same end points, per-slab radius, setup with the cut
+ * plane (SLICE_PLANE_CUT; SLICE_PLANE marches as SLICE_NONE), 30-sample chunks, step, object scale, filter and 8-bit classification index k;
+ * opts->ert_threshold and opts->ert_mode are ignored.  level: an integer in 1..255.  Per pixel, the HIT is the first executed sample, in
+ * march order, with k >= level; the ray executes nothing after it.  A pixel therefore has a hit iff vv_render_mip's M >= level.
+ * Each output may be NULL, at least one must be given; row 0 is the bottom row:
+ *   index_out : W*H bytes: k of the hit, 0 where there is none.
+ *   hit_out   : W*H records of four binary32 (16 bytes; a device pointer must be 16-byte aligned, else VV_ERR_INVALID).  xyz = the hit sample's
+ *               position in cube space -- the coordinates of slice_params planes and of the first-pass images, before the object-scale
+ *               mapping -- bit for bit the march's own accumulated position: origin + dir * dist of the sample's chunk (no contraction), then
+ *               += sdir once per sample.  w = the number of samples the ray executed up to and including the hit, as a float (exact: a ray
+ *               has fewer than 2^24 samples at the minimum step).  Depth along the ray: |xyz - ray origin|, or w * |sdir|.  No hit: (0, 0, 0, 0).
+ *   rgba_out  : W*H*4 bytes: the hit shaded by a headlight, (0,0,0,0) where there is no hit.  With t the hit's texture coordinates,
+ *               n_a the volume's dimensions and h_a = 1.0f / (float)n_a:
+ *                 g_a = (int)k(t + h_a e_a) - (int)k(t - h_a e_a), a = x, y, z: six more samples through the march's fetch, filter,
+ *                       classification and bounds test (index 0 outside [0,1)^3), issued once per pixel (and only when rgba_out is given);
+ *                 G_a = ((float)g_a * (1.0f / scale[a])) * (float)n_a          (the gradient in cube space, up to the common factor 1/2)
+ *                 dp = G . dir,  len = sqrtf(G . G),  diffuse = len > 0 ? fminf(fabsf(dp) / len, 1.0f) : 0.0f,  shade = 0.3f + 0.7f * diffuse
+ *                 channel c of RGB = tf[k][c] * shade, alpha = 1, all four through vv_render's clamp-and-truncate conversion
+ *               in binary32, evaluated in the order written without contraction (dot products x, y, z left to right), IEEE sqrtf and /.
+ * Column W-1, row H-1 and the rows of other shards (slab_row_begin / _end, shard_*) stay untouched in all three images.  With count_samples,
+ * vv_last_sample_count is the sum over the written rays of the samples executed up to and including the hit (all of them where there is none);
+ * the touched_* instruments mark the same samples, and the six gradient gathers only under touched_lines_all = 1.  An instrumented frame
+ * holds the same three images.  `stream`, out_on_device (all three images), the layout policy, vv_last_frame_ms and vv_debug_last_launch
+ * (kernel family 3) work as for vv_render_mip.  The context's state is not changed.
+ * Errors: level outside 1..255, all three outputs NULL, NULL slice / camera / rays: VV_ERR_INVALID; no volume: VV_ERR_NO_VOLUME.   */
+int  vv_render_iso(vv_context *ctx, int width, int height,
+                   const struct slice_params *slice,
+                   const struct camera_params *camera,
+                   const vv_ray_source *rays,
+                   const vv_render_options *opts,     /* NULL => defaults */
+                   int level,
+                   uint8_t *rgba_out, uint8_t *index_out, float *hit_out, int out_on_device, void *stream);
+
 /* ---- slice view: replaces invoke_slice_kernel (kernel.cuh:59, kernel.cu:506-519)
  * and invoke_advanced_slice_kernel (kernel.cuh:61, kernel.cu:522-541).
  * buffer: height*width floats; element (j,i) is stored at j*height+i exactly as
@@ -386,7 +420,7 @@ int  vv_layout_state(const vv_context *ctx, unsigned long long out[8]);
 int  vv_device_bytes(const vv_context *ctx, unsigned long long out[4]);
 
 /* ---- metrics (the reference only has a clock() overlay) ---------------- */
-float              vv_last_frame_ms(const vv_context *ctx);      /* hipEvent time of the last vv_render / vv_render_mip (-1: not timed) */
+float              vv_last_frame_ms(const vv_context *ctx);      /* hipEvent time of the last vv_render / vv_render_mip / vv_render_iso (-1: not timed) */
 /* Every vv_render brackets its kernels with two hipEventRecord (what vv_last_frame_ms reads): two more packets the stream has to retire per
  * frame, ~2-4 us each back to back.  A host that times whole runs itself (bench.py) or does not time at all switches them off (on = 0);
  * vv_last_frame_ms then returns -1.  Default: on, the reference's lastRenderTime overlay (glwidget.cpp:288-293) wants it. */
@@ -394,7 +428,7 @@ int                vv_set_frame_timing(vv_context *ctx, int on);
 unsigned long long vv_last_sample_count(vv_context *ctx);        /* executed samples, if count_samples */
 int                vv_debug_last_launch(vv_context *ctx, int out[8]);  /* what the launch policy chose for the last vv_render (developer aid): wave tile log2 width,
                                                                        * block log2 width, samples per trip, LDS reserve, layout (0 linear, 1 linear/64-bit, 2 bricked,
-                                                                       * 3 z-pair, 4 z-fastest, 5 x-pair), view known to the policy (0 / 1), density x 1000, kernel family (0 unshaded, 1 Phong, 2 MIP: vv_render_mip) */
+                                                                       * 3 z-pair, 4 z-fastest, 5 x-pair), view known to the policy (0 / 1), density x 1000, kernel family (0 unshaded, 1 Phong, 2 MIP: vv_render_mip, 3 isosurface: vv_render_iso) */
 /* The rectangle of pixel coordinates (x_min, x_max, y_min, y_max, margin included) outside of which vv_render lets its pre-pass write (0,0,0,0) instead of
  * marching (analytic ray sources): returns 1 and fills out[4], or 0 when this camera gets no rectangle (a cube corner at or behind the eye's plane, a
  * margin wider than the frame).  Needs no device and no context: tests/test_host.py checks it against the oracle's ray-box test pixel by pixel. */

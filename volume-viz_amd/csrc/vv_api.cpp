@@ -74,7 +74,8 @@ struct vv_context {
     float *d_rad = nullptr; size_t rad_cap = 0;
     uint32_t *d_order = nullptr; size_t order_cap = 0;      // StripMap::order of the frame in flight
     uint8_t *d_frame = nullptr; size_t frame_cap = 0;
-    uint8_t *d_index = nullptr; size_t index_cap = 0;       // MIP: index image of a host-buffer frame / of vv_classify_indices
+    uint8_t *d_index = nullptr; size_t index_cap = 0;       // MIP / iso: index image of a host-buffer frame / of vv_classify_indices
+    uint8_t *d_hit = nullptr; size_t hit_cap = 0;           // iso: hit records of a host-buffer frame
     float4 *d_tf_arg = nullptr;                             // vv_classify_indices: the caller's table
     uint8_t *d_img = nullptr; size_t img_cap = 0;
     float *d_slice = nullptr; size_t slice_cap = 0;
@@ -363,6 +364,7 @@ int vv_shutdown(vv_context *c)
     if (c->d_order) hipFree(c->d_order);
     if (c->d_frame) hipFree(c->d_frame);
     if (c->d_index) hipFree(c->d_index);
+    if (c->d_hit) hipFree(c->d_hit);
     if (c->d_tf_arg) hipFree(c->d_tf_arg);
     if (c->d_img) hipFree(c->d_img);
     if (c->d_slice) hipFree(c->d_slice);
@@ -513,7 +515,7 @@ int vv_device_bytes(const vv_context *c, unsigned long long out[4])
     out[0] = c->d_vol ? c->alloc_bytes : 0;
     out[1] = copy_bytes(c, CP_BRICKS);
     out[2] = copy_bytes(c, CP_ZPAIR) + copy_bytes(c, CP_ZFAST) + copy_bytes(c, CP_XPAIR);
-    out[3] = c->rad_cap + c->frame_cap + c->index_cap + (c->d_tf_arg ? 4096 : 0) + c->img_cap + c->slice_cap + 4096 + 8 * sizeof(unsigned long long);
+    out[3] = c->rad_cap + c->frame_cap + c->index_cap + c->hit_cap + (c->d_tf_arg ? 4096 : 0) + c->img_cap + c->slice_cap + 4096 + 8 * sizeof(unsigned long long);
     return VV_OK;
 }
 
@@ -957,13 +959,20 @@ static bool screen_rect(const MarchArgs &A, int W, int H, double *xmin, double *
 
 static void launch_march(const MarchArgs &A, hipStream_t st) { assert(A.build < MB_COUNT); kLaunchRaymarch[A.build](A, st); }
 static void launch_mip_build(const MarchArgs &A, hipStream_t st) { assert(A.build < MB_COUNT); kLaunchMip[A.build](A, st); }
+static void launch_iso_build(const MarchArgs &A, hipStream_t st) { assert(A.build < MB_COUNT); kLaunchIso[A.build](A, st); }
 
-// One frame: vv_render (mip = false: rgba_out, shading) and vv_render_mip (mip = true: rgba_out and / or index_out, never Phong).  Both share the
-// argument checks, the frame and shard set-up, the launch policy, the screen rectangle and the output staging; only the kernels differ.
+// what a frame keeps of its samples: their composite (vv_render), their maximum (vv_render_mip) or the first at or above a level (vv_render_iso).
+// The values are vv_debug_last_launch's kernel family of the two unshaded-only kinds (composite frames report 0 or 1 with the shading).
+enum FrameKind { FRAME_COMPOSITE = 0, FRAME_MIP = 2, FRAME_ISO = 3 };
+
+// One frame: vv_render (FRAME_COMPOSITE: rgba_out, shading), vv_render_mip (FRAME_MIP: rgba_out and / or index_out, never Phong) and vv_render_iso
+// (FRAME_ISO: any of rgba_out, index_out, hit_out; `level`; never Phong).  All share the argument checks, the frame and shard set-up, the launch policy,
+// the screen rectangle and the output staging; only the kernels differ.
 static int render_frame(vv_context *c, int W, int H, const slice_params *slice, const camera_params *cam,
                         const shading_params *shading, const vv_ray_source *rays, const vv_render_options *opts,
-                        uint8_t *rgba_out, uint8_t *index_out, bool mip, int out_on_device, void *stream)
+                        uint8_t *rgba_out, uint8_t *index_out, float *hit_out, FrameKind kind, int level, int out_on_device, void *stream)
 {
+    const bool mip = kind == FRAME_MIP, iso = kind == FRAME_ISO;
     if (W < 1 || H < 1) return fail(c, VV_ERR_INVALID, "vv_render: width/height must be >= 1");
     if (!c->d_vol || !c->have_tf) return fail(c, VV_ERR_NO_VOLUME, "vv_render: no volume / transfer function loaded");
     if (slice->type != SLICE_NONE && slice->type != SLICE_PLANE && slice->type != SLICE_PLANE_CUT)
@@ -1038,7 +1047,7 @@ static int render_frame(vv_context *c, int W, int H, const slice_params *slice, 
         A.slabs.r0 = r_lo; A.slabs.band = 1 << 28; A.slabs.band_stride = 0;
         A.slabs.n_regular = r_hi > r_lo ? r_hi - r_lo : 0;
     }
-    P.slice_type = (mip && slice->type == SLICE_PLANE) ? SLICE_NONE : slice->type;      // (a MIP frame has no highlight to draw: SLICE_PLANE marches as SLICE_NONE)
+    P.slice_type = ((mip || iso) && slice->type == SLICE_PLANE) ? SLICE_NONE : slice->type;      // (a MIP / iso frame has no highlight to draw: SLICE_PLANE marches as SLICE_NONE)
     for (int a = 0; a < 3; ++a) {
         P.slice_point[a] = slice->params[a]; P.slice_normal[a] = slice->params[3 + a];   // kernel.cu:224-225
         P.cam_pos[a] = cam->origin[a]; P.scale[a] = cam->scale[a];
@@ -1155,9 +1164,10 @@ static int render_frame(vv_context *c, int W, int H, const slice_params *slice, 
         }
     }
     // A MIP frame's pixels beside the rectangle hold the table's entry 0, not rad_kernel's (0,0,0,0), and there is the index image: mip_fill_kernel
-    // writes them, and rad_kernel gets no rectangle (it then writes no pixel and computes every slab's radius).
+    // writes them, and rad_kernel gets no rectangle (it then writes no pixel and computes every slab's radius).  An iso frame likewise: it may have no
+    // RGBA image at all, and has two more (iso_fill_kernel).
     const PixelRect mip_rect = A.rect;
-    if (mip) { A.rect.x0 = 0; A.rect.y0 = 0; A.rect.x1 = INT_MAX; A.rect.y1 = INT_MAX; }
+    if (mip || iso) { A.rect.x0 = 0; A.rect.y0 = 0; A.rect.x1 = INT_MAX; A.rect.y1 = INT_MAX; }
     A.tf = c->d_tf;
     int rc = ensure(c, (void **)&c->d_rad, &c->rad_cap, (size_t)P.nbx * P.nby * sizeof(float));
     if (rc) return rc;
@@ -1182,8 +1192,8 @@ static int render_frame(vv_context *c, int W, int H, const slice_params *slice, 
     A.rad = c->d_rad; A.rad_out = c->d_rad;
     A.counter = c->d_counter;
 
-    const size_t fb = (size_t)W * H * 4, ib = (size_t)W * H;
-    uint8_t *d_out = rgba_out, *d_idx = index_out;
+    const size_t fb = (size_t)W * H * 4, ib = (size_t)W * H, hb = (size_t)W * H * 16;
+    uint8_t *d_out = rgba_out, *d_idx = index_out, *d_hit = (uint8_t *)hit_out;
     // Pixels the frame does not write (column W-1, row H-1, rows of other shards) must keep the caller's bytes.  A whole
     // frame is read back as the (W-1) x (H-1) rectangle it writes; a sharded / row-limited frame goes through a staged
     // copy of the caller's buffer (rare path).
@@ -1200,8 +1210,20 @@ static int render_frame(vv_context *c, int W, int H, const slice_params *slice, 
         d_idx = c->d_index;
         if (!whole) HIPCHK(c, hipMemcpyAsync(d_idx, index_out, ib, hipMemcpyHostToDevice, st));
     }
-    A.pixels = (uint32_t *)d_out; A.index = d_idx;
+    if (!out_on_device && hit_out) {
+        rc = ensure(c, (void **)&c->d_hit, &c->hit_cap, hb);
+        if (rc) return rc;
+        d_hit = c->d_hit;
+        if (!whole) HIPCHK(c, hipMemcpyAsync(d_hit, hit_out, hb, hipMemcpyHostToDevice, st));
+    }
+    A.pixels = (uint32_t *)d_out; A.index = d_idx; A.hit = (float4 *)d_hit;
     if (((uintptr_t)d_out & 3) != 0) return fail(c, VV_ERR_INVALID, "vv_render: output buffer must be 4-byte aligned");
+    if (((uintptr_t)d_hit & 15) != 0) return fail(c, VV_ERR_INVALID, "vv_render_iso: a device hit_out must be 16-byte aligned");      // (iso_kernel writes a record in one store)
+    if (iso) {
+        A.iso.level = level;
+        const int dims[3] = {c->nx, c->ny, c->nz};
+        for (int a = 0; a < 3; ++a) { A.iso.n[a] = (float)dims[a]; A.iso.h[a] = 1.0f / (float)dims[a]; }
+    }
 
     if (A.instr) HIPCHK(c, hipMemsetAsync(c->d_counter, 0, 16 * sizeof(unsigned long long), st));
 #ifdef VV_TIMELINE
@@ -1211,7 +1233,7 @@ static int render_frame(vv_context *c, int W, int H, const slice_params *slice, 
     {
         static const int layout_code[] = {0, 1, 2, 2, 3, 4, 5};        // MarchBuild -> the layout code of vv_debug_last_launch
         const int v[8] = {A.strips.tile_log2w, A.strips.blk_log2w, A.unroll, A.phong ? A.lds_reserve_phong : A.lds_reserve, layout_code[A.build],
-                          have_basis ? 1 : 0, (int)fminf(density * 1000.f, 2e9f), mip ? 2 : (A.phong ? 1 : 0)};
+                          have_basis ? 1 : 0, (int)fminf(density * 1000.f, 2e9f), kind != FRAME_COMPOSITE ? (int)kind : (A.phong ? 1 : 0)};
         memcpy(c->last_launch, v, sizeof v);
     }
     if (c->time_frames) HIPCHK(c, hipEventRecord(c->ev0, st));
@@ -1220,6 +1242,12 @@ static int render_frame(vv_context *c, int W, int H, const slice_params *slice, 
             if (W >= 2 && H >= 2) launch_rad(A, st);
             if (rect_limits) launch_mip_fill(A, mip_rect, st);
             launch_mip_build(A, st);
+        }
+    } else if (iso) {
+        if (A.strips.n_strips > 0) {
+            if (W >= 2 && H >= 2) launch_rad(A, st);
+            if (rect_limits) launch_iso_fill(A, mip_rect, st);
+            launch_iso_build(A, st);
         }
     } else if (A.phong) {
         if (A.fill_outside) { A.rad_out = nullptr; launch_rad(A, st); }          // the pixels beside the volume's screen rectangle (rad_kernel writes them; no radii here)
@@ -1241,6 +1269,10 @@ static int render_frame(vv_context *c, int W, int H, const slice_params *slice, 
             if (whole) HIPCHK(c, hipMemcpy2DAsync(index_out, (size_t)W, d_idx, (size_t)W, (size_t)(W - 1), (size_t)(H - 1), hipMemcpyDeviceToHost, st));
             else HIPCHK(c, hipMemcpyAsync(index_out, d_idx, ib, hipMemcpyDeviceToHost, st));
         }
+        if (hit_out) {
+            if (whole) HIPCHK(c, hipMemcpy2DAsync(hit_out, (size_t)W * 16, d_hit, (size_t)W * 16, (size_t)(W - 1) * 16, (size_t)(H - 1), hipMemcpyDeviceToHost, st));
+            else HIPCHK(c, hipMemcpyAsync(hit_out, d_hit, hb, hipMemcpyDeviceToHost, st));
+        }
         HIPCHK(c, hipStreamSynchronize(st));
     } else if (!stream) {
         HIPCHK(c, hipStreamSynchronize(st));
@@ -1256,7 +1288,7 @@ int vv_render(vv_context *c, int W, int H, const slice_params *slice, const came
 {
     if (!c) return fail(nullptr, VV_ERR_INVALID, "vv_render: NULL context");
     if (!slice || !cam || !shading || !rays || !rgba_out) return fail(c, VV_ERR_INVALID, "vv_render: NULL argument");
-    return render_frame(c, W, H, slice, cam, shading, rays, opts, rgba_out, nullptr, false, out_on_device, stream);
+    return render_frame(c, W, H, slice, cam, shading, rays, opts, rgba_out, nullptr, nullptr, FRAME_COMPOSITE, 0, out_on_device, stream);
 }
 
 // ---- maximum-intensity projection (no reference counterpart) ---------------------------------
@@ -1270,7 +1302,22 @@ int vv_render_mip(vv_context *c, int W, int H, const slice_params *slice, const 
     shading_params unshaded;
     memset(&unshaded, 0, sizeof unshaded);
     unshaded.transferPreset = -1; unshaded.phongShading = false;
-    return render_frame(c, W, H, slice, cam, &unshaded, rays, opts, rgba_out, index_out, true, out_on_device, stream);
+    return render_frame(c, W, H, slice, cam, &unshaded, rays, opts, rgba_out, index_out, nullptr, FRAME_MIP, 0, out_on_device, stream);
+}
+
+// ---- isosurface frames: the first sample at or above a level (no reference counterpart) --------
+int vv_render_iso(vv_context *c, int W, int H, const slice_params *slice, const camera_params *cam,
+                  const vv_ray_source *rays, const vv_render_options *opts, int level,
+                  uint8_t *rgba_out, uint8_t *index_out, float *hit_out, int out_on_device, void *stream)
+{
+    if (!c) return fail(nullptr, VV_ERR_INVALID, "vv_render_iso: NULL context");
+    if (!slice || !cam || !rays) return fail(c, VV_ERR_INVALID, "vv_render_iso: NULL argument");
+    if (!rgba_out && !index_out && !hit_out) return fail(c, VV_ERR_INVALID, "vv_render_iso: rgba_out, index_out and hit_out are all NULL");
+    if (level < 1 || level > 255) return fail(c, VV_ERR_INVALID, "vv_render_iso: level must lie in 1..255");
+    shading_params unshaded;
+    memset(&unshaded, 0, sizeof unshaded);
+    unshaded.transferPreset = -1; unshaded.phongShading = false;
+    return render_frame(c, W, H, slice, cam, &unshaded, rays, opts, rgba_out, index_out, hit_out, FRAME_ISO, level, out_on_device, stream);
 }
 
 int vv_classify_indices(vv_context *c, const uint8_t *index, size_t n, const float tf[1024], uint8_t *rgba_out, int on_device, void *stream)

@@ -83,10 +83,10 @@ EXPORTS = [
     "vv_prepare_layouts", "vv_set_layout_policy", "vv_layout_state", "vv_device_bytes", "vv_reread_env",
     "vv_load_volume_stream_begin", "vv_load_volume_stream_slices", "vv_load_volume_stream_end", "vv_load_volume_t3d",
     "vv_load_volume_stream_slices_async", "vv_load_volume_stream_wait_source", "vv_dataset_preset", "vv_debug_last_launch", "vv_set_frame_timing", "vv_debug_screen_rect",
-    "vv_render_mip", "vv_classify_indices",
+    "vv_render_mip", "vv_classify_indices", "vv_render_iso",
 ]
 # entry points a variant library built from an earlier tree (A/B tools, load_library(path)) may lack
-_NEWER_EXPORTS = ("vv_render_mip", "vv_classify_indices")
+_NEWER_EXPORTS = ("vv_render_mip", "vv_classify_indices", "vv_render_iso")
 
 _lib = None
 _libs = {}
@@ -125,6 +125,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib.vv_render_mip.argtypes = [vp, i, i, C.POINTER(slice_params), C.POINTER(camera_params), C.POINTER(vv_ray_source),
                                       C.POINTER(vv_render_options), vp, vp, i, vp]
         lib.vv_classify_indices.argtypes = [vp, vp, sz, vp, vp, i, vp]
+    if hasattr(lib, "vv_render_iso"):
+        lib.vv_render_iso.argtypes = [vp, i, i, C.POINTER(slice_params), C.POINTER(camera_params), C.POINTER(vv_ray_source),
+                                      C.POINTER(vv_render_options), i, vp, vp, vp, i, vp]
     lib.vv_slice.argtypes = [vp, vp, sz, sz, f, f, f, i, C.POINTER(f * 3), i, i, i, vp]
     lib.vv_slice_advanced.argtypes = [vp, vp, sz, sz, C.POINTER(f * 16), C.POINTER(f * 3), i, i, vp]
     lib.vv_generate_ellipsoids.argtypes = [vp, vp, i, i, i, i, i, vp, vp, vp, vp]
@@ -428,6 +431,37 @@ class Context:
                                          C.byref(options) if options is not None else None,
                                          rgba_ptr or None, index_ptr or None, 1, stream))
 
+    # vv_render_iso (no reference counterpart)
+    def render_iso(self, width: int, height: int, cam: Camera, level: int, *, slice: Optional[slice_params] = None,
+                   rays: Optional[vv_ray_source] = None, options: Optional[vv_render_options] = None,
+                   fill: int = 0, return_index: bool = False, return_hit: bool = False):
+        """Host-buffer isosurface frame at `level` (1..255); returns rgba uint8 [H, W, 4] (row 0 = bottom), or a tuple with index uint8 [H, W]
+        (return_index) and hit float32 [H, W, 4] = (x, y, z, ordinal) (return_hit) behind it.  Pixels the frame does not write keep `fill` in
+        every byte of all images (the float image's bytes too)."""
+        out = np.full((height, width, 4), fill, np.uint8)
+        idx = np.full((height, width), fill, np.uint8) if return_index else None
+        hit = np.full((height, width, 16), fill, np.uint8).view(np.float32) if return_hit else None
+        sp = slice if slice is not None else make_slice_params()
+        cp = cam.params(width, height)
+        rs = rays if rays is not None else analytic_rays(cam)
+        self._chk(self.lib.vv_render_iso(self.h, width, height, C.byref(sp), C.byref(cp), C.byref(rs),
+                                         C.byref(options) if options is not None else None, int(level),
+                                         out.ctypes.data, idx.ctypes.data if return_index else None,
+                                         hit.ctypes.data if return_hit else None, 0, None))
+        res = (out,) + ((idx,) if return_index else ()) + ((hit,) if return_hit else ())
+        return res if len(res) > 1 else out
+
+    def render_iso_device(self, width: int, height: int, cam: Camera, level: int, rgba_ptr: int = 0, index_ptr: int = 0, hit_ptr: int = 0, *,
+                          slice=None, rays=None, options=None, stream: int = 0):
+        """Device-buffer isosurface frame enqueued on `stream` (a hipStream_t as int): rgba_ptr (W*H*4 bytes), index_ptr (W*H bytes) and / or
+        hit_ptr (W*H*16 bytes, 16-byte aligned), 0 = not wanted."""
+        sp = slice if slice is not None else make_slice_params()
+        cp = cam.params(width, height)
+        rs = rays if rays is not None else analytic_rays(cam)
+        self._chk(self.lib.vv_render_iso(self.h, width, height, C.byref(sp), C.byref(cp), C.byref(rs),
+                                         C.byref(options) if options is not None else None, int(level),
+                                         rgba_ptr or None, index_ptr or None, hit_ptr or None, 1, stream))
+
     def classify_indices(self, index: np.ndarray, tf: Optional[np.ndarray] = None) -> np.ndarray:
         """vv_classify_indices on a host index image (uint8, any shape): uint8 [..., 4] through `tf` (float32[1024]) or the context's table."""
         index = np.ascontiguousarray(index, np.uint8)
@@ -470,7 +504,7 @@ class Context:
         """vv_debug_last_launch: what the launch policy chose for the last render."""
         out = (C.c_int * 8)()
         self._chk(self.lib.vv_debug_last_launch(self.h, out))
-        k = ("tile_log2w", "blk_log2w", "unroll", "lds_reserve", "layout", "view_known", "density_x1000", "phong")     # phong: 0 unshaded, 1 Phong, 2 MIP
+        k = ("tile_log2w", "blk_log2w", "unroll", "lds_reserve", "layout", "view_known", "density_x1000", "phong")     # phong: 0 unshaded, 1 Phong, 2 MIP, 3 isosurface
         return dict(zip(k, list(out)))
 
     def reread_env(self):
