@@ -297,6 +297,46 @@ int  vv_slice_advanced(vv_context *ctx, float *buffer, size_t height, size_t wid
                        const float scale[3], int filter,
                        int out_on_device, void *stream);
 
+/* ---- thick-slab slices: the maximum, minimum or mean over K samples around the slice plane (no reference counterpart) ------------
+ * A slab call takes K = slab->samples (1..VV_SLAB_MAX_SAMPLES) samples of vv_slice / vv_slice_advanced per pixel and keeps one number.
+ * Everything is binary32, evaluated in the order written, without contraction.
+ *   spacing = thickness / (float)K;   sample k (0 <= k < K) has offset  o_k = ((float)k - 0.5f * (float)(K - 1)) * spacing.
+ * Position of sample k:
+ *   vv_slice_slab          : the slab runs along the coordinate the slice kernel's orientation switch leaves at 0 -- VV_SAGITTAL: z,
+ *                            VV_HORIZONTAL: y, VV_CORONAL: x.  The position is vv_slice's own arithmetic with that axis' displacement d_a
+ *                            replaced by d_a + o_k (one add, made before anything else).  thickness is in the units of dx, dy, dz.
+ *   vv_slice_advanced_slab : vv_slice_advanced's arithmetic with rz = 0.5f + o_k in the place of 0.5f.  thickness is in the units of the
+ *                            transform's third input coordinate.
+ * A sample is EXECUTED iff its texture coordinates pass the slice kernel's bounds test (all three in [0, 1)); its value s_k is what the
+ * slice kernel would store there (the filtered value, / 255 for u8 volumes).  Samples outside the volume are not executed: they do not
+ * count as 0.  Per pixel, with n the number of executed samples:
+ *   VV_SLAB_MAX  : the largest s_k;  aux = the smallest k that attains it (a later sample replaces the current one only if strictly greater)
+ *   VV_SLAB_MIN  : the smallest s_k; aux = the smallest k that attains it (... only if strictly less)
+ *   VV_SLAB_MEAN : acc / (float)n, IEEE division; acc starts as the first executed sample's value, every later executed sample is added
+ *                  in order of k, one add each; aux = n
+ *   n = 0        : the value is 0.0f; aux = -1 (MAX, MIN) or 0 (MEAN)
+ * Storage is vv_slice's: the element of pixel (j, i) goes to offset j*height + i of `buffer` and, where given, of `aux` (height*width
+ * int32 each); offsets at or beyond height*width are skipped, and so are pixels with i >= height && j + 1 < height.  Elements that are
+ * not written keep the caller's bytes in both buffers.  vv_slice_to_bgra works on `buffer` unchanged.
+ * With samples == 1, `buffer` equals what vv_slice / vv_slice_advanced write for the same arguments, bit for bit, in every mode and for
+ * any thickness.
+ * `stream` and out_on_device work as for vv_slice and apply to both buffers; a device `aux` must be 4-byte aligned.  The kernel samples
+ * the linear volume (volumes above 4 GiB included); the optional layout copies and the context's state are not touched.  f32 voxels: the
+ * value domain of vv_load_volume_f32; a mean whose running sum leaves the binary32 range is +-Inf as IEEE addition says, and no NaN
+ * arises from in-domain voxels.
+ * Errors: NULL ctx, buffer, scale, trans or slab, a mode outside vv_slab_mode, samples outside 1..VV_SLAB_MAX_SAMPLES, a thickness that is
+ * negative or not finite, an orientation other than the three canonical ones, sizes vv_slice rejects, a misaligned device aux:
+ * VV_ERR_INVALID; no volume: VV_ERR_NO_VOLUME.  There is no legacy form.  A failed call leaves the context usable.                  */
+typedef enum { VV_SLAB_MAX = 0, VV_SLAB_MIN = 1, VV_SLAB_MEAN = 2 } vv_slab_mode;
+#define VV_SLAB_MAX_SAMPLES 1024
+typedef struct vv_slab { int mode; int samples; float thickness; } vv_slab;
+int  vv_slice_slab(vv_context *ctx, float *buffer, int32_t *aux /* or NULL */, size_t height, size_t width,
+                   float dx, float dy, float dz, int orientation, const float scale[3], int filter,
+                   const vv_slab *slab, int out_on_device, void *stream);
+int  vv_slice_advanced_slab(vv_context *ctx, float *buffer, int32_t *aux /* or NULL */, size_t height, size_t width,
+                            const float trans[16], const float scale[3], int filter,
+                            const vv_slab *slab, int out_on_device, void *stream);
+
 /* The first pass on its own (firstpass.vert:6, firstpass.frag:4, glwidget.cpp:198-228): the
  * RGBA8 images the reference's two FBOs would hold for this camera -- cube-space entry (front
  * faces) and exit (back faces) positions, UNORM8-rounded, alpha 255 where a face is visible and

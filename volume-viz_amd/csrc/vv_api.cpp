@@ -1493,6 +1493,74 @@ int vv_slice_advanced(vv_context *c, float *buffer, size_t height, size_t width,
     return run_slice(c, S, buffer, out_on_device, stream);
 }
 
+// ---- thick-slab slices (include/volviz.h: vv_slice_slab) ------------------------------------
+static int run_slab(vv_context *c, SlabArgs &S, float *buffer, int32_t *aux, const vv_slab *slab, int out_on_device, void *stream)
+{
+    if (!buffer) return fail(c, VV_ERR_INVALID, "vv_slice_slab: NULL buffer");
+    if (slab->mode != VV_SLAB_MAX && slab->mode != VV_SLAB_MIN && slab->mode != VV_SLAB_MEAN)
+        return fail(c, VV_ERR_INVALID, "vv_slice_slab: mode must be VV_SLAB_MAX, VV_SLAB_MIN or VV_SLAB_MEAN");
+    if (slab->samples < 1 || slab->samples > VV_SLAB_MAX_SAMPLES) return fail(c, VV_ERR_INVALID, "vv_slice_slab: samples must lie in 1..1024");
+    if (!(slab->thickness >= 0.f) || !std::isfinite(slab->thickness)) return fail(c, VV_ERR_INVALID, "vv_slice_slab: thickness must be finite and >= 0");
+    if (S.height < 1 || S.width < 1 || S.height > 65535u * 16 || S.width > 65535u * 16)
+        return fail(c, VV_ERR_INVALID, "vv_slice_slab: bad buffer size");
+    if (out_on_device && ((uintptr_t)aux & 3) != 0) return fail(c, VV_ERR_INVALID, "vv_slice_slab: a device aux must be 4-byte aligned");
+    if (!c->d_vol) return fail(c, VV_ERR_NO_VOLUME, "vv_slice_slab: no volume loaded");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = pick_stream(c, stream);
+    const size_t bytes = S.height * S.width * sizeof(float);        // of either image
+    S.V = view_of(c, MB_LINEAR); S.V_type = c->vtype;
+    S.mode = slab->mode; S.samples = slab->samples; S.thickness = slab->thickness;
+    float *d = buffer; int32_t *da = aux;
+    if (!out_on_device) {
+        // both images in the slice scratch; elements the kernel skips keep the caller's bytes, as in run_slice
+        int rc = ensure(c, (void **)&c->d_slice, &c->slice_cap, aux ? 2 * bytes : bytes);
+        if (rc) return rc;
+        d = c->d_slice;
+        HIPCHK(c, hipMemcpyAsync(d, buffer, bytes, hipMemcpyHostToDevice, st));
+        if (aux) {
+            da = (int32_t *)(c->d_slice + S.height * S.width);
+            HIPCHK(c, hipMemcpyAsync(da, aux, bytes, hipMemcpyHostToDevice, st));
+        }
+    }
+    S.buffer = d; S.aux = da;
+    launch_slab(S, st);
+    HIPCHK(c, hipGetLastError());
+    if (!out_on_device) {
+        HIPCHK(c, hipMemcpyAsync(buffer, d, bytes, hipMemcpyDeviceToHost, st));
+        if (aux) HIPCHK(c, hipMemcpyAsync(aux, da, bytes, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+    } else if (!stream) HIPCHK(c, hipStreamSynchronize(st));
+    return VV_OK;
+}
+
+int vv_slice_slab(vv_context *c, float *buffer, int32_t *aux, size_t height, size_t width, float dx, float dy, float dz,
+                  int orientation, const float scale[3], int filter, const vv_slab *slab, int out_on_device, void *stream)
+{
+    if (!c) return fail(nullptr, VV_ERR_INVALID, "vv_slice_slab: NULL context");
+    if (!scale || !slab) return fail(c, VV_ERR_INVALID, "vv_slice_slab: NULL argument");
+    if (orientation != VV_SAGITTAL && orientation != VV_HORIZONTAL && orientation != VV_CORONAL)
+        return fail(c, VV_ERR_INVALID, "vv_slice_slab: orientation must be VV_SAGITTAL, VV_HORIZONTAL or VV_CORONAL");
+    SlabArgs S; memset(&S, 0, sizeof S);
+    S.height = height; S.width = width; S.dx = dx; S.dy = dy; S.dz = dz;
+    S.orientation = orientation; S.advanced = 0;
+    S.tex8 = filter != VV_FILTER_EXACT;
+    for (int a = 0; a < 3; ++a) S.scale[a] = scale[a];
+    return run_slab(c, S, buffer, aux, slab, out_on_device, stream);
+}
+
+int vv_slice_advanced_slab(vv_context *c, float *buffer, int32_t *aux, size_t height, size_t width, const float trans[16],
+                           const float scale[3], int filter, const vv_slab *slab, int out_on_device, void *stream)
+{
+    if (!c) return fail(nullptr, VV_ERR_INVALID, "vv_slice_advanced_slab: NULL context");
+    if (!scale || !trans || !slab) return fail(c, VV_ERR_INVALID, "vv_slice_advanced_slab: NULL argument");
+    SlabArgs S; memset(&S, 0, sizeof S);
+    S.height = height; S.width = width; S.advanced = 1; S.orientation = VV_SAGITTAL;
+    S.tex8 = filter != VV_FILTER_EXACT;
+    for (int a = 0; a < 3; ++a) S.scale[a] = scale[a];
+    memcpy(S.trans, trans, 16 * sizeof(float));
+    return run_slab(c, S, buffer, aux, slab, out_on_device, stream);
+}
+
 // ---- generator: VolumeGenerator::drawEllipsoid / drawDefaultBrain ------------------------
 static int generate_impl(vv_context *c, uint8_t *out, int out_on_device, int nx, int ny, int nz, int n,
                          const float *centers, const float *axes, const uint8_t *colors, int in_place, void *stream);

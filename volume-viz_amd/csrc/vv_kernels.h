@@ -96,6 +96,17 @@ struct SliceArgs {
     float trans[16]; int advanced;
 };
 void launch_slice(const SliceArgs &a, hipStream_t s);
+// thick-slab slices (vv_slab.hip): SliceArgs' view, image and position fields without the legacy form, the slab (vv_slab of include/volviz.h) and the
+// second image: aux[offset] = the extremum's sample (MAX / MIN) or the number of executed samples (MEAN), or null
+struct SlabArgs {
+    VolumeView V; int V_type; bool tex8;
+    float *buffer; int32_t *aux; size_t height, width;
+    float dx, dy, dz; int orientation;
+    float scale[3];
+    float trans[16]; int advanced;
+    int mode, samples; float thickness;
+};
+void launch_slab(const SlabArgs &a, hipStream_t s);
 void launch_first_pass(const FrameParams &P, uint32_t *front, uint32_t *back, hipStream_t s);
 
 size_t generate_scratch_floats(int nx, int ny, int nz, int n);

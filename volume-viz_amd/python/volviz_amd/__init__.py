@@ -28,6 +28,8 @@ VOXEL_U8, VOXEL_F32 = 0, 1
 LAYOUT_BRICKED, LAYOUT_ZPAIR, LAYOUT_ZFAST, LAYOUT_POLICY = 1, 2, 4, 256
 FILTER_TEX8, FILTER_EXACT = 0, 1
 ERT_REFERENCE, ERT_TRUE = 0, 1
+SLAB_MAX, SLAB_MIN, SLAB_MEAN = 0, 1, 2          # vv_slab_mode
+SLAB_MAX_SAMPLES = 1024
 RAYS_IMAGES, RAYS_ANALYTIC = 0, 1
 TF_ENGINE, TF_HEAD, TF_MRI = 0, 1, 2
 # `stream` arguments: 0/None = the context's own stream, synchronous; STREAM_DEFAULT_ASYNC = the device's default (null)
@@ -71,6 +73,10 @@ class vv_render_options(C.Structure):
                 ("touched_block_lines", C.c_void_p), ("touched_block_lines_log2", C.c_int)]
 
 
+class vv_slab(C.Structure):
+    _fields_ = [("mode", C.c_int), ("samples", C.c_int), ("thickness", C.c_float)]
+
+
 EXPORTS = [
     "vv_init", "vv_shutdown", "vv_last_error", "vv_load_volume_u8", "vv_load_volume_f32",
     "vv_load_volume_device", "vv_set_transfer_function", "vv_render", "vv_slice",
@@ -83,10 +89,10 @@ EXPORTS = [
     "vv_prepare_layouts", "vv_set_layout_policy", "vv_layout_state", "vv_device_bytes", "vv_reread_env",
     "vv_load_volume_stream_begin", "vv_load_volume_stream_slices", "vv_load_volume_stream_end", "vv_load_volume_t3d",
     "vv_load_volume_stream_slices_async", "vv_load_volume_stream_wait_source", "vv_dataset_preset", "vv_debug_last_launch", "vv_set_frame_timing", "vv_debug_screen_rect",
-    "vv_render_mip", "vv_classify_indices", "vv_render_iso",
+    "vv_render_mip", "vv_classify_indices", "vv_render_iso", "vv_slice_slab", "vv_slice_advanced_slab",
 ]
 # entry points a variant library built from an earlier tree (A/B tools, load_library(path)) may lack
-_NEWER_EXPORTS = ("vv_render_mip", "vv_classify_indices", "vv_render_iso")
+_NEWER_EXPORTS = ("vv_render_mip", "vv_classify_indices", "vv_render_iso", "vv_slice_slab", "vv_slice_advanced_slab")
 
 _lib = None
 _libs = {}
@@ -130,6 +136,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
                                       C.POINTER(vv_render_options), i, vp, vp, vp, i, vp]
     lib.vv_slice.argtypes = [vp, vp, sz, sz, f, f, f, i, C.POINTER(f * 3), i, i, i, vp]
     lib.vv_slice_advanced.argtypes = [vp, vp, sz, sz, C.POINTER(f * 16), C.POINTER(f * 3), i, i, vp]
+    if hasattr(lib, "vv_slice_slab"):
+        lib.vv_slice_slab.argtypes = [vp, vp, vp, sz, sz, f, f, f, i, C.POINTER(f * 3), i, C.POINTER(vv_slab), i, vp]
+        lib.vv_slice_advanced_slab.argtypes = [vp, vp, vp, sz, sz, C.POINTER(f * 16), C.POINTER(f * 3), i, C.POINTER(vv_slab), i, vp]
     lib.vv_generate_ellipsoids.argtypes = [vp, vp, i, i, i, i, i, vp, vp, vp, vp]
     lib.vv_generate_default_brain.argtypes = [vp, vp, i, i, i, i, vp]
     lib.vv_draw_ellipsoid.argtypes = [vp, vp, i, i, i, i, vp, vp, C.c_uint8, vp]
@@ -557,6 +566,41 @@ class Context:
         self._chk(self.lib.vv_slice_advanced(self.h, buf.ctypes.data, height, width, C.byref(t), C.byref(sc),
                                              filter, 0, None))
         return buf
+
+    # vv_slice_slab / vv_slice_advanced_slab: the maximum, minimum or mean over `samples` slices across `thickness`
+    def slice_slab(self, height: int, width: int, dx=0.0, dy=0.0, dz=0.0, orientation=SAGITTAL, *, mode=SLAB_MAX, samples=1,
+                   thickness=0.0, scale=(1.0, 1.0, 1.0), filter=FILTER_TEX8, fill=0.0, return_aux=False, aux_fill=-7):
+        """The float32 buffer, or (buffer, aux int32): aux = the extremum's sample (MAX, MIN; -1: none) or the number of
+        executed samples (MEAN).  Elements the kernel does not write hold `fill` / `aux_fill`."""
+        buf = np.full(height * width, fill, np.float32)
+        aux = np.full(height * width, aux_fill, np.int32) if return_aux else None
+        self.slice_slab_device(height, width, dx, dy, dz, orientation, buf.ctypes.data, aux.ctypes.data if return_aux else 0,
+                               mode=mode, samples=samples, thickness=thickness, scale=scale, filter=filter, stream=None, on_device=False)
+        return (buf, aux) if return_aux else buf
+
+    def slice_advanced_slab(self, height: int, width: int, trans: np.ndarray, *, mode=SLAB_MAX, samples=1, thickness=0.0,
+                            scale=(1.0, 1.0, 1.0), filter=FILTER_TEX8, fill=0.0, return_aux=False, aux_fill=-7):
+        buf = np.full(height * width, fill, np.float32)
+        aux = np.full(height * width, aux_fill, np.int32) if return_aux else None
+        self.slice_advanced_slab_device(height, width, trans, buf.ctypes.data, aux.ctypes.data if return_aux else 0,
+                                        mode=mode, samples=samples, thickness=thickness, scale=scale, filter=filter, stream=None, on_device=False)
+        return (buf, aux) if return_aux else buf
+
+    def slice_slab_device(self, height: int, width: int, dx, dy, dz, orientation, buffer_ptr: int, aux_ptr: int = 0, *, mode=SLAB_MAX,
+                          samples=1, thickness=0.0, scale=(1.0, 1.0, 1.0), filter=FILTER_TEX8, stream=0, on_device=True):
+        """Device pointers (height * width float32, and int32 or 0); with a stream the call only enqueues."""
+        sc = (C.c_float * 3)(*[float(v) for v in scale])
+        sl = vv_slab(int(mode), int(samples), float(thickness))
+        self._chk(self.lib.vv_slice_slab(self.h, buffer_ptr or None, aux_ptr or None, height, width, dx, dy, dz, orientation, C.byref(sc),
+                                         filter, C.byref(sl), int(on_device), stream or None))
+
+    def slice_advanced_slab_device(self, height: int, width: int, trans, buffer_ptr: int, aux_ptr: int = 0, *, mode=SLAB_MAX, samples=1,
+                                   thickness=0.0, scale=(1.0, 1.0, 1.0), filter=FILTER_TEX8, stream=0, on_device=True):
+        t = (C.c_float * 16)(*[float(v) for v in np.asarray(trans, np.float32).reshape(16)])
+        sc = (C.c_float * 3)(*[float(v) for v in scale])
+        sl = vv_slab(int(mode), int(samples), float(thickness))
+        self._chk(self.lib.vv_slice_advanced_slab(self.h, buffer_ptr or None, aux_ptr or None, height, width, C.byref(t), C.byref(sc),
+                                                  filter, C.byref(sl), int(on_device), stream or None))
 
     # VolumeGenerator::drawEllipsoid x n / drawDefaultBrain (volumegenerator.cpp:31-119)
     def generate_ellipsoids(self, nx: int, ny: int, nz: int, centers, axes, colors) -> np.ndarray:
