@@ -337,6 +337,41 @@ int  vv_slice_advanced_slab(vv_context *ctx, float *buffer, int32_t *aux /* or N
                             const float trans[16], const float scale[3], int filter,
                             const vv_slab *slab, int out_on_device, void *stream);
 
+/* ---- histograms: how the loaded volume, or an index image, is distributed over the 256 classification indices (no reference counterpart) ----
+ * vv_volume_histogram counts the voxels of a box of the loaded volume where it lies, in HBM, whatever put it there (host upload, device buffer,
+ * streamed upload with or without promotion, re-pitching after the upload).
+ *  1. BIN of a voxel v: the 8-bit classification index the march, MIP and isosurface kernels give a sample that falls exactly on the voxel's
+ *     centre (the kernels' own conversion, index_of in csrc/vv_device.h).  u8: the byte itself.  f32: s = v * 255.0f in binary32, one rounding;
+ *     the bin is 0 if s is NaN or s < 1, 255 if s >= 255 (+Inf included), otherwise s truncated toward zero.  counts[k] therefore answers "how
+ *     much of the volume does table entry k colour".
+ *  2. RANGE: vmin / vmax are bit-for-bit copies of a voxel of the box: the least and the greatest of its non-NaN voxels under the total order of
+ *     binary32 bit patterns (-0.0 below +0.0; +-Inf take part; denormals are not flushed: integer keys are compared, no floating-point minimum
+ *     or maximum is taken, and the denormal mode of the library's units does not show).  No non-NaN voxel: vmin = +Inf, vmax = -Inf.  u8 volumes:
+ *     the smallest and the largest byte, as float.  NaN voxels are counted in nan_voxels and, by rule 1, in counts[0].
+ *  3. BOX: box_lo inclusive, box_hi exclusive, in voxels (x, y, z), 0 <= lo[a] < hi[a] <= dims[a]; both NULL = the whole volume.  Only voxels of
+ *     the box are read as data; the padding of a re-pitched volume (32 bytes per row, an extra row per slice) is never counted.
+ *  4. EXACT: every field is exact and the same from run to run (integer adds and maxima do not depend on the order of arrival); nothing depends
+ *     on what `out` held, on the volume's layout in HBM, on the launch geometry or on how the volume was loaded.
+ *  5. vv_histogram_indices: counts[k] = the number of bytes of index[0..n) equal to k; n = 0 gives 256 zeros.  index and counts are both host or
+ *     both device pointers (on_device); device counts must be 8-byte aligned.  Needs no volume, as vv_classify_indices: the distribution of a MIP
+ *     or isosurface index image, for auto-windowing.  No byte outside index[0..n) is read.
+ *  6. `stream` / out_on_device / on_device as for vv_classify_indices: NULL = the context's stream, the call returns when the work is complete; any
+ *     other handle with device output only enqueues.  The accumulators live in scratch of the context: keep enqueue-only histogram calls of one
+ *     context on one stream.  The context's volume, table, layout copies and residency state are not touched; vv_last_frame_ms keeps its value.
+ *  7. Errors: NULL ctx or out / counts, a box with one bound NULL, a box outside rule 3, a misaligned device out / counts, NULL index with
+ *     n > 0: VV_ERR_INVALID; vv_volume_histogram before a volume is loaded: VV_ERR_NO_VOLUME.  A failed call leaves the context usable.
+ * A device vv_histogram must be 8-byte aligned.                                                                                              */
+typedef struct vv_histogram {
+    unsigned long long counts[256];  /* voxels per classification index */
+    unsigned long long voxels;       /* voxels in the box = sum of counts */
+    unsigned long long nan_voxels;   /* f32 volumes: NaN voxels (also counted in counts[0]); u8: 0 */
+    float vmin, vmax;                /* storage units: u8 0..255 as float, f32 the voxel itself */
+} vv_histogram;                      /* 2072 bytes */
+int  vv_volume_histogram(vv_context *ctx, const int box_lo[3], const int box_hi[3],   /* both NULL = whole volume */
+                         vv_histogram *out, int out_on_device, void *stream);
+int  vv_histogram_indices(vv_context *ctx, const uint8_t *index, size_t n,
+                          unsigned long long counts[256], int on_device, void *stream);
+
 /* The first pass on its own (firstpass.vert:6, firstpass.frag:4, glwidget.cpp:198-228): the
  * RGBA8 images the reference's two FBOs would hold for this camera -- cube-space entry (front
  * faces) and exit (back faces) positions, UNORM8-rounded, alpha 255 where a face is visible and

@@ -27,6 +27,7 @@ struct vv_knobs {
     int tile_log2w = -1, xcd_band = -1, unroll = -1, lds_reserve = -1, lds_reserve_phong = -1;
     int bricked = -1, zpair = -1, zfast = -1, force_big = 0;
     int block_w = -1, tail = -1, rect = -1, lpt = -1, lpt_run = -1, phong_bricks = -1;
+    int hist_blocks = -1;                   // VV_HIST_BLOCKS: cap on hist_kernel's grid (tests drive its grid-stride loop with it)
     static int geti(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
     void read()
     {
@@ -36,6 +37,7 @@ struct vv_knobs {
         block_w = geti("VV_BLOCK_W", -1); tail = geti("VV_TAIL", -1);
         zfast = geti("VV_ZFAST", -1); force_big = getenv("VV_FORCE_BIG") != nullptr;
         rect = geti("VV_RECT", -1); lpt = geti("VV_LPT", -1); lpt_run = geti("VV_LPT_RUN", -1); phong_bricks = geti("VV_PHONG_BRICKS", -1);
+        hist_blocks = geti("VV_HIST_BLOCKS", -1);
     }
 };
 
@@ -86,6 +88,8 @@ struct vv_context {
     std::vector<uint8_t> row_buf;
     int last_launch[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // vv_debug_last_launch
     unsigned long long *d_counter = nullptr;
+    unsigned long long *d_hist = nullptr;       // histogram calls: the accumulator (kHistAccWords), then a vv_histogram for host-output calls
+    int n_cu = 0;                               // compute units of the device (hist_kernel's grid)
     bool counter_valid = false;          // counters of the last instrumented frame
     // streamed upload
     hipStream_t copy_stream = nullptr, promo_stream = nullptr;   // H2D copies / u8 -> f32 promotion kernels
@@ -97,6 +101,11 @@ struct vv_context {
 };
 
 static std::string g_err;
+
+// vv_context::d_hist: the accumulator, then (8-byte aligned) the vv_histogram a host-output call copies back
+static const size_t kHistResultOffset = kHistAccWords * sizeof(unsigned long long);
+static const size_t kHistScratchBytes = kHistResultOffset + sizeof(vv_histogram);
+static_assert(sizeof(vv_histogram) == 2072 && sizeof(unsigned long long) == 8, "vv_histogram layout (include/volviz.h)");
 
 static int fail(vv_context *c, int code, const std::string &msg)
 {
@@ -344,6 +353,8 @@ int vv_init(int device, vv_context **out)
     if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&c->stream) != hipSuccess ||
         hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess || hipEventCreateWithFlags(&c->ev_count, hipEventDisableTiming) != hipSuccess ||
         hipMalloc((void **)&c->d_counter, 16 * sizeof(unsigned long long)) != hipSuccess ||
+        hipMalloc((void **)&c->d_hist, kHistScratchBytes) != hipSuccess ||
+        hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess ||
         hipMalloc((void **)&c->d_tf, 256 * sizeof(float4)) != hipSuccess) {
         delete c;
         return fail(nullptr, VV_ERR_DEVICE, "vv_init: device set-up failed");
@@ -370,6 +381,7 @@ int vv_shutdown(vv_context *c)
     if (c->d_slice) hipFree(c->d_slice);
     if (c->d_gen) hipFree(c->d_gen);
     if (c->d_counter) hipFree(c->d_counter);
+    if (c->d_hist) hipFree(c->d_hist);
     for (int i = 0; i < 2; ++i) {
         if (c->pin[i]) hipHostFree(c->pin[i]);
         if (c->pin_ev[i]) hipEventDestroy(c->pin_ev[i]);
@@ -515,7 +527,7 @@ int vv_device_bytes(const vv_context *c, unsigned long long out[4])
     out[0] = c->d_vol ? c->alloc_bytes : 0;
     out[1] = copy_bytes(c, CP_BRICKS);
     out[2] = copy_bytes(c, CP_ZPAIR) + copy_bytes(c, CP_ZFAST) + copy_bytes(c, CP_XPAIR);
-    out[3] = c->rad_cap + c->frame_cap + c->index_cap + c->hit_cap + (c->d_tf_arg ? 4096 : 0) + c->img_cap + c->slice_cap + 4096 + 8 * sizeof(unsigned long long);
+    out[3] = c->rad_cap + c->frame_cap + c->index_cap + c->hit_cap + (c->d_tf_arg ? 4096 : 0) + c->img_cap + c->slice_cap + 4096 + 8 * sizeof(unsigned long long) + kHistScratchBytes;
     return VV_OK;
 }
 
@@ -1559,6 +1571,90 @@ int vv_slice_advanced_slab(vv_context *c, float *buffer, int32_t *aux, size_t he
     for (int a = 0; a < 3; ++a) S.scale[a] = scale[a];
     memcpy(S.trans, trans, 16 * sizeof(float));
     return run_slab(c, S, buffer, aux, slab, out_on_device, stream);
+}
+
+// ---- histograms (include/volviz.h: vv_volume_histogram) ------------------------------------
+// accumulator zeroed, counted (unless there is nothing to count), turned into `out` / `counts`: all on `st`
+static int run_hist(vv_context *c, const HistRuns *runs, int vtype, unsigned long long voxels, vv_histogram *d_out, unsigned long long *d_counts, hipStream_t st)
+{
+    HIPCHK(c, hipMemsetAsync(c->d_hist, 0, kHistAccWords * sizeof(unsigned long long), st));
+    if (runs) launch_hist(*runs, c->n_cu, c->knobs.hist_blocks, c->d_hist, st);
+    launch_hist_finish(c->d_hist, vtype, voxels, d_out, d_counts, st);
+    HIPCHK(c, hipGetLastError());
+    return VV_OK;
+}
+
+int vv_volume_histogram(vv_context *c, const int box_lo[3], const int box_hi[3], vv_histogram *out, int out_on_device, void *stream)
+{
+    if (!c) return fail(nullptr, VV_ERR_INVALID, "vv_volume_histogram: NULL context");
+    if (!out) return fail(c, VV_ERR_INVALID, "vv_volume_histogram: NULL out");
+    if ((box_lo == nullptr) != (box_hi == nullptr)) return fail(c, VV_ERR_INVALID, "vv_volume_histogram: box_lo and box_hi must both be given or both be NULL");
+    if (out_on_device && ((uintptr_t)out & 7) != 0) return fail(c, VV_ERR_INVALID, "vv_volume_histogram: a device out must be 8-byte aligned");
+    if (!c->d_vol) return fail(c, VV_ERR_NO_VOLUME, "vv_volume_histogram: no volume loaded");
+    const int dims[3] = {c->nx, c->ny, c->nz};
+    int lo[3] = {0, 0, 0}, hi[3] = {c->nx, c->ny, c->nz};
+    if (box_lo)
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = box_lo[a]; hi[a] = box_hi[a];
+            if (!(0 <= lo[a] && lo[a] < hi[a] && hi[a] <= dims[a])) return fail(c, VV_ERR_INVALID, "vv_volume_histogram: the box must satisfy 0 <= lo < hi <= dims on every axis");
+        }
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = pick_stream(c, stream);
+    // the box as runs of the linear layout: its rows; whole slices of it where the rows are dense and taken whole; the whole box where the slices are too
+    const size_t size = c->vtype == VV_VOXEL_F32 ? 4 : 1;
+    const size_t bx = (size_t)(hi[0] - lo[0]), by = (size_t)(hi[1] - lo[1]), bz = (size_t)(hi[2] - lo[2]);
+    const bool rows_dense = bx == (size_t)c->nx && c->row_pitch == (size_t)c->nx * size;
+    const bool slices_dense = rows_dense && by == (size_t)c->ny && c->slice_pitch == (size_t)c->ny * c->row_pitch;
+    HistRuns R;
+    memset(&R, 0, sizeof R);
+    R.vtype = c->vtype; R.tight = 0;
+    R.data0 = (const char *)c->d_vol + (size_t)lo[2] * c->slice_pitch + (size_t)lo[1] * c->row_pitch + (size_t)lo[0] * size;
+    R.row_step = c->row_pitch; R.slice_step = c->slice_pitch;
+    if (slices_dense)    { R.run_voxels = bx * by * bz; R.rps = 1; R.n_slices = 1; }
+    else if (rows_dense) { R.run_voxels = bx * by; R.rps = 1; R.n_slices = (uint32_t)bz; }
+    else                 { R.run_voxels = bx; R.rps = (uint32_t)by; R.n_slices = (uint32_t)bz; }
+    // what launch_hist is promised: the last voxel of the box lies inside the volume, which ends more than 16 bytes before its allocation does
+    const size_t last = (size_t)(hi[2] - 1) * c->slice_pitch + (size_t)(hi[1] - 1) * c->row_pitch + (size_t)hi[0] * size;
+    if (((uintptr_t)c->d_vol & 15) != 0 || last + 16 > c->alloc_bytes) return fail(c, VV_ERR_DEVICE, "vv_volume_histogram: volume allocation is not what the kernel expects");
+    vv_histogram *d_out = out_on_device ? out : (vv_histogram *)((char *)c->d_hist + kHistResultOffset);
+    int rc = run_hist(c, &R, c->vtype, (unsigned long long)(bx * by * bz), d_out, nullptr, st);
+    if (rc) return rc;
+    if (!out_on_device) {
+        HIPCHK(c, hipMemcpyAsync(out, d_out, sizeof(vv_histogram), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+    } else if (!stream) HIPCHK(c, hipStreamSynchronize(st));
+    return VV_OK;
+}
+
+int vv_histogram_indices(vv_context *c, const uint8_t *index, size_t n, unsigned long long counts[256], int on_device, void *stream)
+{
+    if (!c) return fail(nullptr, VV_ERR_INVALID, "vv_histogram_indices: NULL context");
+    if (!counts || (!index && n)) return fail(c, VV_ERR_INVALID, "vv_histogram_indices: NULL argument");
+    if (on_device && ((uintptr_t)counts & 7) != 0) return fail(c, VV_ERR_INVALID, "vv_histogram_indices: device counts must be 8-byte aligned");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = pick_stream(c, stream);
+    const uint8_t *d_idx = index;
+    unsigned long long *d_counts = counts;
+    if (!on_device) {
+        if (n) {
+            int rc = ensure(c, (void **)&c->d_index, &c->index_cap, n);
+            if (rc) return rc;
+            HIPCHK(c, hipMemcpyAsync(c->d_index, index, n, hipMemcpyHostToDevice, st));
+            d_idx = c->d_index;
+        }
+        d_counts = (unsigned long long *)((char *)c->d_hist + kHistResultOffset);
+    }
+    HistRuns R;
+    memset(&R, 0, sizeof R);
+    R.data0 = d_idx; R.vtype = VV_VOXEL_U8; R.tight = 1;          // one run of n bytes in a buffer whose surroundings are not ours to read
+    R.run_voxels = n; R.rps = 1; R.n_slices = 1;
+    int rc = run_hist(c, n ? &R : nullptr, VV_VOXEL_U8, n, nullptr, d_counts, st);
+    if (rc) return rc;
+    if (!on_device) {
+        HIPCHK(c, hipMemcpyAsync(counts, d_counts, 256 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+    } else if (!stream) HIPCHK(c, hipStreamSynchronize(st));
+    return VV_OK;
 }
 
 // ---- generator: VolumeGenerator::drawEllipsoid / drawDefaultBrain ------------------------

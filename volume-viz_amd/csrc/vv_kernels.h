@@ -107,6 +107,21 @@ struct SlabArgs {
     int mode, samples; float thickness;
 };
 void launch_slab(const SlabArgs &a, hipStream_t s);
+// histograms (vv_hist.hip).  What is counted is a set of equally long contiguous runs of voxels: run (ry, rz), 0 <= ry < rps, 0 <= rz < n_slices, starts at
+// data0 + rz * slice_step + ry * row_step bytes and holds run_voxels voxels (a box of the volume: its rows, or whole slices / the whole box where the
+// rows are dense; an index image: one run of u8).  The caller vouches that every run lies inside one allocation that starts 16-byte aligned and, unless
+// `tight`, extends 16 bytes beyond the last run; with `tight` no byte outside the runs is read.
+struct HistRuns {
+    const void *data0; int vtype; int tight;
+    uint64_t run_voxels, row_step, slice_step;
+    uint32_t rps, n_slices;
+};
+// the accumulator: 256 counts, the NaN count, and two uint32 in one word: the largest key and the largest complemented key of the non-NaN f32 voxels.
+// All zeros before launch_hist (zero keys = no voxel yet).
+constexpr int kHistAccNan = 256, kHistAccKeys = 257, kHistAccWords = 258;
+void launch_hist(const HistRuns &r, int n_cu, int max_blocks /* <= 0: kHistBlocksPerCU per CU */, unsigned long long *acc, hipStream_t s);
+void launch_hist_finish(const unsigned long long *acc, int vtype, unsigned long long voxels, vv_histogram *out, unsigned long long *counts /* used when out is null */,
+                        hipStream_t s);
 void launch_first_pass(const FrameParams &P, uint32_t *front, uint32_t *back, hipStream_t s);
 
 size_t generate_scratch_floats(int nx, int ny, int nz, int n);

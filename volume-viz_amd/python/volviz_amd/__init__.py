@@ -77,6 +77,29 @@ class vv_slab(C.Structure):
     _fields_ = [("mode", C.c_int), ("samples", C.c_int), ("thickness", C.c_float)]
 
 
+class vv_histogram(C.Structure):          # 2072 bytes
+    _fields_ = [("counts", C.c_ulonglong * 256), ("voxels", C.c_ulonglong), ("nan_voxels", C.c_ulonglong),
+                ("vmin", C.c_float), ("vmax", C.c_float)]
+
+
+@dataclass
+class Histogram:
+    """vv_histogram as numpy values: counts uint64[256], voxels, nan_voxels, vmin / vmax as np.float32 (bit for bit what the library wrote)."""
+    counts: np.ndarray
+    voxels: int
+    nan_voxels: int
+    vmin: np.float32
+    vmax: np.float32
+
+    @staticmethod
+    def from_bytes(raw) -> "Histogram":
+        """From the 2072 bytes of a vv_histogram (e.g. read back from a device buffer)."""
+        raw = np.frombuffer(bytes(raw), np.uint8, C.sizeof(vv_histogram))
+        q = raw[:258 * 8].view(np.uint64)
+        f = raw[258 * 8:].view(np.float32)
+        return Histogram(q[:256].copy(), int(q[256]), int(q[257]), f[0], f[1])
+
+
 EXPORTS = [
     "vv_init", "vv_shutdown", "vv_last_error", "vv_load_volume_u8", "vv_load_volume_f32",
     "vv_load_volume_device", "vv_set_transfer_function", "vv_render", "vv_slice",
@@ -90,9 +113,11 @@ EXPORTS = [
     "vv_load_volume_stream_begin", "vv_load_volume_stream_slices", "vv_load_volume_stream_end", "vv_load_volume_t3d",
     "vv_load_volume_stream_slices_async", "vv_load_volume_stream_wait_source", "vv_dataset_preset", "vv_debug_last_launch", "vv_set_frame_timing", "vv_debug_screen_rect",
     "vv_render_mip", "vv_classify_indices", "vv_render_iso", "vv_slice_slab", "vv_slice_advanced_slab",
+    "vv_volume_histogram", "vv_histogram_indices",
 ]
 # entry points a variant library built from an earlier tree (A/B tools, load_library(path)) may lack
-_NEWER_EXPORTS = ("vv_render_mip", "vv_classify_indices", "vv_render_iso", "vv_slice_slab", "vv_slice_advanced_slab")
+_NEWER_EXPORTS = ("vv_render_mip", "vv_classify_indices", "vv_render_iso", "vv_slice_slab", "vv_slice_advanced_slab",
+                  "vv_volume_histogram", "vv_histogram_indices")
 
 _lib = None
 _libs = {}
@@ -139,6 +164,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     if hasattr(lib, "vv_slice_slab"):
         lib.vv_slice_slab.argtypes = [vp, vp, vp, sz, sz, f, f, f, i, C.POINTER(f * 3), i, C.POINTER(vv_slab), i, vp]
         lib.vv_slice_advanced_slab.argtypes = [vp, vp, vp, sz, sz, C.POINTER(f * 16), C.POINTER(f * 3), i, C.POINTER(vv_slab), i, vp]
+    if hasattr(lib, "vv_volume_histogram"):
+        lib.vv_volume_histogram.argtypes = [vp, C.POINTER(i * 3), C.POINTER(i * 3), vp, i, vp]
+        lib.vv_histogram_indices.argtypes = [vp, vp, sz, vp, i, vp]
     lib.vv_generate_ellipsoids.argtypes = [vp, vp, i, i, i, i, i, vp, vp, vp, vp]
     lib.vv_generate_default_brain.argtypes = [vp, vp, i, i, i, i, vp]
     lib.vv_draw_ellipsoid.argtypes = [vp, vp, i, i, i, i, vp, vp, C.c_uint8, vp]
@@ -601,6 +629,39 @@ class Context:
         sl = vv_slab(int(mode), int(samples), float(thickness))
         self._chk(self.lib.vv_slice_advanced_slab(self.h, buffer_ptr or None, aux_ptr or None, height, width, C.byref(t), C.byref(sc),
                                                   filter, C.byref(sl), int(on_device), stream or None))
+
+    # vv_volume_histogram / vv_histogram_indices (no reference counterpart)
+    @staticmethod
+    def _box(box):
+        if box is None:
+            return None, None
+        (x0, y0, z0), (x1, y1, z1) = box
+        return C.byref((C.c_int * 3)(int(x0), int(y0), int(z0))), C.byref((C.c_int * 3)(int(x1), int(y1), int(z1)))
+
+    def histogram(self, box=None, prefill: int = 0) -> Histogram:
+        """vv_volume_histogram of the loaded volume, or of box = ((x0, y0, z0), (x1, y1, z1)), lo inclusive, hi exclusive, in voxels.
+        `prefill`: the byte the output structure holds before the call (the result does not depend on it)."""
+        out = vv_histogram()
+        C.memset(C.byref(out), prefill, C.sizeof(out))
+        lo, hi = self._box(box)
+        self._chk(self.lib.vv_volume_histogram(self.h, lo, hi, C.addressof(out), 0, None))
+        return Histogram.from_bytes(out)
+
+    def histogram_device(self, out_ptr: int, box=None, stream: int = 0):
+        """vv_volume_histogram into a device vv_histogram (2072 bytes, 8-byte aligned), enqueued on `stream`."""
+        lo, hi = self._box(box)
+        self._chk(self.lib.vv_volume_histogram(self.h, lo, hi, out_ptr or None, 1, stream or None))
+
+    def histogram_indices(self, index: np.ndarray) -> np.ndarray:
+        """vv_histogram_indices of a host index image (uint8, any shape): uint64[256]."""
+        index = np.ascontiguousarray(index, np.uint8)
+        counts = np.full(256, 0xA5A5A5A5A5A5A5A5, np.uint64)
+        self._chk(self.lib.vv_histogram_indices(self.h, index.ctypes.data if index.size else None, index.size, counts.ctypes.data, 0, None))
+        return counts
+
+    def histogram_indices_device(self, index_ptr: int, n: int, counts_ptr: int, stream: int = 0):
+        """vv_histogram_indices on device buffers (n index bytes -> 256 uint64, 8-byte aligned), enqueued on `stream`."""
+        self._chk(self.lib.vv_histogram_indices(self.h, index_ptr or None, n, counts_ptr or None, 1, stream or None))
 
     # VolumeGenerator::drawEllipsoid x n / drawDefaultBrain (volumegenerator.cpp:31-119)
     def generate_ellipsoids(self, nx: int, ny: int, nz: int, centers, axes, colors) -> np.ndarray:
