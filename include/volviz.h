@@ -283,6 +283,45 @@ int  vv_render_iso(vv_context *ctx, int width, int height,
                    int level,
                    uint8_t *rgba_out, uint8_t *index_out, float *hit_out, int out_on_device, void *stream);
 
+/* ---- projection frames: maximum, minimum and mean intensity, with the extremum's place along the ray (no reference counterpart) ----
+ * A projection frame marches exactly the rays and executed samples of a vv_render_mip frame: same end points, per-slab radius, setup with the
+ * cut plane (SLICE_PLANE_CUT, its clipping and early return; SLICE_PLANE marches as SLICE_NONE), 30-sample chunks (sample i of a chunk runs
+ * iff i * sstep + dist <= upper), step, object scale and filter; opts->ert_threshold and opts->ert_mode are ignored.
+ * An executed sample is COUNTED iff its texture coordinates pass the march's bounds test, all three in [0,1); its k is the 8-bit
+ * classification index the march gives it.  Executed samples outside the volume are not counted: they are no zeros.  (The per-slab sphere
+ * starts rays in front of the cube, so most rays execute some.)  n = the counted samples of the ray, e = its executed samples, outside
+ * ones included.  Per pixel, in integer arithmetic:
+ *   VV_PROJ_MAX  : v = the largest k over the counted samples; ord = the 1-based ordinal, among the ray's executed samples in march order,
+ *                  of the first counted sample with k == v (a later sample replaces an earlier one only if strictly greater).
+ *   VV_PROJ_MIN  : the same with the smallest k and strictly less.
+ *   VV_PROJ_MEAN : s = the sum of k over the counted samples (it fits 32 bits: a ray has fewer than 2^24 samples);
+ *                  v = (2 * s + n) / (2 * n), evaluated in 64 bits, truncating: the mean rounded half up.
+ *   n == 0       : v = 0, ord = 0, s = 0 (a ray that misses the volume, a zero-length ray, the cut plane's early return, a ray whose
+ *                  samples all lie outside).
+ * Each output may be NULL, at least one must be given; row 0 is the bottom row:
+ *   index_out : W*H bytes holding v.
+ *   rgba_out  : W*H*4 bytes: vv_render_mip's conversion of tf[v], for every pixel the frame writes, n == 0 included.
+ *   stat_out  : W*H records of two uint32 (8 bytes; a device pointer must be 8-byte aligned, else VV_ERR_INVALID): {ord, n} for
+ *               VV_PROJ_MAX / VV_PROJ_MIN, {s, n} for VV_PROJ_MEAN.  Depth of the extremum along the ray: ord * |sdir|, the meaning
+ *               vv_render_iso gives to its w.
+ * In VV_PROJ_MAX, index_out and rgba_out equal vv_render_mip's byte for byte for the same arguments (there an outside sample contributes 0
+ * to the maximum, and n == 0 gives 0).
+ * Column W-1, row H-1 and the rows of other shards (slab_row_begin / _end, shard_*) stay untouched in all three images.  With count_samples,
+ * vv_last_sample_count is the sum of e over the written rays -- vv_render_mip's count; the touched_* instruments mark what they mark in a MIP
+ * frame.  An instrumented frame holds the same three images.  `stream`, out_on_device (all three images), the layout policy, vv_last_frame_ms
+ * and vv_debug_last_launch (kernel family 4) work as for vv_render_mip.  The context's state is not changed.  No result depends on the layout
+ * sampled, the launch geometry or the samples per loop trip.
+ * Errors: NULL ctx / slice / camera / rays, a mode outside 0..2, all three outputs NULL, a misaligned device stat_out: VV_ERR_INVALID; no
+ * volume: VV_ERR_NO_VOLUME.  A failed call leaves the context usable.   */
+typedef enum { VV_PROJ_MAX = 0, VV_PROJ_MIN = 1, VV_PROJ_MEAN = 2 } vv_proj_mode;
+int  vv_render_projection(vv_context *ctx, int width, int height,
+                          const struct slice_params *slice,
+                          const struct camera_params *camera,
+                          const vv_ray_source *rays,
+                          const vv_render_options *opts,     /* NULL => defaults */
+                          int mode,
+                          uint8_t *rgba_out, uint8_t *index_out, uint32_t *stat_out, int out_on_device, void *stream);
+
 /* ---- slice view: replaces invoke_slice_kernel (kernel.cuh:59, kernel.cu:506-519)
  * and invoke_advanced_slice_kernel (kernel.cuh:61, kernel.cu:522-541).
  * buffer: height*width floats; element (j,i) is stored at j*height+i exactly as
@@ -495,7 +534,7 @@ int  vv_layout_state(const vv_context *ctx, unsigned long long out[8]);
 int  vv_device_bytes(const vv_context *ctx, unsigned long long out[4]);
 
 /* ---- metrics (the reference only has a clock() overlay) ---------------- */
-float              vv_last_frame_ms(const vv_context *ctx);      /* hipEvent time of the last vv_render / vv_render_mip / vv_render_iso (-1: not timed) */
+float              vv_last_frame_ms(const vv_context *ctx);      /* hipEvent time of the last vv_render / vv_render_mip / vv_render_iso / vv_render_projection (-1: not timed) */
 /* Every vv_render brackets its kernels with two hipEventRecord (what vv_last_frame_ms reads): two more packets the stream has to retire per
  * frame, ~2-4 us each back to back.  A host that times whole runs itself (bench.py) or does not time at all switches them off (on = 0);
  * vv_last_frame_ms then returns -1.  Default: on, the reference's lastRenderTime overlay (glwidget.cpp:288-293) wants it. */
@@ -503,7 +542,7 @@ int                vv_set_frame_timing(vv_context *ctx, int on);
 unsigned long long vv_last_sample_count(vv_context *ctx);        /* executed samples, if count_samples */
 int                vv_debug_last_launch(vv_context *ctx, int out[8]);  /* what the launch policy chose for the last vv_render (developer aid): wave tile log2 width,
                                                                        * block log2 width, samples per trip, LDS reserve, layout (0 linear, 1 linear/64-bit, 2 bricked,
-                                                                       * 3 z-pair, 4 z-fastest, 5 x-pair), view known to the policy (0 / 1), density x 1000, kernel family (0 unshaded, 1 Phong, 2 MIP: vv_render_mip, 3 isosurface: vv_render_iso) */
+                                                                       * 3 z-pair, 4 z-fastest, 5 x-pair), view known to the policy (0 / 1), density x 1000, kernel family (0 unshaded, 1 Phong, 2 MIP: vv_render_mip, 3 isosurface: vv_render_iso, 4 projection: vv_render_projection) */
 /* The rectangle of pixel coordinates (x_min, x_max, y_min, y_max, margin included) outside of which vv_render lets its pre-pass write (0,0,0,0) instead of
  * marching (analytic ray sources): returns 1 and fills out[4], or 0 when this camera gets no rectangle (a cube corner at or behind the eye's plane, a
  * margin wider than the frame).  Needs no device and no context: tests/test_host.py checks it against the oracle's ray-box test pixel by pixel. */

@@ -78,6 +78,7 @@ struct vv_context {
     uint8_t *d_frame = nullptr; size_t frame_cap = 0;
     uint8_t *d_index = nullptr; size_t index_cap = 0;       // MIP / iso: index image of a host-buffer frame / of vv_classify_indices
     uint8_t *d_hit = nullptr; size_t hit_cap = 0;           // iso: hit records of a host-buffer frame
+    uint8_t *d_stat = nullptr; size_t stat_cap = 0;         // projection: stat records of a host-buffer frame
     float4 *d_tf_arg = nullptr;                             // vv_classify_indices: the caller's table
     uint8_t *d_img = nullptr; size_t img_cap = 0;
     float *d_slice = nullptr; size_t slice_cap = 0;
@@ -376,6 +377,7 @@ int vv_shutdown(vv_context *c)
     if (c->d_frame) hipFree(c->d_frame);
     if (c->d_index) hipFree(c->d_index);
     if (c->d_hit) hipFree(c->d_hit);
+    if (c->d_stat) hipFree(c->d_stat);
     if (c->d_tf_arg) hipFree(c->d_tf_arg);
     if (c->d_img) hipFree(c->d_img);
     if (c->d_slice) hipFree(c->d_slice);
@@ -527,7 +529,7 @@ int vv_device_bytes(const vv_context *c, unsigned long long out[4])
     out[0] = c->d_vol ? c->alloc_bytes : 0;
     out[1] = copy_bytes(c, CP_BRICKS);
     out[2] = copy_bytes(c, CP_ZPAIR) + copy_bytes(c, CP_ZFAST) + copy_bytes(c, CP_XPAIR);
-    out[3] = c->rad_cap + c->frame_cap + c->index_cap + c->hit_cap + (c->d_tf_arg ? 4096 : 0) + c->img_cap + c->slice_cap + 4096 + 8 * sizeof(unsigned long long) + kHistScratchBytes;
+    out[3] = c->rad_cap + c->frame_cap + c->index_cap + c->hit_cap + c->stat_cap + (c->d_tf_arg ? 4096 : 0) + c->img_cap + c->slice_cap + 4096 + 8 * sizeof(unsigned long long) + kHistScratchBytes;
     return VV_OK;
 }
 
@@ -972,19 +974,22 @@ static bool screen_rect(const MarchArgs &A, int W, int H, double *xmin, double *
 static void launch_march(const MarchArgs &A, hipStream_t st) { assert(A.build < MB_COUNT); kLaunchRaymarch[A.build](A, st); }
 static void launch_mip_build(const MarchArgs &A, hipStream_t st) { assert(A.build < MB_COUNT); kLaunchMip[A.build](A, st); }
 static void launch_iso_build(const MarchArgs &A, hipStream_t st) { assert(A.build < MB_COUNT); kLaunchIso[A.build](A, st); }
+static void launch_proj_build(const MarchArgs &A, hipStream_t st) { assert(A.build < MB_COUNT); kLaunchProj[A.build](A, st); }
 
-// what a frame keeps of its samples: their composite (vv_render), their maximum (vv_render_mip) or the first at or above a level (vv_render_iso).
-// The values are vv_debug_last_launch's kernel family of the two unshaded-only kinds (composite frames report 0 or 1 with the shading).
-enum FrameKind { FRAME_COMPOSITE = 0, FRAME_MIP = 2, FRAME_ISO = 3 };
+// what a frame keeps of its samples: their composite (vv_render), their maximum (vv_render_mip), the first at or above a level (vv_render_iso) or the
+// maximum / minimum / mean of those inside the volume (vv_render_projection).
+// The values are vv_debug_last_launch's kernel family of the three unshaded-only kinds (composite frames report 0 or 1 with the shading).
+enum FrameKind { FRAME_COMPOSITE = 0, FRAME_MIP = 2, FRAME_ISO = 3, FRAME_PROJ = 4 };
 
 // One frame: vv_render (FRAME_COMPOSITE: rgba_out, shading), vv_render_mip (FRAME_MIP: rgba_out and / or index_out, never Phong) and vv_render_iso
-// (FRAME_ISO: any of rgba_out, index_out, hit_out; `level`; never Phong).  All share the argument checks, the frame and shard set-up, the launch policy,
-// the screen rectangle and the output staging; only the kernels differ.
+// (FRAME_ISO: any of rgba_out, index_out, hit_out; `level`; never Phong) and vv_render_projection (FRAME_PROJ: any of rgba_out, index_out, stat_out; `level`
+// holds the vv_proj_mode; never Phong).  All share the argument checks, the frame and shard set-up, the launch policy, the screen rectangle and the
+// output staging; only the kernels differ.
 static int render_frame(vv_context *c, int W, int H, const slice_params *slice, const camera_params *cam,
                         const shading_params *shading, const vv_ray_source *rays, const vv_render_options *opts,
-                        uint8_t *rgba_out, uint8_t *index_out, float *hit_out, FrameKind kind, int level, int out_on_device, void *stream)
+                        uint8_t *rgba_out, uint8_t *index_out, float *hit_out, uint32_t *stat_out, FrameKind kind, int level, int out_on_device, void *stream)
 {
-    const bool mip = kind == FRAME_MIP, iso = kind == FRAME_ISO;
+    const bool mip = kind == FRAME_MIP, iso = kind == FRAME_ISO, proj = kind == FRAME_PROJ;
     if (W < 1 || H < 1) return fail(c, VV_ERR_INVALID, "vv_render: width/height must be >= 1");
     if (!c->d_vol || !c->have_tf) return fail(c, VV_ERR_NO_VOLUME, "vv_render: no volume / transfer function loaded");
     if (slice->type != SLICE_NONE && slice->type != SLICE_PLANE && slice->type != SLICE_PLANE_CUT)
@@ -1059,7 +1064,7 @@ static int render_frame(vv_context *c, int W, int H, const slice_params *slice, 
         A.slabs.r0 = r_lo; A.slabs.band = 1 << 28; A.slabs.band_stride = 0;
         A.slabs.n_regular = r_hi > r_lo ? r_hi - r_lo : 0;
     }
-    P.slice_type = ((mip || iso) && slice->type == SLICE_PLANE) ? SLICE_NONE : slice->type;      // (a MIP / iso frame has no highlight to draw: SLICE_PLANE marches as SLICE_NONE)
+    P.slice_type = ((mip || iso || proj) && slice->type == SLICE_PLANE) ? SLICE_NONE : slice->type;      // (a MIP / iso / projection frame has no highlight to draw: SLICE_PLANE marches as SLICE_NONE)
     for (int a = 0; a < 3; ++a) {
         P.slice_point[a] = slice->params[a]; P.slice_normal[a] = slice->params[3 + a];   // kernel.cu:224-225
         P.cam_pos[a] = cam->origin[a]; P.scale[a] = cam->scale[a];
@@ -1177,9 +1182,9 @@ static int render_frame(vv_context *c, int W, int H, const slice_params *slice, 
     }
     // A MIP frame's pixels beside the rectangle hold the table's entry 0, not rad_kernel's (0,0,0,0), and there is the index image: mip_fill_kernel
     // writes them, and rad_kernel gets no rectangle (it then writes no pixel and computes every slab's radius).  An iso frame likewise: it may have no
-    // RGBA image at all, and has two more (iso_fill_kernel).
+    // RGBA image at all, and has two more (iso_fill_kernel); a projection frame as an iso frame (proj_fill_kernel).
     const PixelRect mip_rect = A.rect;
-    if (mip || iso) { A.rect.x0 = 0; A.rect.y0 = 0; A.rect.x1 = INT_MAX; A.rect.y1 = INT_MAX; }
+    if (mip || iso || proj) { A.rect.x0 = 0; A.rect.y0 = 0; A.rect.x1 = INT_MAX; A.rect.y1 = INT_MAX; }
     A.tf = c->d_tf;
     int rc = ensure(c, (void **)&c->d_rad, &c->rad_cap, (size_t)P.nbx * P.nby * sizeof(float));
     if (rc) return rc;
@@ -1204,8 +1209,8 @@ static int render_frame(vv_context *c, int W, int H, const slice_params *slice, 
     A.rad = c->d_rad; A.rad_out = c->d_rad;
     A.counter = c->d_counter;
 
-    const size_t fb = (size_t)W * H * 4, ib = (size_t)W * H, hb = (size_t)W * H * 16;
-    uint8_t *d_out = rgba_out, *d_idx = index_out, *d_hit = (uint8_t *)hit_out;
+    const size_t fb = (size_t)W * H * 4, ib = (size_t)W * H, hb = (size_t)W * H * 16, sb = (size_t)W * H * 8;
+    uint8_t *d_out = rgba_out, *d_idx = index_out, *d_hit = (uint8_t *)hit_out, *d_stat = (uint8_t *)stat_out;
     // Pixels the frame does not write (column W-1, row H-1, rows of other shards) must keep the caller's bytes.  A whole
     // frame is read back as the (W-1) x (H-1) rectangle it writes; a sharded / row-limited frame goes through a staged
     // copy of the caller's buffer (rare path).
@@ -1228,9 +1233,16 @@ static int render_frame(vv_context *c, int W, int H, const slice_params *slice, 
         d_hit = c->d_hit;
         if (!whole) HIPCHK(c, hipMemcpyAsync(d_hit, hit_out, hb, hipMemcpyHostToDevice, st));
     }
-    A.pixels = (uint32_t *)d_out; A.index = d_idx; A.hit = (float4 *)d_hit;
+    if (!out_on_device && stat_out) {
+        rc = ensure(c, (void **)&c->d_stat, &c->stat_cap, sb);
+        if (rc) return rc;
+        d_stat = c->d_stat;
+        if (!whole) HIPCHK(c, hipMemcpyAsync(d_stat, stat_out, sb, hipMemcpyHostToDevice, st));
+    }
+    A.pixels = (uint32_t *)d_out; A.index = d_idx; A.hit = (float4 *)d_hit; A.stat = (uint2 *)d_stat; A.proj_mode = proj ? level : 0;
     if (((uintptr_t)d_out & 3) != 0) return fail(c, VV_ERR_INVALID, "vv_render: output buffer must be 4-byte aligned");
     if (((uintptr_t)d_hit & 15) != 0) return fail(c, VV_ERR_INVALID, "vv_render_iso: a device hit_out must be 16-byte aligned");      // (iso_kernel writes a record in one store)
+    if (((uintptr_t)d_stat & 7) != 0) return fail(c, VV_ERR_INVALID, "vv_render_projection: a device stat_out must be 8-byte aligned");      // (proj_kernel writes a record in one store)
     if (iso) {
         A.iso.level = level;
         const int dims[3] = {c->nx, c->ny, c->nz};
@@ -1261,6 +1273,12 @@ static int render_frame(vv_context *c, int W, int H, const slice_params *slice, 
             if (rect_limits) launch_iso_fill(A, mip_rect, st);
             launch_iso_build(A, st);
         }
+    } else if (proj) {
+        if (A.strips.n_strips > 0) {
+            if (W >= 2 && H >= 2) launch_rad(A, st);
+            if (rect_limits) launch_proj_fill(A, mip_rect, st);
+            launch_proj_build(A, st);
+        }
     } else if (A.phong) {
         if (A.fill_outside) { A.rad_out = nullptr; launch_rad(A, st); }          // the pixels beside the volume's screen rectangle (rad_kernel writes them; no radii here)
         launch_march(A, st);
@@ -1285,6 +1303,10 @@ static int render_frame(vv_context *c, int W, int H, const slice_params *slice, 
             if (whole) HIPCHK(c, hipMemcpy2DAsync(hit_out, (size_t)W * 16, d_hit, (size_t)W * 16, (size_t)(W - 1) * 16, (size_t)(H - 1), hipMemcpyDeviceToHost, st));
             else HIPCHK(c, hipMemcpyAsync(hit_out, d_hit, hb, hipMemcpyDeviceToHost, st));
         }
+        if (stat_out) {
+            if (whole) HIPCHK(c, hipMemcpy2DAsync(stat_out, (size_t)W * 8, d_stat, (size_t)W * 8, (size_t)(W - 1) * 8, (size_t)(H - 1), hipMemcpyDeviceToHost, st));
+            else HIPCHK(c, hipMemcpyAsync(stat_out, d_stat, sb, hipMemcpyDeviceToHost, st));
+        }
         HIPCHK(c, hipStreamSynchronize(st));
     } else if (!stream) {
         HIPCHK(c, hipStreamSynchronize(st));
@@ -1300,7 +1322,7 @@ int vv_render(vv_context *c, int W, int H, const slice_params *slice, const came
 {
     if (!c) return fail(nullptr, VV_ERR_INVALID, "vv_render: NULL context");
     if (!slice || !cam || !shading || !rays || !rgba_out) return fail(c, VV_ERR_INVALID, "vv_render: NULL argument");
-    return render_frame(c, W, H, slice, cam, shading, rays, opts, rgba_out, nullptr, nullptr, FRAME_COMPOSITE, 0, out_on_device, stream);
+    return render_frame(c, W, H, slice, cam, shading, rays, opts, rgba_out, nullptr, nullptr, nullptr, FRAME_COMPOSITE, 0, out_on_device, stream);
 }
 
 // ---- maximum-intensity projection (no reference counterpart) ---------------------------------
@@ -1314,7 +1336,7 @@ int vv_render_mip(vv_context *c, int W, int H, const slice_params *slice, const 
     shading_params unshaded;
     memset(&unshaded, 0, sizeof unshaded);
     unshaded.transferPreset = -1; unshaded.phongShading = false;
-    return render_frame(c, W, H, slice, cam, &unshaded, rays, opts, rgba_out, index_out, nullptr, FRAME_MIP, 0, out_on_device, stream);
+    return render_frame(c, W, H, slice, cam, &unshaded, rays, opts, rgba_out, index_out, nullptr, nullptr, FRAME_MIP, 0, out_on_device, stream);
 }
 
 // ---- isosurface frames: the first sample at or above a level (no reference counterpart) --------
@@ -1329,7 +1351,23 @@ int vv_render_iso(vv_context *c, int W, int H, const slice_params *slice, const 
     shading_params unshaded;
     memset(&unshaded, 0, sizeof unshaded);
     unshaded.transferPreset = -1; unshaded.phongShading = false;
-    return render_frame(c, W, H, slice, cam, &unshaded, rays, opts, rgba_out, index_out, hit_out, FRAME_ISO, level, out_on_device, stream);
+    return render_frame(c, W, H, slice, cam, &unshaded, rays, opts, rgba_out, index_out, hit_out, nullptr, FRAME_ISO, level, out_on_device, stream);
+}
+
+// ---- projection frames: maximum / minimum / mean over the samples inside the volume (no reference counterpart) --------
+int vv_render_projection(vv_context *c, int W, int H, const slice_params *slice, const camera_params *cam,
+                         const vv_ray_source *rays, const vv_render_options *opts, int mode,
+                         uint8_t *rgba_out, uint8_t *index_out, uint32_t *stat_out, int out_on_device, void *stream)
+{
+    if (!c) return fail(nullptr, VV_ERR_INVALID, "vv_render_projection: NULL context");
+    if (!slice || !cam || !rays) return fail(c, VV_ERR_INVALID, "vv_render_projection: NULL argument");
+    if (mode != VV_PROJ_MAX && mode != VV_PROJ_MIN && mode != VV_PROJ_MEAN) return fail(c, VV_ERR_INVALID, "vv_render_projection: mode must be VV_PROJ_MAX, VV_PROJ_MIN or VV_PROJ_MEAN");
+    if (!rgba_out && !index_out && !stat_out) return fail(c, VV_ERR_INVALID, "vv_render_projection: rgba_out, index_out and stat_out are all NULL");
+    if (out_on_device && ((uintptr_t)stat_out & 7) != 0) return fail(c, VV_ERR_INVALID, "vv_render_projection: a device stat_out must be 8-byte aligned");
+    shading_params unshaded;
+    memset(&unshaded, 0, sizeof unshaded);
+    unshaded.transferPreset = -1; unshaded.phongShading = false;
+    return render_frame(c, W, H, slice, cam, &unshaded, rays, opts, rgba_out, index_out, nullptr, stat_out, FRAME_PROJ, mode, out_on_device, stream);
 }
 
 int vv_classify_indices(vv_context *c, const uint8_t *index, size_t n, const float tf[1024], uint8_t *rgba_out, int on_device, void *stream)

@@ -16,7 +16,7 @@ struct SlabMap  { int r0, band, band_stride, n_regular;
                   // volume's screen rectangle, or all of them (gx0 = 0, wg = nbx, gs0 = 0, gs1 = n_regular)
                   int gx0, wg, gs0, gs1; };
 
-// the build of the march kernels a frame runs: vv_raymarch.hip, vv_mip.hip and vv_iso.hip are compiled once for each (vv_layout.h: kBuild)
+// the build of the march kernels a frame runs: vv_raymarch.hip, vv_mip.hip, vv_iso.hip and vv_proj.hip are compiled once for each (vv_layout.h: kBuild)
 // (the list generates the enum and the launcher tables below, so their orders cannot part: MB_LINEAR_BIG volumes above 4 GiB, MB_BRICKED on VolumeView::bricks,
 //  MB_BRICKED_CACHED the same for volumes up to 1 GiB, MB_ZPAIR on VolumeView::zpair, MB_ZFAST on VolumeView::zfast, MB_XPAIR on the x-pair copy, handed over in VolumeView::zpair)
 #define VV_FOR_EACH_BUILD(X) X(MB_LINEAR) X(MB_LINEAR_BIG) X(MB_BRICKED) X(MB_BRICKED_CACHED) X(MB_ZPAIR) X(MB_ZFAST) X(MB_XPAIR)
@@ -49,18 +49,21 @@ struct MarchArgs {
     uint8_t *index;             // MIP frames: device image of the per-pixel maxima, W * H bytes, or null (isosurface frames: of the hits' indices)
     float4 *hit;                // isosurface frames: device image of the hit records (x, y, z, ordinal), W * H * 16 bytes, or null
     IsoParams iso;              // isosurface frames
+    uint2 *stat;                // projection frames: device image of the records {ord, n} / {s, n}, W * H * 8 bytes, or null
+    int proj_mode;              // projection frames: vv_proj_mode
     unsigned long long *counter;
     InstrArgs I;                // bitmaps of an instrumented frame (vv_render_options::touched_bricks / touched_lines)
 };
 
-// The march, MIP and isosurface launchers, one explicit specialisation per build, each defined by the unit compiled for that build; kLaunchRaymarch[b] /
-// kLaunchMip[b] / kLaunchIso[b] is the launcher of MarchBuild b.  rad_kernel (the pre-pass of all three), mip_fill_kernel, mip_classify_kernel and
-// iso_fill_kernel live in the linear build's units.
+// The march, MIP, isosurface and projection launchers, one explicit specialisation per build, each defined by the unit compiled for that build;
+// kLaunchRaymarch[b] / kLaunchMip[b] / kLaunchIso[b] / kLaunchProj[b] is the launcher of MarchBuild b.  rad_kernel (the pre-pass of all four),
+// mip_fill_kernel, mip_classify_kernel, iso_fill_kernel and proj_fill_kernel live in the linear build's units.
 template <MarchBuild B> void launch_raymarch(const MarchArgs &a, hipStream_t s);
 template <MarchBuild B> void launch_mip(const MarchArgs &a, hipStream_t s);
 template <MarchBuild B> void launch_iso(const MarchArgs &a, hipStream_t s);
+template <MarchBuild B> void launch_proj(const MarchArgs &a, hipStream_t s);
 #define VV_X(B) template <> void launch_raymarch<B>(const MarchArgs &, hipStream_t); template <> void launch_mip<B>(const MarchArgs &, hipStream_t); \
-                template <> void launch_iso<B>(const MarchArgs &, hipStream_t);
+                template <> void launch_iso<B>(const MarchArgs &, hipStream_t); template <> void launch_proj<B>(const MarchArgs &, hipStream_t);
 VV_FOR_EACH_BUILD(VV_X)
 #undef VV_X
 using MarchLauncher = void (*)(const MarchArgs &, hipStream_t);
@@ -73,12 +76,16 @@ constexpr MarchLauncher kLaunchMip[] = { VV_FOR_EACH_BUILD(VV_X) };
 #define VV_X(B) launch_iso<B>,
 constexpr MarchLauncher kLaunchIso[] = { VV_FOR_EACH_BUILD(VV_X) };
 #undef VV_X
+#define VV_X(B) launch_proj<B>,
+constexpr MarchLauncher kLaunchProj[] = { VV_FOR_EACH_BUILD(VV_X) };
+#undef VV_X
 static_assert(sizeof(kLaunchRaymarch) / sizeof(MarchLauncher) == MB_COUNT && sizeof(kLaunchMip) / sizeof(MarchLauncher) == MB_COUNT &&
-              sizeof(kLaunchIso) / sizeof(MarchLauncher) == MB_COUNT, "one launcher per build");
+              sizeof(kLaunchIso) / sizeof(MarchLauncher) == MB_COUNT && sizeof(kLaunchProj) / sizeof(MarchLauncher) == MB_COUNT, "one launcher per build");
 void launch_rad(const MarchArgs &a, hipStream_t s);
 constexpr int kMipTableBytes = 4096;      // march_kernel's LDS table, which mip_kernel does not have: added to lds_reserve so that the blocks per CU stay what the policy measured
 void launch_mip_fill(const MarchArgs &a, const PixelRect &rect, hipStream_t s);      // M = 0 for the owned pixels outside `rect` (both images)
 void launch_iso_fill(const MarchArgs &a, const PixelRect &rect, hipStream_t s);      // no hit for the owned pixels outside `rect`: zeros in all three images
+void launch_proj_fill(const MarchArgs &a, const PixelRect &rect, hipStream_t s);     // n = 0 for the owned pixels outside `rect`: v = 0, tf[0] and {0, 0}
 void launch_mip_classify(const uint8_t *index, size_t n, const float4 *tf, uint32_t *pixels, hipStream_t s);   // pixels[i] = RGBA8 of tf[index[i]]
 void launch_build_xpair(int vtype, const void *zfast, uint32_t zf_row_bytes, uint64_t zf_slice_bytes, void *xpair, int nx, int ny, int nz, hipStream_t s);
 void launch_build_zfast(int vtype, const void *vol, uint32_t row_pitch, uint64_t slice_pitch, void *out, uint32_t zf_row_bytes, uint64_t zf_slice_bytes, int nx, int ny, int nz, hipStream_t s);

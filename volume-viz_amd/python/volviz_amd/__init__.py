@@ -30,6 +30,7 @@ FILTER_TEX8, FILTER_EXACT = 0, 1
 ERT_REFERENCE, ERT_TRUE = 0, 1
 SLAB_MAX, SLAB_MIN, SLAB_MEAN = 0, 1, 2          # vv_slab_mode
 SLAB_MAX_SAMPLES = 1024
+PROJ_MAX, PROJ_MIN, PROJ_MEAN = 0, 1, 2          # vv_proj_mode
 RAYS_IMAGES, RAYS_ANALYTIC = 0, 1
 TF_ENGINE, TF_HEAD, TF_MRI = 0, 1, 2
 # `stream` arguments: 0/None = the context's own stream, synchronous; STREAM_DEFAULT_ASYNC = the device's default (null)
@@ -113,11 +114,11 @@ EXPORTS = [
     "vv_load_volume_stream_begin", "vv_load_volume_stream_slices", "vv_load_volume_stream_end", "vv_load_volume_t3d",
     "vv_load_volume_stream_slices_async", "vv_load_volume_stream_wait_source", "vv_dataset_preset", "vv_debug_last_launch", "vv_set_frame_timing", "vv_debug_screen_rect",
     "vv_render_mip", "vv_classify_indices", "vv_render_iso", "vv_slice_slab", "vv_slice_advanced_slab",
-    "vv_volume_histogram", "vv_histogram_indices",
+    "vv_volume_histogram", "vv_histogram_indices", "vv_render_projection",
 ]
 # entry points a variant library built from an earlier tree (A/B tools, load_library(path)) may lack
 _NEWER_EXPORTS = ("vv_render_mip", "vv_classify_indices", "vv_render_iso", "vv_slice_slab", "vv_slice_advanced_slab",
-                  "vv_volume_histogram", "vv_histogram_indices")
+                  "vv_volume_histogram", "vv_histogram_indices", "vv_render_projection")
 
 _lib = None
 _libs = {}
@@ -159,6 +160,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     if hasattr(lib, "vv_render_iso"):
         lib.vv_render_iso.argtypes = [vp, i, i, C.POINTER(slice_params), C.POINTER(camera_params), C.POINTER(vv_ray_source),
                                       C.POINTER(vv_render_options), i, vp, vp, vp, i, vp]
+    if hasattr(lib, "vv_render_projection"):
+        lib.vv_render_projection.argtypes = [vp, i, i, C.POINTER(slice_params), C.POINTER(camera_params), C.POINTER(vv_ray_source),
+                                             C.POINTER(vv_render_options), i, vp, vp, vp, i, vp]
     lib.vv_slice.argtypes = [vp, vp, sz, sz, f, f, f, i, C.POINTER(f * 3), i, i, i, vp]
     lib.vv_slice_advanced.argtypes = [vp, vp, sz, sz, C.POINTER(f * 16), C.POINTER(f * 3), i, i, vp]
     if hasattr(lib, "vv_slice_slab"):
@@ -499,6 +503,38 @@ class Context:
                                          C.byref(options) if options is not None else None, int(level),
                                          rgba_ptr or None, index_ptr or None, hit_ptr or None, 1, stream))
 
+    # vv_render_projection (no reference counterpart)
+    def render_projection(self, width: int, height: int, cam: Camera, mode: int, *, slice: Optional[slice_params] = None,
+                          rays: Optional[vv_ray_source] = None, options: Optional[vv_render_options] = None,
+                          fill: int = 0, return_index: bool = False, return_stat: bool = False):
+        """Host-buffer projection frame, mode PROJ_MAX / PROJ_MIN / PROJ_MEAN over the samples inside the volume; returns rgba uint8 [H, W, 4]
+        (row 0 = bottom), or a tuple with index uint8 [H, W] (return_index) and stat uint32 [H, W, 2] (return_stat) behind it: (ordinal of the
+        extremum among the ray's executed samples, counted samples) for PROJ_MAX / PROJ_MIN, (sum, counted samples) for PROJ_MEAN.  Pixels the
+        frame does not write keep `fill` in every byte of all images."""
+        out = np.full((height, width, 4), fill, np.uint8)
+        idx = np.full((height, width), fill, np.uint8) if return_index else None
+        stat = np.full((height, width, 8), fill, np.uint8).view(np.uint32) if return_stat else None
+        sp = slice if slice is not None else make_slice_params()
+        cp = cam.params(width, height)
+        rs = rays if rays is not None else analytic_rays(cam)
+        self._chk(self.lib.vv_render_projection(self.h, width, height, C.byref(sp), C.byref(cp), C.byref(rs),
+                                                C.byref(options) if options is not None else None, int(mode),
+                                                out.ctypes.data, idx.ctypes.data if return_index else None,
+                                                stat.ctypes.data if return_stat else None, 0, None))
+        res = (out,) + ((idx,) if return_index else ()) + ((stat,) if return_stat else ())
+        return res if len(res) > 1 else out
+
+    def render_projection_device(self, width: int, height: int, cam: Camera, mode: int, rgba_ptr: int = 0, index_ptr: int = 0, stat_ptr: int = 0, *,
+                                 slice=None, rays=None, options=None, stream: int = 0):
+        """Device-buffer projection frame enqueued on `stream` (a hipStream_t as int): rgba_ptr (W*H*4 bytes), index_ptr (W*H bytes) and / or
+        stat_ptr (W*H*8 bytes, 8-byte aligned), 0 = not wanted."""
+        sp = slice if slice is not None else make_slice_params()
+        cp = cam.params(width, height)
+        rs = rays if rays is not None else analytic_rays(cam)
+        self._chk(self.lib.vv_render_projection(self.h, width, height, C.byref(sp), C.byref(cp), C.byref(rs),
+                                                C.byref(options) if options is not None else None, int(mode),
+                                                rgba_ptr or None, index_ptr or None, stat_ptr or None, 1, stream))
+
     def classify_indices(self, index: np.ndarray, tf: Optional[np.ndarray] = None) -> np.ndarray:
         """vv_classify_indices on a host index image (uint8, any shape): uint8 [..., 4] through `tf` (float32[1024]) or the context's table."""
         index = np.ascontiguousarray(index, np.uint8)
@@ -541,7 +577,7 @@ class Context:
         """vv_debug_last_launch: what the launch policy chose for the last render."""
         out = (C.c_int * 8)()
         self._chk(self.lib.vv_debug_last_launch(self.h, out))
-        k = ("tile_log2w", "blk_log2w", "unroll", "lds_reserve", "layout", "view_known", "density_x1000", "phong")     # phong: 0 unshaded, 1 Phong, 2 MIP, 3 isosurface
+        k = ("tile_log2w", "blk_log2w", "unroll", "lds_reserve", "layout", "view_known", "density_x1000", "phong")     # phong: 0 unshaded, 1 Phong, 2 MIP, 3 isosurface, 4 projection
         return dict(zip(k, list(out)))
 
     def reread_env(self):
