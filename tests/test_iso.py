@@ -10,9 +10,11 @@ import numpy as np
 import pytest
 
 import iso_model as IM
+import mip_oracle as MO
 import oracle_lib as O
 import volviz_amd as vv
 import witness as Wt
+from test_mip_geometry import RECT_CAMS, RECT_OFF_SCREEN, _rect_case, _rect_volume
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CAM_A = vv.Camera.orbit(3.0, 1.0, 0.6)
@@ -480,3 +482,67 @@ def test_iso_leaves_the_context_alone_and_reports_errors(ctx, monkeypatch):
             empty.render_iso(W, H, CAM_A, 40)
         assert e.value.code == ERR_NO_VOLUME
     assert np.array_equal(ctx.render(W, H, CAM_A, fill=1), O.render(vol, tf, W, H, CAM_A, fill=1)[0])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the screen rectangle and the fill beside it (fill_outside_kernel, shared with the MIP and projection frames): test_mip_geometry's frames
+# ---------------------------------------------------------------------------------------------------------------------
+RECT_CIS = (0, 1, RECT_OFF_SCREEN)               # cube partly off the left edge, partly off the bottom, wholly off the screen
+RECT_MIN_HIT_SHARE = {0: 0.10, 1: 0.015}         # of the (W-1) x (H-1) pixels; the model gives 0.135 and 0.0187 (levels 146 and 136)
+
+
+def _rect_calls(H):
+    return [{}, {"shard": (4, 2, 0)}, {"shard": (4, 2, 1)}] + ([{"slab_rows": (1, 3)}] if H >= 43 else [])
+
+
+@functools.lru_cache(maxsize=None)
+def _rect_frames(ci):
+    """(W, H, level, table, calls, the model's frame for each call) of one rectangle camera: computed once, shared, read-only.  The level is the median
+    of the MIP model's non-zero indices (128 where it has none: the cube is off the screen)."""
+    W, H, M = _rect_case(ci)
+    level = _median_level(M) if M.any() else 128
+    tf = _colour_table(17)
+    calls = _rect_calls(H)
+    models = [_model(_rect_volume(), tf, W, H, RECT_CAMS[ci], level, **kw) for kw in calls]
+    for m in models:
+        for a in m.values():
+            if isinstance(a, np.ndarray):
+                a.setflags(write=False)
+    return W, H, level, tf, calls, models
+
+
+@pytest.mark.parametrize("ci", RECT_CIS)
+def test_iso_screen_rectangle_preconditions(ci):
+    """What keeps test_iso_screen_rectangle_and_fill from passing on an empty frame (the models alone)."""
+    W, H, level, _, calls, models = _rect_frames(ci)
+    whole = models[0]
+    assert whole["written"][:-1, :-1].all() and whole["written"].sum() == (W - 1) * (H - 1)
+    hit = whole["written"] & (whole["hit"][..., 3] > 0)
+    share = hit.sum() / ((W - 1) * (H - 1))
+    print(f"camera {ci} {W}x{H}: level {level}, hit on {share:.4f} of the written pixels")
+    if ci == RECT_OFF_SCREEN:
+        assert not hit.any()                      # every pixel is the fill kernel's
+    else:
+        assert share >= RECT_MIN_HIT_SHARE[ci], f"camera {ci}: a hit on {share:.4f} of the pixels only"
+        assert (whole["written"] & ~hit).sum() > hit.sum()       # most written pixels lie beside the cube
+    assert (whole["rgba"][whole["written"] & ~hit] == 0).all() and FILL != 0           # "no hit" is told from the fill byte
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ci", RECT_CIS)
+def test_iso_screen_rectangle_and_fill(ctx, ci):
+    """iso_kernel covers the tiles under the volume's screen rectangle, fill_outside_kernel writes "no hit" (zeros in all three images) beside it: whole
+    frames, both shards of two, a row range, and the same frames with the rectangle switched off -- all equal to the model, bit for bit."""
+    vol, cam = _rect_volume(), RECT_CAMS[ci]
+    W, H, level, tf, calls, models = _rect_frames(ci)
+    frames = {}
+    for rect in (None, "0"):
+        with MO.knobs(ctx, {} if rect is None else {"VV_RECT": rect}):
+            ctx.load_volume(vol, tf)
+            for k, kw in enumerate(calls):
+                frames[rect, k] = _iso(ctx, W, H, cam, level, options=vv.make_options(**kw))
+                _same_triple(frames[rect, k], models[k], f"camera {ci} {W}x{H} level {level} VV_RECT={rect} {kw}")
+                assert ctx.last_launch()["phong"] == 3
+    for k in range(len(calls)):
+        for a, b in zip(frames[None, k], frames["0", k]):
+            _same(a, b, f"camera {ci} {calls[k]}: with and without the rectangle")

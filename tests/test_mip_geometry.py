@@ -1,6 +1,6 @@
 """Maximum-intensity projection: every kernel build, the frame's edges and the launch geometry, against the level-set sweep of the CPU oracle.
 
-tests/test_mip.py pins the MIP frame itself; this module drives mip_kernel / mip_fill_kernel through the mechanisms they share with (but hold their own
+tests/test_mip.py pins the MIP frame itself; this module drives mip_kernel / fill_outside_kernel through the mechanisms they share with (but hold their own
 copy of) the compositing path: the seven builds, the screen rectangle and its fill, the block-to-pixel mapping, tiny and ragged frames, odd volume shapes
 and the instruments.  Every comparison is exact, covers every pixel of both images (RGBA and index) over a non-zero fill byte, and takes its expectation
 from MO.sweep / MO.written_mask / MO.rgba_of / MO.executed_samples alone.  One sweep per camera serves all of its knob sets, shards and row ranges.
@@ -16,7 +16,7 @@ Coverage (rows: what could be wrong; cells: the test that would notice):
                 XCD bands 0 / 1 / 3                                                                  test_mip_block_to_pixel_mapping
                 block shapes 8 x 32, 16 x 16, 32 x 8, 64 x 4, 128 x 2; wave tiles 8 x 8, 16 x 4, 32 x 2  test_mip_block_to_pixel_mapping
                 no LDS reserve (more blocks per CU)                                                  test_mip_block_to_pixel_mapping
-                mip_fill_kernel: rectangle partly / wholly off the screen, no rectangle, VV_RECT=0,
+                fill_outside_kernel: rectangle partly / wholly off the screen, no rectangle, VV_RECT=0,
                 shards and row ranges that cut the rectangle                                         test_mip_screen_rectangle_and_fill
                 instruments (sample count, slots, touched bricks, touched lines)                     test_mip_instruments_equal_the_march
   edges         frames of 1 x 1 ... 16 x 15 and 29 x 43 (no rad_kernel, no fill below 2 pixels)      test_mip_tiny_frames
@@ -135,7 +135,7 @@ def test_screen_rectangle_preconditions(ci):
     if ci == RECT_OFF_SCREEN:
         assert not M.any()
         written = _written(_rect_volume(), W, H, RECT_CAMS[ci], {})
-        assert written[:-1, :-1].all() and not written[-1].any() and not written[:, -1].any()       # every pixel is mip_fill_kernel's
+        assert written[:-1, :-1].all() and not written[-1].any() and not written[:, -1].any()       # every pixel is fill_outside_kernel's
     else:
         share, levels = MO.share_and_levels(M)
         assert share >= 0.03, f"camera {ci}: M > 0 on {share:.3f} of the pixels only"
@@ -145,7 +145,7 @@ def test_screen_rectangle_preconditions(ci):
 @pytest.mark.gpu
 @pytest.mark.parametrize("ci", range(len(RECT_CAMS)))
 def test_mip_screen_rectangle_and_fill(ctx, ci):
-    """mip_kernel covers the tiles under the volume's screen rectangle, mip_fill_kernel writes table entry 0 / index 0 beside it: whole frames, both shards
+    """mip_kernel covers the tiles under the volume's screen rectangle, fill_outside_kernel writes table entry 0 / index 0 beside it: whole frames, both shards
     of two, a row range, and the same frames with the rectangle switched off -- all equal to one expectation."""
     vol, cam = _rect_volume(), RECT_CAMS[ci]
     W, H, M = _rect_case(ci)

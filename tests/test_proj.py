@@ -17,6 +17,7 @@ import oracle_lib as O
 import proj_model as PM
 import volviz_amd as vv
 import witness as Wt
+from test_mip_geometry import RECT_CAMS, RECT_OFF_SCREEN, RECT_SIZES, _rect_volume
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CAM_A = vv.Camera.orbit(3.0, 1.0, 0.6)
@@ -583,3 +584,65 @@ def test_projection_leaves_the_context_alone_and_reports_errors(ctx, monkeypatch
     m = _model(vol, tf, W, H, CAM_A, PM.PROJ_MIN)
     _same_triple(_proj(ctx, W, H, CAM_A, PM.PROJ_MIN), m, "a projection frame after the failed calls")
     assert np.array_equal(ctx.render(W, H, CAM_A, fill=1), O.render(vol, tf, W, H, CAM_A, fill=1)[0])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the screen rectangle and the fill beside it (fill_outside_kernel, shared with the MIP and isosurface frames): test_mip_geometry's frames
+# ---------------------------------------------------------------------------------------------------------------------
+RECT_CIS = (0, 1, RECT_OFF_SCREEN)               # cube partly off the left edge, partly off the bottom, wholly off the screen
+RECT_MIN_COUNTED_SHARE = {0: 0.25, 1: 0.03}      # n > 0, of the (W-1) x (H-1) pixels; the model gives 0.260 and 0.0354
+RECT_MIN_VALUES = 50                             # distinct v among those pixels, in every mode; the model's minimum is 55
+
+
+def _rect_calls(H):
+    return [{}, {"shard": (4, 2, 0)}, {"shard": (4, 2, 1)}] + ([{"slab_rows": (1, 3)}] if H >= 43 else [])
+
+
+@functools.lru_cache(maxsize=None)
+def _rect_frames(ci, mode):
+    """(W, H, table, calls, the model's frame for each call) of one rectangle camera and mode: computed once, shared, read-only."""
+    W, H = RECT_SIZES[ci]
+    tf = _colour_table(17)
+    assert (PM.rgba_of(tf, 0) != FILL).all()                    # the fill kernel's RGBA differs from the fill byte in every channel
+    calls = _rect_calls(H)
+    return W, H, tf, calls, [_freeze(_model(_rect_volume(), tf, W, H, RECT_CAMS[ci], mode, **kw)) for kw in calls]
+
+
+@pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
+@pytest.mark.parametrize("ci", RECT_CIS)
+def test_projection_screen_rectangle_preconditions(ci, mode):
+    """What keeps test_projection_screen_rectangle_and_fill from passing on an empty frame (the models alone)."""
+    W, H, _, calls, models = _rect_frames(ci, mode)
+    whole = models[0]
+    assert whole["written"][:-1, :-1].all() and whole["written"].sum() == (W - 1) * (H - 1)
+    counted = whole["written"] & (whole["n"] > 0)
+    share = counted.sum() / ((W - 1) * (H - 1))
+    values = len(np.unique(whole["index"][counted]))
+    print(f"camera {ci} {W}x{H} mode {mode}: n > 0 on {share:.4f} of the written pixels, {values} distinct v")
+    if ci == RECT_OFF_SCREEN:
+        assert not counted.any()                  # every pixel is the fill kernel's
+    else:
+        assert share >= RECT_MIN_COUNTED_SHARE[ci], f"camera {ci}: n > 0 on {share:.4f} of the pixels only"
+        assert values >= RECT_MIN_VALUES, f"camera {ci} mode {mode}: {values} distinct v only"
+        assert 2 * (whole["written"] & ~counted).sum() > whole["written"].sum()       # more than half of the written pixels are the fill's (n == 0)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
+@pytest.mark.parametrize("ci", RECT_CIS)
+def test_projection_screen_rectangle_and_fill(ctx, ci, mode):
+    """proj_kernel covers the tiles under the volume's screen rectangle, fill_outside_kernel writes n = 0 (v = 0, table entry 0, {0, 0}) beside it:
+    whole frames, both shards of two, a row range, and the same frames with the rectangle switched off -- all equal to the model, bit for bit."""
+    vol, cam = _rect_volume(), RECT_CAMS[ci]
+    W, H, tf, calls, models = _rect_frames(ci, mode)
+    frames = {}
+    for rect in (None, "0"):
+        with MO.knobs(ctx, {} if rect is None else {"VV_RECT": rect}):
+            ctx.load_volume(vol, tf)
+            for k, kw in enumerate(calls):
+                frames[rect, k] = _proj(ctx, W, H, cam, mode, options=vv.make_options(**kw))
+                _same_triple(frames[rect, k], models[k], f"camera {ci} {W}x{H} mode {mode} VV_RECT={rect} {kw}")
+                assert ctx.last_launch()["phong"] == 4
+    for k in range(len(calls)):
+        for a, b in zip(frames[None, k], frames["0", k]):
+            _same(a, b, f"camera {ci} mode {mode} {calls[k]}: with and without the rectangle")

@@ -971,25 +971,33 @@ static bool screen_rect(const MarchArgs &A, int W, int H, double *xmin, double *
     return true;
 }
 
-static void launch_march(const MarchArgs &A, hipStream_t st) { assert(A.build < MB_COUNT); kLaunchRaymarch[A.build](A, st); }
-static void launch_mip_build(const MarchArgs &A, hipStream_t st) { assert(A.build < MB_COUNT); kLaunchMip[A.build](A, st); }
-static void launch_iso_build(const MarchArgs &A, hipStream_t st) { assert(A.build < MB_COUNT); kLaunchIso[A.build](A, st); }
-static void launch_proj_build(const MarchArgs &A, hipStream_t st) { assert(A.build < MB_COUNT); kLaunchProj[A.build](A, st); }
+static void launch_build(FrameKind kind, const MarchArgs &A, hipStream_t st) { assert(A.build < MB_COUNT); kLaunch[frame_row(kind)][A.build](A, st); }
 
-// what a frame keeps of its samples: their composite (vv_render), their maximum (vv_render_mip), the first at or above a level (vv_render_iso) or the
-// maximum / minimum / mean of those inside the volume (vv_render_projection).
-// The values are vv_debug_last_launch's kernel family of the three unshaded-only kinds (composite frames report 0 or 1 with the shading).
-enum FrameKind { FRAME_COMPOSITE = 0, FRAME_MIP = 2, FRAME_ISO = 3, FRAME_PROJ = 4 };
+// One output image of a frame.  render_frame describes the four once (rgba, index, hit, stat: the order of every enqueued copy) and stages, checks and
+// reads them back in loops over that table.
+struct FrameImage {
+    void *host;                         // the caller's buffer (on the device when out_on_device), or null: not asked for
+    size_t px_bytes;                    // bytes per pixel
+    uint8_t **scratch; size_t *cap;     // the context's staging buffer of a host-buffer frame
+    unsigned align;                     // of the device pointer the kernels write through (a record is written in one store)
+    const char *misaligned;             // vv_last_error text of a misaligned device pointer
+    uint8_t *dev;                       // where the kernels write: `host` itself, or *scratch
+};
 
-// One frame: vv_render (FRAME_COMPOSITE: rgba_out, shading), vv_render_mip (FRAME_MIP: rgba_out and / or index_out, never Phong) and vv_render_iso
-// (FRAME_ISO: any of rgba_out, index_out, hit_out; `level`; never Phong) and vv_render_projection (FRAME_PROJ: any of rgba_out, index_out, stat_out; `level`
-// holds the vv_proj_mode; never Phong).  All share the argument checks, the frame and shard set-up, the launch policy, the screen rectangle and the
-// output staging; only the kernels differ.
-static int render_frame(vv_context *c, int W, int H, const slice_params *slice, const camera_params *cam,
-                        const shading_params *shading, const vv_ray_source *rays, const vv_render_options *opts,
-                        uint8_t *rgba_out, uint8_t *index_out, float *hit_out, uint32_t *stat_out, FrameKind kind, int level, int out_on_device, void *stream)
+// What the stages of render_frame hand on to each other.
+struct Frame {
+    MarchArgs A;
+    FrameKind kind; int W, H; hipStream_t st;
+    bool have_basis; float density;     // what the launch policy knows about the view: P.side is filled in; voxels of volume per sample (unknown ray source: sparse)
+    bool beyond_caches;                 // choose_launch's verdict
+    bool rect_limits; PixelRect fill_rect;      // unshaded frames: the screen rectangle limits the launch; the pixels the tiles cover (what launch_fill leaves alone)
+    bool whole;                         // the frame writes the whole (W-1) x (H-1) rectangle: no shards, no row limits
+    FrameImage img[4];
+};
+
+// stage 1: the arguments every frame kind checks before it touches the device
+static int check_frame_args(vv_context *c, int W, int H, const slice_params *slice, const camera_params *cam, const vv_ray_source *rays)
 {
-    const bool mip = kind == FRAME_MIP, iso = kind == FRAME_ISO, proj = kind == FRAME_PROJ;
     if (W < 1 || H < 1) return fail(c, VV_ERR_INVALID, "vv_render: width/height must be >= 1");
     if (!c->d_vol || !c->have_tf) return fail(c, VV_ERR_NO_VOLUME, "vv_render: no volume / transfer function loaded");
     if (slice->type != SLICE_NONE && slice->type != SLICE_PLANE && slice->type != SLICE_PLANE_CUT)
@@ -1001,12 +1009,16 @@ static int render_frame(vv_context *c, int W, int H, const slice_params *slice, 
     for (int a = 0; a < 3; ++a)
         if (!(cam->scale[a] > 0.f) || !std::isfinite(cam->scale[a]))
             return fail(c, VV_ERR_INVALID, "vv_render: camera scale must be finite and > 0");
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = pick_stream(c, stream);
+    return VV_OK;
+}
 
-    MarchArgs A;
-    memset(&A, 0, sizeof A);
+// stage 2: options and camera -> FrameParams, and the grid maps of the shard / slab rows this call launches
+static int frame_params(vv_context *c, Frame &F, const slice_params *slice, const camera_params *cam, const vv_ray_source *rays, const vv_render_options *opts)
+{
+    MarchArgs &A = F.A;
     FrameParams &P = A.P;
+    const int W = F.W, H = F.H;
+    const bool reducer = F.kind != FRAME_COMPOSITE;
     P.W = W; P.H = H;
     P.nbx = W / kSlab + ((W % kSlab) ? 1 : 0);                         // kernel.cu:418-425
     P.nby = H / kSlab + ((H % kSlab) ? 1 : 0);
@@ -1064,7 +1076,7 @@ static int render_frame(vv_context *c, int W, int H, const slice_params *slice, 
         A.slabs.r0 = r_lo; A.slabs.band = 1 << 28; A.slabs.band_stride = 0;
         A.slabs.n_regular = r_hi > r_lo ? r_hi - r_lo : 0;
     }
-    P.slice_type = ((mip || iso || proj) && slice->type == SLICE_PLANE) ? SLICE_NONE : slice->type;      // (a MIP / iso / projection frame has no highlight to draw: SLICE_PLANE marches as SLICE_NONE)
+    P.slice_type = (reducer && slice->type == SLICE_PLANE) ? SLICE_NONE : slice->type;      // (a MIP / iso / projection frame has no highlight to draw: SLICE_PLANE marches as SLICE_NONE)
     for (int a = 0; a < 3; ++a) {
         P.slice_point[a] = slice->params[a]; P.slice_normal[a] = slice->params[3 + a];   // kernel.cu:224-225
         P.cam_pos[a] = cam->origin[a]; P.scale[a] = cam->scale[a];
@@ -1079,10 +1091,21 @@ static int render_frame(vv_context *c, int W, int H, const slice_params *slice, 
                      P.step[0] <= kSafeDivStepMax && P.step[1] <= kSafeDivStepMax && P.step[2] <= kSafeDivStepMax;          // (>= kStepMin and finite: checked above)
     }
     P.ray_mode = rays->mode; P.quantize8 = rays->quantize8;
-    // What the launch policy below knows about the view (speed only): the camera basis -- given (analytic rays), hinted (an image
-    // source whose look / up fields are filled in: the host that drew the first pass knows its camera) or estimated from the images.
-    bool have_basis = false;
-    float density = 1e9f;                           // voxels of volume per sample; unknown ray source: treat as sparse
+    return VV_OK;
+}
+
+// stage 3: what the launch policy knows about the view (speed only): the camera basis -- given (analytic rays), hinted (an image
+// source whose look / up fields are filled in: the host that drew the first pass knows its camera) or estimated from the images.
+// Host images of an image ray source are uploaded here.
+static int view_knowledge(vv_context *c, Frame &F, const camera_params *cam, const vv_ray_source *rays, void *stream)
+{
+    FrameParams &P = F.A.P;
+    const int W = F.W, H = F.H;
+    hipStream_t st = F.st;
+    bool &have_basis = F.have_basis;
+    float &density = F.density;
+    have_basis = false;
+    density = 1e9f;                                 // voxels of volume per sample; unknown ray source: treat as sparse
     if (rays->mode == VV_RAYS_ANALYTIC) {
         int brc = camera_basis(c, P, cam, rays, W, H);
         if (brc) return brc;
@@ -1135,115 +1158,177 @@ static int render_frame(vv_context *c, int W, int H, const slice_params *slice, 
             }
         }
     }
-    const bool beyond_caches = choose_launch(c, A, cam, rays, shading, have_basis, density, H, st);
-    density = c->last_density;
-    A.gray = c->tf_gray; A.phong = shading->phongShading;
-    // march_kernel's tiles: those under the volume's screen rectangle (screen_rect), or all of them
-    bool rect_limits = false;
-    {
-        StripMap &M = A.strips;
-        const int bw = 1 << M.blk_log2w, bh = 256 >> M.blk_log2w;
-        M.tx0 = 0; M.wr = (W + bw - 1) >> M.blk_log2w; M.s0 = 0; M.s1 = M.n_strips;
-        A.rect.x0 = 0; A.rect.y0 = 0; A.rect.x1 = INT_MAX; A.rect.y1 = INT_MAX;
-        double xmin, xmax, ymin, ymax;
-        SlabMap &S = A.slabs;
-        S.gx0 = 0; S.wg = P.nbx; S.gs0 = 0; S.gs1 = S.n_regular;
-        A.fill_outside = false;
-        const bool have_rect = c->knobs.rect != 0 && rays->mode == VV_RAYS_ANALYTIC && W >= 2 && H >= 2 && screen_rect(A, W, H, &xmin, &xmax, &ymin, &ymax);
-        if (have_rect && A.phong && S.n_regular > 0) {
-            // march_phong_kernel: the slabs whose own 14 x 14 pixels meet the rectangle.  A pixel is written by the slab that owns it (pin 10): when W == 1 (mod 14)
-            // pixel column W-2 lies in slab column nbx-2 and belongs to nbx-1, which therefore comes along; the extra slab row is always launched.
-            auto slab_of = [](double v, int lo, int hi) { const double t = floor(v / kSlab); return t < lo ? lo : (t > hi ? hi : (int)t); };
-            int gx0 = slab_of(xmin, 0, P.nbx), gx1 = slab_of(xmax, -1, P.nbx - 1) + 1;
-            if (P.conflict_x && gx1 == P.nbx - 1) gx1 = P.nbx;
-            if (gx1 < gx0) gx1 = gx0;
-            S.gx0 = gx0; S.wg = gx1 - gx0;
-            A.rect.x0 = gx0 * kSlab; A.rect.x1 = gx1 >= P.nbx ? INT_MAX : gx1 * kSlab;
-            if (s_count <= 1) {
-                S.gs0 = slab_of(ymin, S.r0, S.r0 + S.n_regular) - S.r0; S.gs1 = slab_of(ymax, S.r0 - 1, S.r0 + S.n_regular - 1) + 1 - S.r0;
-                if (S.gs1 < S.gs0) S.gs1 = S.gs0;
-                A.rect.y0 = (S.r0 + S.gs0) * kSlab; A.rect.y1 = (S.r0 + S.gs1) * kSlab;
-            }
-            if (S.wg == 0 || S.gs1 == S.gs0) { S.wg = 0; A.rect.x0 = A.rect.x1 = A.rect.y0 = A.rect.y1 = 0; }
-            A.fill_outside = true;
+    return VV_OK;
+}
+
+// stage 4: the unshaded kernels' tiles / march_phong_kernel's slabs: those under the volume's screen rectangle (screen_rect), or all of them
+static void tiles_under_rect(const vv_context *c, Frame &F, const vv_ray_source *rays)
+{
+    MarchArgs &A = F.A;
+    const FrameParams &P = A.P;
+    const int W = F.W, H = F.H, s_count = P.count;
+    bool &rect_limits = F.rect_limits;
+    rect_limits = false;
+    StripMap &M = A.strips;
+    const int bw = 1 << M.blk_log2w, bh = 256 >> M.blk_log2w;
+    M.tx0 = 0; M.wr = (W + bw - 1) >> M.blk_log2w; M.s0 = 0; M.s1 = M.n_strips;
+    A.rect.x0 = 0; A.rect.y0 = 0; A.rect.x1 = INT_MAX; A.rect.y1 = INT_MAX;
+    double xmin, xmax, ymin, ymax;
+    SlabMap &S = A.slabs;
+    S.gx0 = 0; S.wg = P.nbx; S.gs0 = 0; S.gs1 = S.n_regular;
+    A.fill_outside = false;
+    const bool have_rect = c->knobs.rect != 0 && rays->mode == VV_RAYS_ANALYTIC && W >= 2 && H >= 2 && screen_rect(A, W, H, &xmin, &xmax, &ymin, &ymax);
+    if (have_rect && A.phong && S.n_regular > 0) {
+        // march_phong_kernel: the slabs whose own 14 x 14 pixels meet the rectangle.  A pixel is written by the slab that owns it (pin 10): when W == 1 (mod 14)
+        // pixel column W-2 lies in slab column nbx-2 and belongs to nbx-1, which therefore comes along; the extra slab row is always launched.
+        auto slab_of = [](double v, int lo, int hi) { const double t = floor(v / kSlab); return t < lo ? lo : (t > hi ? hi : (int)t); };
+        int gx0 = slab_of(xmin, 0, P.nbx), gx1 = slab_of(xmax, -1, P.nbx - 1) + 1;
+        if (P.conflict_x && gx1 == P.nbx - 1) gx1 = P.nbx;
+        if (gx1 < gx0) gx1 = gx0;
+        S.gx0 = gx0; S.wg = gx1 - gx0;
+        A.rect.x0 = gx0 * kSlab; A.rect.x1 = gx1 >= P.nbx ? INT_MAX : gx1 * kSlab;
+        if (s_count <= 1) {
+            S.gs0 = slab_of(ymin, S.r0, S.r0 + S.n_regular) - S.r0; S.gs1 = slab_of(ymax, S.r0 - 1, S.r0 + S.n_regular - 1) + 1 - S.r0;
+            if (S.gs1 < S.gs0) S.gs1 = S.gs0;
+            A.rect.y0 = (S.r0 + S.gs0) * kSlab; A.rect.y1 = (S.r0 + S.gs1) * kSlab;
         }
-        if (have_rect && !A.phong && M.n_strips > 0) {
-            auto tile_of = [](double v, int unit, int lo, int hi) { const double t = floor(v / unit); return t < lo ? lo : (t > hi ? hi : (int)t); };
-            const int ntx = M.wr;
-            M.tx0 = tile_of(xmin, bw, 0, ntx); M.wr = tile_of(xmax, bw, -1, ntx - 1) + 1 - M.tx0;
-            if (s_count <= 1) { M.s0 = tile_of(ymin - M.y0, bh, 0, M.n_strips); M.s1 = tile_of(ymax - M.y0, bh, -1, M.n_strips - 1) + 1; }
-            if (M.wr < 0) M.wr = 0;
-            if (M.s1 < M.s0) M.s1 = M.s0;
-            A.rect.x0 = M.tx0 * bw; A.rect.x1 = (M.tx0 + M.wr) * bw;
-            if (s_count <= 1) { A.rect.y0 = M.y0 + M.s0 * bh; A.rect.y1 = M.y0 + M.s1 * bh; }
-            if (M.wr == 0 || M.s1 == M.s0) { A.rect.x0 = A.rect.x1 = A.rect.y0 = A.rect.y1 = 0; }       // (the cube is off the screen: every pixel is rad_kernel's)
-            rect_limits = true;
-        }
+        if (S.wg == 0 || S.gs1 == S.gs0) { S.wg = 0; A.rect.x0 = A.rect.x1 = A.rect.y0 = A.rect.y1 = 0; }
+        A.fill_outside = true;
     }
-    // A MIP frame's pixels beside the rectangle hold the table's entry 0, not rad_kernel's (0,0,0,0), and there is the index image: mip_fill_kernel
-    // writes them, and rad_kernel gets no rectangle (it then writes no pixel and computes every slab's radius).  An iso frame likewise: it may have no
-    // RGBA image at all, and has two more (iso_fill_kernel); a projection frame as an iso frame (proj_fill_kernel).
-    const PixelRect mip_rect = A.rect;
-    if (mip || iso || proj) { A.rect.x0 = 0; A.rect.y0 = 0; A.rect.x1 = INT_MAX; A.rect.y1 = INT_MAX; }
-    A.tf = c->d_tf;
-    int rc = ensure(c, (void **)&c->d_rad, &c->rad_cap, (size_t)P.nbx * P.nby * sizeof(float));
-    if (rc) return rc;
-    // Balanced, heaviest-first tile order (StripMap::order, built by rad_kernel's extra block): analytic rays (the weights are the centre rays' chords),
-    // 8 ... 1024 units of at most 16 x-adjacent tiles.  VV_LPT=0 switches it off, VV_LPT_RUN sets the unit length.
-    // (units, their number and the table's size: vv_tiles.h)
+    if (have_rect && !A.phong && M.n_strips > 0) {
+        auto tile_of = [](double v, int unit, int lo, int hi) { const double t = floor(v / unit); return t < lo ? lo : (t > hi ? hi : (int)t); };
+        const int ntx = M.wr;
+        M.tx0 = tile_of(xmin, bw, 0, ntx); M.wr = tile_of(xmax, bw, -1, ntx - 1) + 1 - M.tx0;
+        if (s_count <= 1) { M.s0 = tile_of(ymin - M.y0, bh, 0, M.n_strips); M.s1 = tile_of(ymax - M.y0, bh, -1, M.n_strips - 1) + 1; }
+        if (M.wr < 0) M.wr = 0;
+        if (M.s1 < M.s0) M.s1 = M.s0;
+        A.rect.x0 = M.tx0 * bw; A.rect.x1 = (M.tx0 + M.wr) * bw;
+        if (s_count <= 1) { A.rect.y0 = M.y0 + M.s0 * bh; A.rect.y1 = M.y0 + M.s1 * bh; }
+        if (M.wr == 0 || M.s1 == M.s0) { A.rect.x0 = A.rect.x1 = A.rect.y0 = A.rect.y1 = 0; }       // (the cube is off the screen: every pixel is rad_kernel's)
+        rect_limits = true;
+    }
+    // The pixels beside the rectangle of a MIP, isosurface or projection frame are not rad_kernel's (0,0,0,0): they hold the table's entry 0 or no RGBA
+    // image at all, and there are the other images.  fill_outside_kernel writes them, and rad_kernel gets no rectangle (it then writes no pixel and computes
+    // every slab's radius).
+    F.fill_rect = A.rect;
+    if (F.kind != FRAME_COMPOSITE) { A.rect.x0 = 0; A.rect.y0 = 0; A.rect.x1 = INT_MAX; A.rect.y1 = INT_MAX; }
+}
+
+// stage 5: balanced, heaviest-first tile order (StripMap::order, built by rad_kernel's extra block): analytic rays (the weights are the centre rays' chords),
+// 8 ... 1024 units of at most 16 x-adjacent tiles.  VV_LPT=0 switches it off, VV_LPT_RUN sets the unit length.
+// (units, their number and the table's size: vv_tiles.h)
+static int tile_order(vv_context *c, Frame &F, const vv_ray_source *rays)
+{
+    MarchArgs &A = F.A;
+    const int W = F.W, H = F.H;
+    const bool beyond_caches = F.beyond_caches;
     A.strips.order = nullptr; A.order_out = nullptr;
-    {
-        const int wr = A.strips.wr, ns = A.strips.s1 - A.strips.s0;
-        A.strips.order_run = wr > 0 ? (wr + (wr + 15) / 16 - 1) / ((wr + 15) / 16) : 1;                  // the strip in ceil(wr / 16) equal runs
-        if (c->knobs.lpt_run > 0 && c->knobs.lpt_run <= 256) A.strips.order_run = c->knobs.lpt_run;
-        const int units = wr > 0 ? order_units(A.strips) : 0;
-        // Measured (tools/ab_rep.sh, profiles/EXPERIMENTS.md part A5): aligned views of volumes up to 1 GiB gain 4 % (C2, 512^3, u8 1024^3); volumes beyond the
-        // caches lose 1-6 % (the heaviest tiles marching together move more bytes), oblique views gain or lose up to 15 % with the camera: there the strips stay.
-        const bool want = c->knobs.lpt > 0 ? true : (A.strips.tile_log2w == 5 && !beyond_caches && (long long)wr * ns >= 1024);      // (C1's 576 tiles: +2 %, the sort outlasts the rad pre-pass)
-        if (c->knobs.lpt != 0 && want && !A.phong && rays->mode == VV_RAYS_ANALYTIC && W >= 2 && H >= 2 && units >= 8 && units <= 1024 && (long long)(wr + 1) * (ns + 1) <= 24576) {     // (rad_kernel: kMaxUnits, kMaxPoints)
-            rc = ensure(c, (void **)&c->d_order, &c->order_cap, std::max((size_t)order_words(A.strips), (size_t)65536) * sizeof(uint32_t));
-            if (rc) return rc;
-            A.strips.order = c->d_order; A.order_out = c->d_order;
-        } else A.strips.order_run = 1;
+    const int wr = A.strips.wr, ns = A.strips.s1 - A.strips.s0;
+    A.strips.order_run = wr > 0 ? (wr + (wr + 15) / 16 - 1) / ((wr + 15) / 16) : 1;                  // the strip in ceil(wr / 16) equal runs
+    if (c->knobs.lpt_run > 0 && c->knobs.lpt_run <= 256) A.strips.order_run = c->knobs.lpt_run;
+    const int units = wr > 0 ? order_units(A.strips) : 0;
+    // Measured (tools/ab_rep.sh, profiles/EXPERIMENTS.md part A5): aligned views of volumes up to 1 GiB gain 4 % (C2, 512^3, u8 1024^3); volumes beyond the
+    // caches lose 1-6 % (the heaviest tiles marching together move more bytes), oblique views gain or lose up to 15 % with the camera: there the strips stay.
+    const bool want = c->knobs.lpt > 0 ? true : (A.strips.tile_log2w == 5 && !beyond_caches && (long long)wr * ns >= 1024);      // (C1's 576 tiles: +2 %, the sort outlasts the rad pre-pass)
+    if (c->knobs.lpt != 0 && want && !A.phong && rays->mode == VV_RAYS_ANALYTIC && W >= 2 && H >= 2 && units >= 8 && units <= 1024 && (long long)(wr + 1) * (ns + 1) <= 24576) {     // (rad_kernel: kMaxUnits, kMaxPoints)
+        const int rc = ensure(c, (void **)&c->d_order, &c->order_cap, std::max((size_t)order_words(A.strips), (size_t)65536) * sizeof(uint32_t));
+        if (rc) return rc;
+        A.strips.order = c->d_order; A.order_out = c->d_order;
+    } else A.strips.order_run = 1;
+    return VV_OK;
+}
+
+// stage 6: where the kernels write.  Pixels the frame does not write (column W-1, row H-1, rows of other shards) must keep the caller's bytes.  A whole
+// frame is read back as the (W-1) x (H-1) rectangle it writes; a sharded / row-limited frame goes through a staged copy of the caller's buffer (rare path).
+static int stage_images(vv_context *c, Frame &F, int out_on_device)
+{
+    const size_t npx = (size_t)F.W * F.H;
+    for (FrameImage &im : F.img) {
+        im.dev = (uint8_t *)im.host;
+        if (out_on_device || !im.host) continue;
+        int rc = ensure(c, (void **)im.scratch, im.cap, npx * im.px_bytes);
+        if (rc) return rc;
+        im.dev = *im.scratch;
+        if (!F.whole) HIPCHK(c, hipMemcpyAsync(im.dev, im.host, npx * im.px_bytes, hipMemcpyHostToDevice, F.st));
     }
+    for (const FrameImage &im : F.img)
+        if (((uintptr_t)im.dev & (im.align - 1)) != 0) return fail(c, VV_ERR_INVALID, im.misaligned);
+    return VV_OK;
+}
+
+// stage 7: the kernels.  Unshaded frames: the rad pre-pass, the fill beside the rectangle (not composite frames: rad_kernel writes theirs), the march.
+static void launch_kernels(Frame &F)
+{
+    MarchArgs &A = F.A;
+    hipStream_t st = F.st;
+    if (A.phong) {
+        if (A.fill_outside) { A.rad_out = nullptr; launch_rad(A, st); }          // the pixels beside the volume's screen rectangle (rad_kernel writes them; no radii here)
+        launch_build(F.kind, A, st);
+    } else if (A.strips.n_strips > 0) {
+        if (F.W >= 2 && F.H >= 2) launch_rad(A, st);
+        if (F.kind != FRAME_COMPOSITE && F.rect_limits) launch_fill(A, F.fill_rect, st);
+        launch_build(F.kind, A, st);
+    }
+}
+
+// stage 8: host-buffer frames: the images back to the caller, and the wait; device-buffer frames wait only when the call is synchronous
+static int read_back(vv_context *c, const Frame &F, int out_on_device, void *stream)
+{
+    const size_t W = (size_t)F.W, H = (size_t)F.H;
+    if (!out_on_device) {
+        for (const FrameImage &im : F.img) {
+            if (!im.host) continue;
+            const size_t pitch = W * im.px_bytes;
+            if (F.whole) HIPCHK(c, hipMemcpy2DAsync(im.host, pitch, im.dev, pitch, (W - 1) * im.px_bytes, H - 1, hipMemcpyDeviceToHost, F.st));
+            else HIPCHK(c, hipMemcpyAsync(im.host, im.dev, pitch * H, hipMemcpyDeviceToHost, F.st));
+        }
+        HIPCHK(c, hipStreamSynchronize(F.st));
+    } else if (!stream) {
+        HIPCHK(c, hipStreamSynchronize(F.st));
+    }
+    return VV_OK;
+}
+
+// One frame: vv_render (FRAME_COMPOSITE: rgba_out, shading), vv_render_mip (FRAME_MIP: rgba_out and / or index_out), vv_render_iso (FRAME_ISO: any of
+// rgba_out, index_out, hit_out; `level`) and vv_render_projection (FRAME_PROJ: any of rgba_out, index_out, stat_out; `level` holds the vv_proj_mode); the
+// last three never Phong.  All share the stages above; only the kernels (kLaunch's row) and the images differ.
+static int render_frame(vv_context *c, int W, int H, const slice_params *slice, const camera_params *cam,
+                        const shading_params *shading, const vv_ray_source *rays, const vv_render_options *opts,
+                        uint8_t *rgba_out, uint8_t *index_out, float *hit_out, uint32_t *stat_out, FrameKind kind, int level, int out_on_device, void *stream)
+{
+    int rc = check_frame_args(c, W, H, slice, cam, rays);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    Frame F;
+    memset(&F, 0, sizeof F);
+    F.kind = kind; F.W = W; F.H = H; F.st = pick_stream(c, stream);
+    MarchArgs &A = F.A;
+    const FrameParams &P = A.P;
+    hipStream_t st = F.st;
+    if ((rc = frame_params(c, F, slice, cam, rays, opts)) != VV_OK) return rc;
+    if ((rc = view_knowledge(c, F, cam, rays, stream)) != VV_OK) return rc;
+    F.beyond_caches = choose_launch(c, A, cam, rays, shading, F.have_basis, F.density, H, st);
+    F.density = c->last_density;
+    A.gray = c->tf_gray; A.phong = shading->phongShading;
+    tiles_under_rect(c, F, rays);
+    A.tf = c->d_tf; A.fill_tf = kind == FRAME_ISO ? nullptr : A.tf;
+    if ((rc = ensure(c, (void **)&c->d_rad, &c->rad_cap, (size_t)P.nbx * P.nby * sizeof(float))) != VV_OK) return rc;
+    if ((rc = tile_order(c, F, rays)) != VV_OK) return rc;
     A.rad = c->d_rad; A.rad_out = c->d_rad;
     A.counter = c->d_counter;
 
-    const size_t fb = (size_t)W * H * 4, ib = (size_t)W * H, hb = (size_t)W * H * 16, sb = (size_t)W * H * 8;
-    uint8_t *d_out = rgba_out, *d_idx = index_out, *d_hit = (uint8_t *)hit_out, *d_stat = (uint8_t *)stat_out;
-    // Pixels the frame does not write (column W-1, row H-1, rows of other shards) must keep the caller's bytes.  A whole
-    // frame is read back as the (W-1) x (H-1) rectangle it writes; a sharded / row-limited frame goes through a staged
-    // copy of the caller's buffer (rare path).
-    const bool whole = s_count <= 1 && rb == 0 && re == P.nby && W >= 2 && H >= 2;
-    if (!out_on_device && rgba_out) {
-        rc = ensure(c, (void **)&c->d_frame, &c->frame_cap, fb);
-        if (rc) return rc;
-        d_out = c->d_frame;
-        if (!whole) HIPCHK(c, hipMemcpyAsync(d_out, rgba_out, fb, hipMemcpyHostToDevice, st));
-    }
-    if (!out_on_device && index_out) {
-        rc = ensure(c, (void **)&c->d_index, &c->index_cap, ib);
-        if (rc) return rc;
-        d_idx = c->d_index;
-        if (!whole) HIPCHK(c, hipMemcpyAsync(d_idx, index_out, ib, hipMemcpyHostToDevice, st));
-    }
-    if (!out_on_device && hit_out) {
-        rc = ensure(c, (void **)&c->d_hit, &c->hit_cap, hb);
-        if (rc) return rc;
-        d_hit = c->d_hit;
-        if (!whole) HIPCHK(c, hipMemcpyAsync(d_hit, hit_out, hb, hipMemcpyHostToDevice, st));
-    }
-    if (!out_on_device && stat_out) {
-        rc = ensure(c, (void **)&c->d_stat, &c->stat_cap, sb);
-        if (rc) return rc;
-        d_stat = c->d_stat;
-        if (!whole) HIPCHK(c, hipMemcpyAsync(d_stat, stat_out, sb, hipMemcpyHostToDevice, st));
-    }
-    A.pixels = (uint32_t *)d_out; A.index = d_idx; A.hit = (float4 *)d_hit; A.stat = (uint2 *)d_stat; A.proj_mode = proj ? level : 0;
-    if (((uintptr_t)d_out & 3) != 0) return fail(c, VV_ERR_INVALID, "vv_render: output buffer must be 4-byte aligned");
-    if (((uintptr_t)d_hit & 15) != 0) return fail(c, VV_ERR_INVALID, "vv_render_iso: a device hit_out must be 16-byte aligned");      // (iso_kernel writes a record in one store)
-    if (((uintptr_t)d_stat & 7) != 0) return fail(c, VV_ERR_INVALID, "vv_render_projection: a device stat_out must be 8-byte aligned");      // (proj_kernel writes a record in one store)
-    if (iso) {
+    F.whole = P.count <= 1 && P.rb == 0 && P.re == P.nby && W >= 2 && H >= 2;
+    const FrameImage images[4] = {
+        {rgba_out,  4,  &c->d_frame, &c->frame_cap, 4,  "vv_render: output buffer must be 4-byte aligned", nullptr},
+        {index_out, 1,  &c->d_index, &c->index_cap, 1,  "", nullptr},
+        {hit_out,   16, &c->d_hit,   &c->hit_cap,   16, "vv_render_iso: a device hit_out must be 16-byte aligned", nullptr},                  // (iso_kernel writes a record in one store)
+        {stat_out,  8,  &c->d_stat,  &c->stat_cap,  8,  "vv_render_projection: a device stat_out must be 8-byte aligned", nullptr},          // (proj_kernel likewise)
+    };
+    memcpy(F.img, images, sizeof images);
+    if ((rc = stage_images(c, F, out_on_device)) != VV_OK) return rc;
+    A.pixels = (uint32_t *)F.img[0].dev; A.index = F.img[1].dev; A.hit = (float4 *)F.img[2].dev; A.stat = (uint2 *)F.img[3].dev;
+    A.proj_mode = kind == FRAME_PROJ ? level : 0;
+    if (kind == FRAME_ISO) {
         A.iso.level = level;
         const int dims[3] = {c->nx, c->ny, c->nz};
         for (int a = 0; a < 3; ++a) { A.iso.n[a] = (float)dims[a]; A.iso.h[a] = 1.0f / (float)dims[a]; }
@@ -1257,61 +1342,25 @@ static int render_frame(vv_context *c, int W, int H, const slice_params *slice, 
     {
         static const int layout_code[] = {0, 1, 2, 2, 3, 4, 5};        // MarchBuild -> the layout code of vv_debug_last_launch
         const int v[8] = {A.strips.tile_log2w, A.strips.blk_log2w, A.unroll, A.phong ? A.lds_reserve_phong : A.lds_reserve, layout_code[A.build],
-                          have_basis ? 1 : 0, (int)fminf(density * 1000.f, 2e9f), kind != FRAME_COMPOSITE ? (int)kind : (A.phong ? 1 : 0)};
+                          F.have_basis ? 1 : 0, (int)fminf(F.density * 1000.f, 2e9f), kind != FRAME_COMPOSITE ? (int)kind : (A.phong ? 1 : 0)};
         memcpy(c->last_launch, v, sizeof v);
     }
     if (c->time_frames) HIPCHK(c, hipEventRecord(c->ev0, st));
-    if (mip) {
-        if (A.strips.n_strips > 0) {
-            if (W >= 2 && H >= 2) launch_rad(A, st);
-            if (rect_limits) launch_mip_fill(A, mip_rect, st);
-            launch_mip_build(A, st);
-        }
-    } else if (iso) {
-        if (A.strips.n_strips > 0) {
-            if (W >= 2 && H >= 2) launch_rad(A, st);
-            if (rect_limits) launch_iso_fill(A, mip_rect, st);
-            launch_iso_build(A, st);
-        }
-    } else if (proj) {
-        if (A.strips.n_strips > 0) {
-            if (W >= 2 && H >= 2) launch_rad(A, st);
-            if (rect_limits) launch_proj_fill(A, mip_rect, st);
-            launch_proj_build(A, st);
-        }
-    } else if (A.phong) {
-        if (A.fill_outside) { A.rad_out = nullptr; launch_rad(A, st); }          // the pixels beside the volume's screen rectangle (rad_kernel writes them; no radii here)
-        launch_march(A, st);
-    } else if (A.strips.n_strips > 0) {
-        if (W >= 2 && H >= 2) launch_rad(A, st);
-        launch_march(A, st);
-    }
+    launch_kernels(F);
     if (c->time_frames) HIPCHK(c, hipEventRecord(c->ev1, st));
     if (A.instr) HIPCHK(c, hipEventRecord(c->ev_count, st));      // frame timing may be off, and the read-back's null-stream copy does not order behind a non-blocking stream
     HIPCHK(c, hipGetLastError());
     c->timed = c->time_frames;
-    if (!out_on_device) {
-        if (rgba_out) {
-            if (whole) HIPCHK(c, hipMemcpy2DAsync(rgba_out, (size_t)W * 4, d_out, (size_t)W * 4, (size_t)(W - 1) * 4, (size_t)(H - 1), hipMemcpyDeviceToHost, st));
-            else HIPCHK(c, hipMemcpyAsync(rgba_out, d_out, fb, hipMemcpyDeviceToHost, st));
-        }
-        if (index_out) {
-            if (whole) HIPCHK(c, hipMemcpy2DAsync(index_out, (size_t)W, d_idx, (size_t)W, (size_t)(W - 1), (size_t)(H - 1), hipMemcpyDeviceToHost, st));
-            else HIPCHK(c, hipMemcpyAsync(index_out, d_idx, ib, hipMemcpyDeviceToHost, st));
-        }
-        if (hit_out) {
-            if (whole) HIPCHK(c, hipMemcpy2DAsync(hit_out, (size_t)W * 16, d_hit, (size_t)W * 16, (size_t)(W - 1) * 16, (size_t)(H - 1), hipMemcpyDeviceToHost, st));
-            else HIPCHK(c, hipMemcpyAsync(hit_out, d_hit, hb, hipMemcpyDeviceToHost, st));
-        }
-        if (stat_out) {
-            if (whole) HIPCHK(c, hipMemcpy2DAsync(stat_out, (size_t)W * 8, d_stat, (size_t)W * 8, (size_t)(W - 1) * 8, (size_t)(H - 1), hipMemcpyDeviceToHost, st));
-            else HIPCHK(c, hipMemcpyAsync(stat_out, d_stat, sb, hipMemcpyDeviceToHost, st));
-        }
-        HIPCHK(c, hipStreamSynchronize(st));
-    } else if (!stream) {
-        HIPCHK(c, hipStreamSynchronize(st));
-    }
-    return VV_OK;
+    return read_back(c, F, out_on_device, stream);
+}
+
+// the shading of the frame kinds that have none (MIP, isosurface, projection)
+static shading_params unshaded()
+{
+    shading_params s;
+    memset(&s, 0, sizeof s);
+    s.transferPreset = -1; s.phongShading = false;
+    return s;
 }
 
 extern "C" {
@@ -1333,10 +1382,8 @@ int vv_render_mip(vv_context *c, int W, int H, const slice_params *slice, const 
     if (!c) return fail(nullptr, VV_ERR_INVALID, "vv_render_mip: NULL context");
     if (!slice || !cam || !rays) return fail(c, VV_ERR_INVALID, "vv_render_mip: NULL argument");
     if (!rgba_out && !index_out) return fail(c, VV_ERR_INVALID, "vv_render_mip: rgba_out and index_out are both NULL");
-    shading_params unshaded;
-    memset(&unshaded, 0, sizeof unshaded);
-    unshaded.transferPreset = -1; unshaded.phongShading = false;
-    return render_frame(c, W, H, slice, cam, &unshaded, rays, opts, rgba_out, index_out, nullptr, nullptr, FRAME_MIP, 0, out_on_device, stream);
+    const shading_params none = unshaded();
+    return render_frame(c, W, H, slice, cam, &none, rays, opts, rgba_out, index_out, nullptr, nullptr, FRAME_MIP, 0, out_on_device, stream);
 }
 
 // ---- isosurface frames: the first sample at or above a level (no reference counterpart) --------
@@ -1348,10 +1395,8 @@ int vv_render_iso(vv_context *c, int W, int H, const slice_params *slice, const 
     if (!slice || !cam || !rays) return fail(c, VV_ERR_INVALID, "vv_render_iso: NULL argument");
     if (!rgba_out && !index_out && !hit_out) return fail(c, VV_ERR_INVALID, "vv_render_iso: rgba_out, index_out and hit_out are all NULL");
     if (level < 1 || level > 255) return fail(c, VV_ERR_INVALID, "vv_render_iso: level must lie in 1..255");
-    shading_params unshaded;
-    memset(&unshaded, 0, sizeof unshaded);
-    unshaded.transferPreset = -1; unshaded.phongShading = false;
-    return render_frame(c, W, H, slice, cam, &unshaded, rays, opts, rgba_out, index_out, hit_out, nullptr, FRAME_ISO, level, out_on_device, stream);
+    const shading_params none = unshaded();
+    return render_frame(c, W, H, slice, cam, &none, rays, opts, rgba_out, index_out, hit_out, nullptr, FRAME_ISO, level, out_on_device, stream);
 }
 
 // ---- projection frames: maximum / minimum / mean over the samples inside the volume (no reference counterpart) --------
@@ -1364,10 +1409,8 @@ int vv_render_projection(vv_context *c, int W, int H, const slice_params *slice,
     if (mode != VV_PROJ_MAX && mode != VV_PROJ_MIN && mode != VV_PROJ_MEAN) return fail(c, VV_ERR_INVALID, "vv_render_projection: mode must be VV_PROJ_MAX, VV_PROJ_MIN or VV_PROJ_MEAN");
     if (!rgba_out && !index_out && !stat_out) return fail(c, VV_ERR_INVALID, "vv_render_projection: rgba_out, index_out and stat_out are all NULL");
     if (out_on_device && ((uintptr_t)stat_out & 7) != 0) return fail(c, VV_ERR_INVALID, "vv_render_projection: a device stat_out must be 8-byte aligned");
-    shading_params unshaded;
-    memset(&unshaded, 0, sizeof unshaded);
-    unshaded.transferPreset = -1; unshaded.phongShading = false;
-    return render_frame(c, W, H, slice, cam, &unshaded, rays, opts, rgba_out, index_out, nullptr, stat_out, FRAME_PROJ, mode, out_on_device, stream);
+    const shading_params none = unshaded();
+    return render_frame(c, W, H, slice, cam, &none, rays, opts, rgba_out, index_out, nullptr, stat_out, FRAME_PROJ, mode, out_on_device, stream);
 }
 
 int vv_classify_indices(vv_context *c, const uint8_t *index, size_t n, const float tf[1024], uint8_t *rgba_out, int on_device, void *stream)

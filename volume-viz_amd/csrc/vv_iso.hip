@@ -7,8 +7,8 @@
 // images: RGBA, index, and a 16-byte record (x, y, z, ordinal).  Per sample the work behind the trilinear reconstruction is one compare and a few selects.
 //   * iso_kernel        the march: mip_kernel's tile grid, block order, trip structure, fetch and scheduling barrier; a lane with a hit stops contributing and
 //                       a wave leaves both loops as soon as none of its lanes has samples left (one ballot per trip) -- the early exit is what makes the frame cheap;
-//   * iso_fill_kernel   the pixels beside the volume's screen rectangle (no hit: zeros in all three images), which iso_kernel's tiles do not cover.
-// Like vv_mip.hip this file is compiled once per volume layout (vv_layout.h), through the vv_iso_*.hip wrappers; each unit defines launch_iso<kBuild>.
+// The pixels beside the volume's screen rectangle, which iso_kernel's tiles do not cover, are fill_outside_kernel's (vv_mip.hip; no hit: zeros in all three images).
+// Like vv_mip.hip this file is compiled once per volume layout (vv_layout.h); each unit defines launch_frame<FRAME_ISO, kBuild>.
 #include "vv_device.h"
 #include "vv_kernels.h"
 #include "vv_layout.h"
@@ -169,61 +169,18 @@ __global__ __launch_bounds__(256) void iso_kernel(FrameParams P, VolumeView V, I
     if (INSTR) flush_counters(counter, executed, slots);
 }
 
-template <int VOXEL, bool TEX8, bool INSTR>
-static void launch_iso_t(const MarchArgs &a, hipStream_t s)
+static void launch_iso_impl(const MarchArgs &a, hipStream_t s)
 {
     const unsigned nblocks = grid_blocks(a.strips);
     if (!nblocks) return;
-    // Blocks per CU: as launch_mip_t.  iso_kernel has no LDS of its own either, so march_kernel's 4 KB table is added to the reserve: the same
-    // number of resident blocks per CU as the march and MIP frames of the same view.
-    const size_t lds = (size_t)a.lds_reserve + kMipTableBytes;
-    dim3 grid(nblocks);
-    if (a.unroll == 3)
-        hipLaunchKernelGGL((iso_kernel<VOXEL, TEX8, INSTR, 3>), grid, dim3(256), lds, s,
+    for_variant(a, [&](auto VOXEL, auto TEX8, auto INSTR, auto U) {
+        hipLaunchKernelGGL((iso_kernel<VOXEL(), TEX8(), INSTR(), U()>), dim3(nblocks), dim3(256), reducer_lds(a), s,
                            a.P, a.V, a.iso, a.tf, a.rad, a.pixels, a.index, a.hit, a.counter, a.I, a.strips);
-    else
-        hipLaunchKernelGGL((iso_kernel<VOXEL, TEX8, INSTR, 2>), grid, dim3(256), lds, s,
-                           a.P, a.V, a.iso, a.tf, a.rad, a.pixels, a.index, a.hit, a.counter, a.I, a.strips);
+    });
 }
-
-static void launch_iso_impl(const MarchArgs &a, hipStream_t s)
-{
-    const bool f32 = a.V_type == VV_VOXEL_F32;
-    if (a.instr) {
-        if (f32) { if (a.tex8) launch_iso_t<VV_VOXEL_F32, true, true>(a, s); else launch_iso_t<VV_VOXEL_F32, false, true>(a, s); }
-        else     { if (a.tex8) launch_iso_t<VV_VOXEL_U8,  true, true>(a, s); else launch_iso_t<VV_VOXEL_U8,  false, true>(a, s); }
-    } else {
-        if (f32) { if (a.tex8) launch_iso_t<VV_VOXEL_F32, true, false>(a, s); else launch_iso_t<VV_VOXEL_F32, false, false>(a, s); }
-        else     { if (a.tex8) launch_iso_t<VV_VOXEL_U8,  true, false>(a, s); else launch_iso_t<VV_VOXEL_U8,  false, false>(a, s); }
-    }
-}
-
-#ifdef VV_BUILD_LINEAR       // (once: the build for the linear layout)
-// The owned pixels outside the rectangle iso_kernel's tiles cover: their rays miss the volume (vv_render: screen_rect), so there is no hit.
-// One thread per pixel of the frame; threads inside the rectangle, in column W-1 / row H-1 or in another shard's rows leave at once.
-__global__ __launch_bounds__(256) void iso_fill_kernel(FrameParams P, PixelRect R, uint32_t *__restrict__ pixels, uint8_t *__restrict__ index,
-                                                       float4 *__restrict__ hit)
-{
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x > P.W - 2 || y > P.H - 2 || !row_owned(P, y)) return;
-    if (x >= R.x0 && x < R.x1 && y >= R.y0 && y < R.y1) return;
-    const size_t p = (size_t)y * P.W + x;
-    if (index) index[p] = 0;
-    if (hit) hit[p] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (pixels) pixels[p] = 0u;
-}
-#endif
 
 } // namespace VV_BIG_NS
 
-template <> void launch_iso<kBuild>(const MarchArgs &a, hipStream_t s) { VV_BIG_NS::launch_iso_impl(a, s); }
-#ifdef VV_BUILD_LINEAR
-void launch_iso_fill(const MarchArgs &a, const PixelRect &rect, hipStream_t s)
-{
-    if (a.P.W < 2 || a.P.H < 2) return;
-    dim3 grid((unsigned)((a.P.W - 1 + 63) / 64), (unsigned)((a.P.H - 1 + 3) / 4));
-    hipLaunchKernelGGL(small::iso_fill_kernel, grid, dim3(256), 0, s, a.P, rect, a.pixels, a.index, a.hit);
-}
-#endif
+template <> void launch_frame<FRAME_ISO, kBuild>(const MarchArgs &a, hipStream_t s) { VV_BIG_NS::launch_iso_impl(a, s); }
 
 } // namespace vv

@@ -2,7 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "vv_device.h"
-#include "vv_tiles.h"       // StripMap and the tile grid of march_kernel / mip_kernel
+#include "vv_tiles.h"       // StripMap and the tile grid of the march kernels
 
 namespace vv {
 
@@ -16,13 +16,25 @@ struct SlabMap  { int r0, band, band_stride, n_regular;
                   // volume's screen rectangle, or all of them (gx0 = 0, wg = nbx, gs0 = 0, gs1 = n_regular)
                   int gx0, wg, gs0, gs1; };
 
-// the build of the march kernels a frame runs: vv_raymarch.hip, vv_mip.hip, vv_iso.hip and vv_proj.hip are compiled once for each (vv_layout.h: kBuild)
-// (the list generates the enum and the launcher tables below, so their orders cannot part: MB_LINEAR_BIG volumes above 4 GiB, MB_BRICKED on VolumeView::bricks,
+// the build of the march kernels a frame runs: vv_raymarch.hip, vv_mip.hip, vv_iso.hip and vv_proj.hip are each compiled once per build (vv_layout.h: kBuild)
+// (the list generates the enum and the launcher table below, so their orders cannot part: MB_LINEAR_BIG volumes above 4 GiB, MB_BRICKED on VolumeView::bricks,
 //  MB_BRICKED_CACHED the same for volumes up to 1 GiB, MB_ZPAIR on VolumeView::zpair, MB_ZFAST on VolumeView::zfast, MB_XPAIR on the x-pair copy, handed over in VolumeView::zpair)
-#define VV_FOR_EACH_BUILD(X) X(MB_LINEAR) X(MB_LINEAR_BIG) X(MB_BRICKED) X(MB_BRICKED_CACHED) X(MB_ZPAIR) X(MB_ZFAST) X(MB_XPAIR)
-#define VV_X(B) B,
-enum MarchBuild : uint8_t { VV_FOR_EACH_BUILD(VV_X) MB_COUNT };
+#define VV_FOR_EACH_BUILD(X, K) X(K, MB_LINEAR) X(K, MB_LINEAR_BIG) X(K, MB_BRICKED) X(K, MB_BRICKED_CACHED) X(K, MB_ZPAIR) X(K, MB_ZFAST) X(K, MB_XPAIR)
+#define VV_X(K, B) B,
+enum MarchBuild : uint8_t { VV_FOR_EACH_BUILD(VV_X, ) MB_COUNT };
 #undef VV_X
+
+// what a frame keeps of its samples: their composite (vv_render), their maximum (vv_render_mip), the first at or above a level (vv_render_iso) or the
+// maximum / minimum / mean of those inside the volume (vv_render_projection).  One kernel file per kind (vv_raymarch.hip, vv_mip.hip, vv_iso.hip, vv_proj.hip).
+// The values are vv_debug_last_launch's kernel family of the three unshaded-only kinds (composite frames report 0 or 1 with the shading); the list
+// generates the rows of the launcher table, which frame_row() finds.
+enum FrameKind { FRAME_COMPOSITE = 0, FRAME_MIP = 2, FRAME_ISO = 3, FRAME_PROJ = 4 };
+#define VV_FOR_EACH_KIND(X) X(FRAME_COMPOSITE) X(FRAME_MIP) X(FRAME_ISO) X(FRAME_PROJ)
+#define VV_X(K) K,
+constexpr FrameKind kFrameKinds[] = { VV_FOR_EACH_KIND(VV_X) };
+#undef VV_X
+constexpr int kFrameKindCount = sizeof(kFrameKinds) / sizeof(kFrameKinds[0]);
+constexpr int frame_row(FrameKind k) { int r = 0; while (r < kFrameKindCount - 1 && kFrameKinds[r] != k) ++r; return r; }
 
 // what an isosurface frame knows beyond FrameParams / VolumeView (iso_kernel): the level, and the gradient's offsets h[a] = 1 / n_a in texture
 // coordinates with n[a] = (float)n_a, the volume's dimensions
@@ -45,6 +57,7 @@ struct MarchArgs {
     const float4 *tf;           // device, 256 entries
     const float *rad;           // device, nbx*nby (read by march_kernel)
     float *rad_out;             // same buffer (written by rad_kernel)
+    const float4 *fill_tf;      // fill_outside_kernel: the table whose entry 0 is the RGBA of the pixels beside the rectangle, or null for RGBA 0 (isosurface frames)
     uint32_t *pixels;           // device RGBA8 frame (MIP frames: may be null)
     uint8_t *index;             // MIP frames: device image of the per-pixel maxima, W * H bytes, or null (isosurface frames: of the hits' indices)
     float4 *hit;                // isosurface frames: device image of the hit records (x, y, z, ordinal), W * H * 16 bytes, or null
@@ -55,37 +68,26 @@ struct MarchArgs {
     InstrArgs I;                // bitmaps of an instrumented frame (vv_render_options::touched_bricks / touched_lines)
 };
 
-// The march, MIP, isosurface and projection launchers, one explicit specialisation per build, each defined by the unit compiled for that build;
-// kLaunchRaymarch[b] / kLaunchMip[b] / kLaunchIso[b] / kLaunchProj[b] is the launcher of MarchBuild b.  rad_kernel (the pre-pass of all four),
-// mip_fill_kernel, mip_classify_kernel, iso_fill_kernel and proj_fill_kernel live in the linear build's units.
-template <MarchBuild B> void launch_raymarch(const MarchArgs &a, hipStream_t s);
-template <MarchBuild B> void launch_mip(const MarchArgs &a, hipStream_t s);
-template <MarchBuild B> void launch_iso(const MarchArgs &a, hipStream_t s);
-template <MarchBuild B> void launch_proj(const MarchArgs &a, hipStream_t s);
-#define VV_X(B) template <> void launch_raymarch<B>(const MarchArgs &, hipStream_t); template <> void launch_mip<B>(const MarchArgs &, hipStream_t); \
-                template <> void launch_iso<B>(const MarchArgs &, hipStream_t); template <> void launch_proj<B>(const MarchArgs &, hipStream_t);
-VV_FOR_EACH_BUILD(VV_X)
+// The launchers: one explicit specialisation per frame kind and build, each defined by the kind's kernel file compiled for that build;
+// kLaunch[frame_row(k)][b] is the launcher of FrameKind k and MarchBuild b.  The kernels that exist once live in the linear build's units: rad_kernel
+// (the pre-pass of all four kinds) in vv_raymarch.hip, fill_outside_kernel and mip_classify_kernel in vv_mip.hip.
+template <int KIND, MarchBuild B> void launch_frame(const MarchArgs &a, hipStream_t s);
+#define VV_X(K, B) template <> void launch_frame<K, B>(const MarchArgs &, hipStream_t);
+#define VV_ROW(K) VV_FOR_EACH_BUILD(VV_X, K)
+VV_FOR_EACH_KIND(VV_ROW)
+#undef VV_ROW
 #undef VV_X
 using MarchLauncher = void (*)(const MarchArgs &, hipStream_t);
-#define VV_X(B) launch_raymarch<B>,
-constexpr MarchLauncher kLaunchRaymarch[] = { VV_FOR_EACH_BUILD(VV_X) };
+#define VV_X(K, B) launch_frame<K, B>,
+#define VV_ROW(K) { VV_FOR_EACH_BUILD(VV_X, K) },
+constexpr MarchLauncher kLaunch[][MB_COUNT] = { VV_FOR_EACH_KIND(VV_ROW) };
+#undef VV_ROW
 #undef VV_X
-#define VV_X(B) launch_mip<B>,
-constexpr MarchLauncher kLaunchMip[] = { VV_FOR_EACH_BUILD(VV_X) };
-#undef VV_X
-#define VV_X(B) launch_iso<B>,
-constexpr MarchLauncher kLaunchIso[] = { VV_FOR_EACH_BUILD(VV_X) };
-#undef VV_X
-#define VV_X(B) launch_proj<B>,
-constexpr MarchLauncher kLaunchProj[] = { VV_FOR_EACH_BUILD(VV_X) };
-#undef VV_X
-static_assert(sizeof(kLaunchRaymarch) / sizeof(MarchLauncher) == MB_COUNT && sizeof(kLaunchMip) / sizeof(MarchLauncher) == MB_COUNT &&
-              sizeof(kLaunchIso) / sizeof(MarchLauncher) == MB_COUNT && sizeof(kLaunchProj) / sizeof(MarchLauncher) == MB_COUNT, "one launcher per build");
+static_assert(sizeof(kLaunch) == sizeof(MarchLauncher) * kFrameKindCount * MB_COUNT, "one launcher per frame kind and build");
 void launch_rad(const MarchArgs &a, hipStream_t s);
-constexpr int kMipTableBytes = 4096;      // march_kernel's LDS table, which mip_kernel does not have: added to lds_reserve so that the blocks per CU stay what the policy measured
-void launch_mip_fill(const MarchArgs &a, const PixelRect &rect, hipStream_t s);      // M = 0 for the owned pixels outside `rect` (both images)
-void launch_iso_fill(const MarchArgs &a, const PixelRect &rect, hipStream_t s);      // no hit for the owned pixels outside `rect`: zeros in all three images
-void launch_proj_fill(const MarchArgs &a, const PixelRect &rect, hipStream_t s);     // n = 0 for the owned pixels outside `rect`: v = 0, tf[0] and {0, 0}
+constexpr int kMipTableBytes = 4096;      // march_kernel's LDS table, which the reducer kernels (mip, iso, proj) do not have (vv_layout.h: reducer_lds)
+// the owned pixels outside `rect` of a MIP, isosurface or projection frame, whose rays miss the volume: index 0, RGBA of MarchArgs::fill_tf, zero records
+void launch_fill(const MarchArgs &a, const PixelRect &rect, hipStream_t s);
 void launch_mip_classify(const uint8_t *index, size_t n, const float4 *tf, uint32_t *pixels, hipStream_t s);   // pixels[i] = RGBA8 of tf[index[i]]
 void launch_build_xpair(int vtype, const void *zfast, uint32_t zf_row_bytes, uint64_t zf_slice_bytes, void *xpair, int nx, int ny, int nz, hipStream_t s);
 void launch_build_zfast(int vtype, const void *vol, uint32_t row_pitch, uint64_t slice_pitch, void *out, uint32_t zf_row_bytes, uint64_t zf_slice_bytes, int nx, int ny, int nz, hipStream_t s);

@@ -1,11 +1,27 @@
 // vv_layout.h -- the volume layout a march translation unit is compiled for (internal; included once per unit, after vv_device.h).
 //
-// vv_raymarch.hip and vv_mip.hip are each compiled seven times (their *_big / *_brick / *_brick_cached / *_zpair / *_zfast / *_xpair
-// wrappers define VV_BIG_VOLUME / VV_BRICKED (+ VV_BRICKED_CACHED) / VV_ZPAIR / VV_ZFAST / VV_ZPAIR + VV_XPAIR).  This header turns those
-// macros -- here and nowhere else -- into the unit's namespace (VV_BIG_NS), its build (kBuild: the launcher specialisation it defines), its layout constant
-// (kLayout; two builds share the bricked layout), its corner registers and fetch, and the instrumentation of instrumented frames.  The unit for the
-// linear layout, which also holds the kernels that exist once (rad_kernel, mip_fill_kernel, mip_classify_kernel), sees VV_BUILD_LINEAR.
+// The four kernel files (vv_raymarch.hip, vv_mip.hip, vv_iso.hip, vv_proj.hip) are each compiled seven times: as they are, and with the layout macros
+// the Makefile's LAYOUT_FLAGS table gives (VV_BIG_VOLUME / VV_BRICKED (+ VV_BRICKED_CACHED) / VV_ZPAIR / VV_ZFAST / VV_ZPAIR + VV_XPAIR).  This header turns
+// those macros -- here and nowhere else -- into the unit's namespace (VV_BIG_NS), its build (kBuild: the launcher specialisation it defines), its layout
+// constant (kLayout; two builds share the bricked layout), its corner registers and fetch, the instrumentation of instrumented frames, and the host-side
+// choice of a kernel instantiation (for_variant).  The unit for the linear layout, which also holds the kernels that exist once (rad_kernel,
+// fill_outside_kernel, mip_classify_kernel), sees VV_BUILD_LINEAR.
+//
+// The builds, in the order of the chain below:
+//   xpair         the z-pair build on the x-pair copy (the z-pair copy with x and z in each other's roles: records {v(x,y,z), v(x+1,y,z)}, z fastest; handed
+//                 over in VolumeView::zpair): side views of the volumes whose front views take the z-pair copy, two gathers per sample instead of four;
+//   zpair         the z-pair copy (VolumeView::zpair: records {v(x,y,z), v(x,y,z+1)}): views along the memory axis, two 16-byte gathers per sample
+//                 instead of four 8-byte ones;
+//   brick_cached  the bricked build once more for volumes that live in the caches (up to 1 GiB): the same kernels in namespace brickc, compiled without
+//                 the SLP vectoriser (Makefile: NOSLP_LAYOUTS);
+//   brick         the bricked copy (VolumeView::bricks: 4x4x4-voxel bricks with an x halo): views that are not aligned with the memory axis, where the
+//                 linear layout costs one cache line per lane and gather;
+//   zfast         the z-fastest copy (VolumeView::zfast): views whose screen x runs along the volume's z axis (side views) -- the lanes of a 32 x 2 wave
+//                 tile read consecutive z, the rays march along x;
+//   big           the linear layout above 4 GiB (64-bit slice base per sample; tex3d_raw in vv_device.h);
+//   (none)        the linear layout up to 4 GiB.
 #pragma once
+#include <type_traits>
 #include "vv_device.h"
 #include "vv_kernels.h"
 
@@ -124,6 +140,29 @@ __device__ __forceinline__ void flush_counters(unsigned long long *__restrict__ 
     if (kLayout == LAYOUT_BRICKED && first && executed) atomicAdd(counter + 2, 1ull);
     if (kLayout == LAYOUT_ZPAIR && first && executed) atomicAdd(counter + 3, 1ull);
 }
+
+// Host: the kernel instantiation of a frame.  with_bool hands a run-time bool to the generic lambda f as std::true_type / std::false_type; for_sampler
+// hands it a.V_type, a.tex8 and a.instr as the integral constants VOXEL, TEX8 and INSTR; for_variant adds a.unroll as U (2 or 3), so that f launches
+// kernel<VOXEL(), TEX8(), INSTR(), U()>.  (The nesting is the order in which the compiler emits the instantiations into the code object: instrumented
+// first, then f32 before u8, the 8-bit filter before the exact one, U = 3 before 2 -- the order of the hand-written ladders these replace.)
+template <int N> using int_c = std::integral_constant<int, N>;
+template <class F> static void with_bool(bool b, F &&f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+template <class F> static void for_sampler(const MarchArgs &a, F &&f)
+{
+    with_bool(a.instr, [&](auto instr) { with_bool(a.V_type == VV_VOXEL_F32, [&](auto f32) { with_bool(a.tex8, [&](auto tex8) {
+        f(int_c<decltype(f32)::value ? VV_VOXEL_F32 : VV_VOXEL_U8>{}, tex8, instr);
+    }); }); });
+}
+template <class F> static void for_unroll(const MarchArgs &a, F &&f) { if (a.unroll == 3) f(int_c<3>{}); else f(int_c<2>{}); }
+template <class F> static void for_variant(const MarchArgs &a, F &&f)
+{
+    for_sampler(a, [&](auto VOXEL, auto TEX8, auto INSTR) { for_unroll(a, [&](auto U) { f(VOXEL, TEX8, INSTR, U); }); });
+}
+
+// Dynamic LDS of a reducer kernel's launch (mip_kernel, iso_kernel, proj_kernel).  Blocks per CU: the launch policy's lds_reserve values were measured on
+// march_kernel, whose blocks hold a 4 KB table in LDS besides the reserve.  The reducers have no LDS of their own, so the table's 4 KB are added to the
+// reserve here: the same LDS per block, the same number of resident blocks per CU (and waves on its L1) as the march frame of the same view.
+static inline size_t reducer_lds(const MarchArgs &a) { return (size_t)a.lds_reserve + kMipTableBytes; }
 
 } // namespace VV_BIG_NS
 } // namespace vv

@@ -6,9 +6,11 @@
 // blend, no early-termination state: the ray state and the U samples in flight live in registers, the per-sample work behind the
 // trilinear reconstruction is one v_max_u32, and the transfer table is read once per pixel, in the epilogue.
 //   * mip_kernel           the march: trip structure of march_kernel (vv_raymarch.hip), on the tile grid both share (vv_tiles.h: block order, wave tiles, launch size);
-//   * mip_fill_kernel      the pixels beside the volume's screen rectangle (M = 0), which mip_kernel's tiles do not cover;
+//   * fill_outside_kernel  the pixels beside the volume's screen rectangle, which the tiles of mip_kernel, iso_kernel and proj_kernel do not cover: no
+//                          sample, so index 0, no hit, n = 0 (one kernel for the three kinds; linear build only);
 //   * mip_classify_kernel  index image -> RGBA through a table (vv_classify_indices).
-// Like vv_raymarch.hip this file is compiled once per volume layout (vv_layout.h), through the vv_mip_*.hip wrappers; each unit defines launch_mip<kBuild>.
+// Like vv_raymarch.hip this file is compiled once per volume layout (vv_layout.h; the Makefile passes the layout's macros); each unit defines
+// launch_frame<FRAME_MIP, kBuild>.
 #include "vv_device.h"
 #include "vv_kernels.h"
 #include "vv_layout.h"
@@ -114,48 +116,32 @@ __global__ __launch_bounds__(256) void mip_kernel(FrameParams P, VolumeView V,
     if (INSTR) flush_counters(counter, executed, slots);
 }
 
-template <int VOXEL, bool TEX8, bool INSTR>
-static void launch_mip_t(const MarchArgs &a, hipStream_t s)
+static void launch_mip_impl(const MarchArgs &a, hipStream_t s)
 {
     const unsigned nblocks = grid_blocks(a.strips);
     if (!nblocks) return;
-    // Blocks per CU: the launch policy's lds_reserve values were measured on march_kernel, whose blocks hold a 4 KB table in LDS besides
-    // the reserve.  mip_kernel has no LDS of its own, so the table's 4 KB are added to the reserve here: the same LDS per block, the same
-    // number of resident blocks per CU (and waves on its L1) as the march frame of the same view.
-    const size_t lds = (size_t)a.lds_reserve + kMipTableBytes;
-    dim3 grid(nblocks);
-    if (a.unroll == 3)
-        hipLaunchKernelGGL((mip_kernel<VOXEL, TEX8, INSTR, 3>), grid, dim3(256), lds, s,
+    for_variant(a, [&](auto VOXEL, auto TEX8, auto INSTR, auto U) {
+        hipLaunchKernelGGL((mip_kernel<VOXEL(), TEX8(), INSTR(), U()>), dim3(nblocks), dim3(256), reducer_lds(a), s,
                            a.P, a.V, a.tf, a.rad, a.pixels, a.index, a.counter, a.I, a.strips);
-    else
-        hipLaunchKernelGGL((mip_kernel<VOXEL, TEX8, INSTR, 2>), grid, dim3(256), lds, s,
-                           a.P, a.V, a.tf, a.rad, a.pixels, a.index, a.counter, a.I, a.strips);
-}
-
-static void launch_mip_impl(const MarchArgs &a, hipStream_t s)
-{
-    const bool f32 = a.V_type == VV_VOXEL_F32;
-    if (a.instr) {
-        if (f32) { if (a.tex8) launch_mip_t<VV_VOXEL_F32, true, true>(a, s); else launch_mip_t<VV_VOXEL_F32, false, true>(a, s); }
-        else     { if (a.tex8) launch_mip_t<VV_VOXEL_U8,  true, true>(a, s); else launch_mip_t<VV_VOXEL_U8,  false, true>(a, s); }
-    } else {
-        if (f32) { if (a.tex8) launch_mip_t<VV_VOXEL_F32, true, false>(a, s); else launch_mip_t<VV_VOXEL_F32, false, false>(a, s); }
-        else     { if (a.tex8) launch_mip_t<VV_VOXEL_U8,  true, false>(a, s); else launch_mip_t<VV_VOXEL_U8,  false, false>(a, s); }
-    }
+    });
 }
 
 #ifdef VV_BUILD_LINEAR       // (once: the build for the linear layout)
-// The owned pixels outside the rectangle mip_kernel's tiles cover: their rays miss the volume (vv_render: screen_rect), so M = 0.
+// The owned pixels outside the rectangle that the tiles of a MIP, isosurface or projection frame cover: their rays miss the volume (vv_render: screen_rect),
+// so they execute no sample -- index 0, the RGBA of the table's entry 0 (MIP and projection frames; `tf` null: 0, the isosurface frame's "no hit") and
+// all-zero records, each written in one store: `stat` the projection frame's {0, 0}, `hit` the isosurface frame's (0, 0, 0, 0).  Every image may be null.
 // One thread per pixel of the frame; threads inside the rectangle, in column W-1 / row H-1 or in another shard's rows leave at once.
-__global__ __launch_bounds__(256) void mip_fill_kernel(FrameParams P, PixelRect R, const float4 *__restrict__ tf,
-                                                       uint32_t *__restrict__ pixels, uint8_t *__restrict__ index)
+__global__ __launch_bounds__(256) void fill_outside_kernel(FrameParams P, PixelRect R, const float4 *__restrict__ tf, uint32_t *__restrict__ pixels,
+                                                           uint8_t *__restrict__ index, uint2 *__restrict__ stat, float4 *__restrict__ hit)
 {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x > P.W - 2 || y > P.H - 2 || !row_owned(P, y)) return;
     if (x >= R.x0 && x < R.x1 && y >= R.y0 && y < R.y1) return;
     const size_t p = (size_t)y * P.W + x;
     if (index) index[p] = 0;
-    if (pixels) pixels[p] = classify_entry(tf[0]);
+    if (stat) stat[p] = make_uint2(0u, 0u);
+    if (hit) hit[p] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (pixels) pixels[p] = tf ? classify_entry(tf[0]) : 0u;
 }
 
 __global__ __launch_bounds__(256) void mip_classify_kernel(const uint8_t *__restrict__ index, size_t n, const float4 *__restrict__ tf,
@@ -168,13 +154,13 @@ __global__ __launch_bounds__(256) void mip_classify_kernel(const uint8_t *__rest
 
 } // namespace VV_BIG_NS
 
-template <> void launch_mip<kBuild>(const MarchArgs &a, hipStream_t s) { VV_BIG_NS::launch_mip_impl(a, s); }
+template <> void launch_frame<FRAME_MIP, kBuild>(const MarchArgs &a, hipStream_t s) { VV_BIG_NS::launch_mip_impl(a, s); }
 #ifdef VV_BUILD_LINEAR
-void launch_mip_fill(const MarchArgs &a, const PixelRect &rect, hipStream_t s)
+void launch_fill(const MarchArgs &a, const PixelRect &rect, hipStream_t s)
 {
     if (a.P.W < 2 || a.P.H < 2) return;
     dim3 grid((unsigned)((a.P.W - 1 + 63) / 64), (unsigned)((a.P.H - 1 + 3) / 4));
-    hipLaunchKernelGGL(small::mip_fill_kernel, grid, dim3(256), 0, s, a.P, rect, a.tf, a.pixels, a.index);
+    hipLaunchKernelGGL(small::fill_outside_kernel, grid, dim3(256), 0, s, a.P, rect, a.fill_tf, a.pixels, a.index, a.stat, a.hit);
 }
 void launch_mip_classify(const uint8_t *index, size_t n, const float4 *tf, uint32_t *pixels, hipStream_t s)
 {

@@ -13,9 +13,9 @@
 //   * proj_kernel       the march: mip_kernel's tile grid, block order, trip structure, fetch and scheduling barrier.  The ray state, the U samples in
 //                       flight and the two or three words of reduction state live in registers; no LDS; the table is read once per pixel, in the epilogue.
 //                       Per sample behind the reconstruction: the bounds test (made once: classify_raw, not classify_index), and one compare and two selects
-//                       (MAX / MIN) or one predicated add (MEAN), plus the count of counted samples;
-//   * proj_fill_kernel  the pixels beside the volume's screen rectangle (n = 0), which proj_kernel's tiles do not cover.
-// Like vv_mip.hip this file is compiled once per volume layout (vv_layout.h), through the vv_proj_*.hip wrappers; each unit defines launch_proj<kBuild>.
+//                       (MAX / MIN) or one predicated add (MEAN), plus the count of counted samples.
+// The pixels beside the volume's screen rectangle, which proj_kernel's tiles do not cover, are fill_outside_kernel's (vv_mip.hip; n = 0: v = 0, tf[0], {0, 0}).
+// Like vv_mip.hip this file is compiled once per volume layout (vv_layout.h); each unit defines launch_frame<FRAME_PROJ, kBuild>.
 #include "vv_device.h"
 #include "vv_kernels.h"
 #include "vv_layout.h"
@@ -143,69 +143,27 @@ __global__ __launch_bounds__(256) void proj_kernel(FrameParams P, VolumeView V,
     if (INSTR) flush_counters(counter, executed, slots);
 }
 
-template <int VOXEL, bool TEX8, bool INSTR, int MODE>
-static void launch_proj_m(const MarchArgs &a, hipStream_t s)
+static void launch_proj_impl(const MarchArgs &a, hipStream_t s)
 {
     const unsigned nblocks = grid_blocks(a.strips);
     if (!nblocks) return;
-    // Blocks per CU: as launch_mip_t.  proj_kernel has no LDS of its own either, so march_kernel's 4 KB table is added to the reserve: the same
-    // number of resident blocks per CU as the march and MIP frames of the same view.
-    const size_t lds = (size_t)a.lds_reserve + kMipTableBytes;
-    dim3 grid(nblocks);
-    if (a.unroll == 3)
-        hipLaunchKernelGGL((proj_kernel<VOXEL, TEX8, INSTR, 3, MODE>), grid, dim3(256), lds, s,
-                           a.P, a.V, a.tf, a.rad, a.pixels, a.index, a.stat, a.counter, a.I, a.strips);
-    else
-        hipLaunchKernelGGL((proj_kernel<VOXEL, TEX8, INSTR, 2, MODE>), grid, dim3(256), lds, s,
-                           a.P, a.V, a.tf, a.rad, a.pixels, a.index, a.stat, a.counter, a.I, a.strips);
+    for_sampler(a, [&](auto VOXEL, auto TEX8, auto INSTR) {
+        auto launch = [&](auto MODE) {
+            for_unroll(a, [&](auto U) {
+                hipLaunchKernelGGL((proj_kernel<VOXEL(), TEX8(), INSTR(), U(), MODE()>), dim3(nblocks), dim3(256), reducer_lds(a), s,
+                                   a.P, a.V, a.tf, a.rad, a.pixels, a.index, a.stat, a.counter, a.I, a.strips);
+            });
+        };
+        switch (a.proj_mode) {                  // (the mode sits between the sampler and U: see for_sampler on the order of the instantiations)
+        case VV_PROJ_MIN:  launch(int_c<VV_PROJ_MIN>{}); break;
+        case VV_PROJ_MEAN: launch(int_c<VV_PROJ_MEAN>{}); break;
+        default:           launch(int_c<VV_PROJ_MAX>{}); break;
+        }
+    });
 }
-
-template <int VOXEL, bool TEX8, bool INSTR>
-static void launch_proj_t(const MarchArgs &a, hipStream_t s)
-{
-    if (a.proj_mode == VV_PROJ_MIN) launch_proj_m<VOXEL, TEX8, INSTR, VV_PROJ_MIN>(a, s);
-    else if (a.proj_mode == VV_PROJ_MEAN) launch_proj_m<VOXEL, TEX8, INSTR, VV_PROJ_MEAN>(a, s);
-    else launch_proj_m<VOXEL, TEX8, INSTR, VV_PROJ_MAX>(a, s);
-}
-
-static void launch_proj_impl(const MarchArgs &a, hipStream_t s)
-{
-    const bool f32 = a.V_type == VV_VOXEL_F32;
-    if (a.instr) {
-        if (f32) { if (a.tex8) launch_proj_t<VV_VOXEL_F32, true, true>(a, s); else launch_proj_t<VV_VOXEL_F32, false, true>(a, s); }
-        else     { if (a.tex8) launch_proj_t<VV_VOXEL_U8,  true, true>(a, s); else launch_proj_t<VV_VOXEL_U8,  false, true>(a, s); }
-    } else {
-        if (f32) { if (a.tex8) launch_proj_t<VV_VOXEL_F32, true, false>(a, s); else launch_proj_t<VV_VOXEL_F32, false, false>(a, s); }
-        else     { if (a.tex8) launch_proj_t<VV_VOXEL_U8,  true, false>(a, s); else launch_proj_t<VV_VOXEL_U8,  false, false>(a, s); }
-    }
-}
-
-#ifdef VV_BUILD_LINEAR       // (once: the build for the linear layout)
-// The owned pixels outside the rectangle proj_kernel's tiles cover: their rays miss the volume (vv_render: screen_rect), so n = 0 in every mode.
-// One thread per pixel of the frame; threads inside the rectangle, in column W-1 / row H-1 or in another shard's rows leave at once.
-__global__ __launch_bounds__(256) void proj_fill_kernel(FrameParams P, PixelRect R, const float4 *__restrict__ tf,
-                                                        uint32_t *__restrict__ pixels, uint8_t *__restrict__ index, uint2 *__restrict__ stat)
-{
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x > P.W - 2 || y > P.H - 2 || !row_owned(P, y)) return;
-    if (x >= R.x0 && x < R.x1 && y >= R.y0 && y < R.y1) return;
-    const size_t p = (size_t)y * P.W + x;
-    if (index) index[p] = 0;
-    if (stat) stat[p] = make_uint2(0u, 0u);
-    if (pixels) { const float4 e = tf[0]; pixels[p] = pack_rgba(e.x, e.y, e.z, e.w); }
-}
-#endif
 
 } // namespace VV_BIG_NS
 
-template <> void launch_proj<kBuild>(const MarchArgs &a, hipStream_t s) { VV_BIG_NS::launch_proj_impl(a, s); }
-#ifdef VV_BUILD_LINEAR
-void launch_proj_fill(const MarchArgs &a, const PixelRect &rect, hipStream_t s)
-{
-    if (a.P.W < 2 || a.P.H < 2) return;
-    dim3 grid((unsigned)((a.P.W - 1 + 63) / 64), (unsigned)((a.P.H - 1 + 3) / 4));
-    hipLaunchKernelGGL(small::proj_fill_kernel, grid, dim3(256), 0, s, a.P, rect, a.tf, a.pixels, a.index, a.stat);
-}
-#endif
+template <> void launch_frame<FRAME_PROJ, kBuild>(const MarchArgs &a, hipStream_t s) { VV_BIG_NS::launch_proj_impl(a, s); }
 
 } // namespace vv

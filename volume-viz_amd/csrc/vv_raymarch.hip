@@ -15,13 +15,8 @@
 #include "vv_device.h"
 #include "vv_kernels.h"
 
-// This file is compiled seven times: as is (linear volume up to 4 GiB), through vv_raymarch_big.hip
-// with VV_BIG_VOLUME (linear, 64-bit slice addressing), through vv_raymarch_brick.hip with
-// VV_BRICKED (volume sampled from the bricked copy), through vv_raymarch_brick_cached.hip (the same for volumes
-// that live in the caches), through vv_raymarch_zpair.hip with VV_ZPAIR (volume sampled from the z-pair copy) and through
-// vv_raymarch_zfast.hip with VV_ZFAST (volume sampled from the z-fastest copy: side views) and through vv_raymarch_xpair.hip with
-// VV_ZPAIR + VV_XPAIR (the z-pair build on the x-pair copy: side views of small / u8 volumes),
-// so that each path pays only for itself (vv_layout.h names the build; each unit defines launch_raymarch<kBuild>).  The builds for cache-resident volumes (this file as is, z-pair, brick_cached)
+// This file is compiled seven times, once per volume layout (vv_layout.h lists the builds and what each is for; the Makefile passes the layout's macros),
+// so that each path pays only for itself (each unit defines launch_frame<FRAME_COMPOSITE, kBuild>).  The builds for cache-resident volumes (this file as is, z-pair, brick_cached)
 // are compiled with -fno-slp-vectorize: the packed-f32 code the SLP vectoriser makes of the lerps costs a v_mov per
 // operand pair, which VALU-bound frames pay for (C2 -6 %, C1 -4 %, 512^3 -4 %, C2 rotated -6.5 %, Phong -3 ... -6 %),
 // while the builds for volumes beyond the caches are 0.5-3 % (rotated + Phong 9 %) faster with it (Makefile).
@@ -718,7 +713,7 @@ static void launch_raymarch_impl(const MarchArgs &a, hipStream_t s)
 
 } // namespace VV_BIG_NS
 
-template <> void launch_raymarch<kBuild>(const MarchArgs &a, hipStream_t s) { VV_BIG_NS::launch_raymarch_impl(a, s); }
+template <> void launch_frame<FRAME_COMPOSITE, kBuild>(const MarchArgs &a, hipStream_t s) { VV_BIG_NS::launch_raymarch_impl(a, s); }
 #ifdef VV_BUILD_LINEAR
 void launch_rad(const MarchArgs &a, hipStream_t s) { small::launch_rad_impl(a, s); }
 #endif

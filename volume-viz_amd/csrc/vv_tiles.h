@@ -1,9 +1,8 @@
-// vv_tiles.h -- the tile grid of march_kernel and mip_kernel: the one definition of which block marches which tile, which pixel a lane
+// vv_tiles.h -- the tile grid of the unshaded march kernels (march_kernel, mip_kernel, iso_kernel, proj_kernel): the one definition of which block marches which tile, which pixel a lane
 // of it owns, how many blocks a launch has, and the format of the `order` table (internal; included from vv_kernels.h).
 //
-// rad_kernel (writer of the table), march_kernel and mip_kernel (its readers), their launchers and render_frame (which sizes the table) all go
-// through the functions below.  choose_launch and the rectangle code of
-// render_frame fill the map in.  Everything here compiles for the host as well: host/tile_grid_check.cpp walks whole grids on the CPU.
+// rad_kernel (writer of the table), the four march kernels (its readers), their launchers and render_frame (which sizes the table) all go
+// through the functions below.  choose_launch and render_frame's rectangle and tile-order stages fill the map in.  Everything here compiles for the host as well: host/tile_grid_check.cpp walks whole grids on the CPU.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

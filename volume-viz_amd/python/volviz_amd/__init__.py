@@ -418,6 +418,23 @@ class Context:
         tf = np.ascontiguousarray(tf, np.float32).reshape(1024)
         self._chk(self.lib.vv_set_transfer_function(self.h, tf.ctypes.data))
 
+    @staticmethod
+    def _frame_args(width, height, cam, slice, rays, options, shading=None):
+        """The leading arguments of a vv_render* call after (context, W, H): slice, camera, [shading,] ray source, options."""
+        sp = slice if slice is not None else make_slice_params()
+        rs = rays if rays is not None else analytic_rays(cam)
+        return ((C.byref(sp), C.byref(cam.params(width, height))) + ((C.byref(shading),) if shading is not None else ()) +
+                (C.byref(rs), C.byref(options) if options is not None else None))
+
+    @staticmethod
+    def _host_images(width, height, fill, *extra):
+        """The host images of a frame, every byte `fill`: rgba uint8 [H, W, 4] and one per (wanted, bytes of a pixel as a shape, dtype) of `extra`.
+        Returns their addresses (None where not wanted) and what the render method returns: the rgba image, or a tuple with the wanted others behind it."""
+        imgs = [np.full((height, width, 4), fill, np.uint8)]
+        imgs += [np.full((height, width) + px, fill, np.uint8).view(dtype) if wanted else None for wanted, px, dtype in extra]
+        res = tuple(i for i in imgs if i is not None)
+        return [None if i is None else i.ctypes.data for i in imgs], res if len(res) > 1 else res[0]
+
     # runCuda (kernel.cu:388-453)
     def render(self, width: int, height: int, cam: Camera, *, slice: Optional[slice_params] = None,
                phong: bool = False, rays: Optional[vv_ray_source] = None,
@@ -425,26 +442,16 @@ class Context:
                fill: int = 0) -> np.ndarray:
         """Host-buffer render; returns uint8 [H, W, 4] (row 0 = bottom)."""
         if out is None:
-            out = np.full((height, width, 4), fill, np.uint8)
-        sp = slice if slice is not None else make_slice_params()
-        cp = cam.params(width, height)
-        sh = shading_params(-1, phong)
-        rs = rays if rays is not None else analytic_rays(cam)
-        self._chk(self.lib.vv_render(self.h, width, height, C.byref(sp), C.byref(cp), C.byref(sh), C.byref(rs),
-                                     C.byref(options) if options is not None else None,
-                                     out.ctypes.data, 0, None))
+            _, out = self._host_images(width, height, fill)
+        args = self._frame_args(width, height, cam, slice, rays, options, shading_params(-1, phong))
+        self._chk(self.lib.vv_render(self.h, width, height, *args, out.ctypes.data, 0, None))
         return out
 
     def render_device(self, width: int, height: int, cam: Camera, out_ptr: int, *, slice=None, phong=False,
                       rays=None, options=None, stream: int = 0):
         """Device-buffer render enqueued on `stream` (a hipStream_t as int)."""
-        sp = slice if slice is not None else make_slice_params()
-        cp = cam.params(width, height)
-        sh = shading_params(-1, phong)
-        rs = rays if rays is not None else analytic_rays(cam)
-        self._chk(self.lib.vv_render(self.h, width, height, C.byref(sp), C.byref(cp), C.byref(sh), C.byref(rs),
-                                     C.byref(options) if options is not None else None,
-                                     out_ptr, 1, stream))
+        args = self._frame_args(width, height, cam, slice, rays, options, shading_params(-1, phong))
+        self._chk(self.lib.vv_render(self.h, width, height, *args, out_ptr, 1, stream))
 
     # vv_render_mip / vv_classify_indices (no reference counterpart)
     def render_mip(self, width: int, height: int, cam: Camera, *, slice: Optional[slice_params] = None,
@@ -452,24 +459,14 @@ class Context:
                    fill: int = 0, return_index: bool = False):
         """Host-buffer maximum-intensity projection; returns rgba uint8 [H, W, 4] (row 0 = bottom), or (rgba, index uint8 [H, W])
         with return_index.  Pixels the frame does not write keep `fill` in both images."""
-        out = np.full((height, width, 4), fill, np.uint8)
-        idx = np.full((height, width), fill, np.uint8) if return_index else None
-        sp = slice if slice is not None else make_slice_params()
-        cp = cam.params(width, height)
-        rs = rays if rays is not None else analytic_rays(cam)
-        self._chk(self.lib.vv_render_mip(self.h, width, height, C.byref(sp), C.byref(cp), C.byref(rs),
-                                         C.byref(options) if options is not None else None,
-                                         out.ctypes.data, idx.ctypes.data if return_index else None, 0, None))
-        return (out, idx) if return_index else out
+        ptrs, res = self._host_images(width, height, fill, (return_index, (), np.uint8))
+        self._chk(self.lib.vv_render_mip(self.h, width, height, *self._frame_args(width, height, cam, slice, rays, options), *ptrs, 0, None))
+        return res
 
     def render_mip_device(self, width: int, height: int, cam: Camera, rgba_ptr: int = 0, index_ptr: int = 0, *, slice=None,
                           rays=None, options=None, stream: int = 0):
         """Device-buffer MIP frame enqueued on `stream` (a hipStream_t as int): rgba_ptr (W*H*4 bytes) and / or index_ptr (W*H bytes), 0 = not wanted."""
-        sp = slice if slice is not None else make_slice_params()
-        cp = cam.params(width, height)
-        rs = rays if rays is not None else analytic_rays(cam)
-        self._chk(self.lib.vv_render_mip(self.h, width, height, C.byref(sp), C.byref(cp), C.byref(rs),
-                                         C.byref(options) if options is not None else None,
+        self._chk(self.lib.vv_render_mip(self.h, width, height, *self._frame_args(width, height, cam, slice, rays, options),
                                          rgba_ptr or None, index_ptr or None, 1, stream))
 
     # vv_render_iso (no reference counterpart)
@@ -479,28 +476,15 @@ class Context:
         """Host-buffer isosurface frame at `level` (1..255); returns rgba uint8 [H, W, 4] (row 0 = bottom), or a tuple with index uint8 [H, W]
         (return_index) and hit float32 [H, W, 4] = (x, y, z, ordinal) (return_hit) behind it.  Pixels the frame does not write keep `fill` in
         every byte of all images (the float image's bytes too)."""
-        out = np.full((height, width, 4), fill, np.uint8)
-        idx = np.full((height, width), fill, np.uint8) if return_index else None
-        hit = np.full((height, width, 16), fill, np.uint8).view(np.float32) if return_hit else None
-        sp = slice if slice is not None else make_slice_params()
-        cp = cam.params(width, height)
-        rs = rays if rays is not None else analytic_rays(cam)
-        self._chk(self.lib.vv_render_iso(self.h, width, height, C.byref(sp), C.byref(cp), C.byref(rs),
-                                         C.byref(options) if options is not None else None, int(level),
-                                         out.ctypes.data, idx.ctypes.data if return_index else None,
-                                         hit.ctypes.data if return_hit else None, 0, None))
-        res = (out,) + ((idx,) if return_index else ()) + ((hit,) if return_hit else ())
-        return res if len(res) > 1 else out
+        ptrs, res = self._host_images(width, height, fill, (return_index, (), np.uint8), (return_hit, (16,), np.float32))
+        self._chk(self.lib.vv_render_iso(self.h, width, height, *self._frame_args(width, height, cam, slice, rays, options), int(level), *ptrs, 0, None))
+        return res
 
     def render_iso_device(self, width: int, height: int, cam: Camera, level: int, rgba_ptr: int = 0, index_ptr: int = 0, hit_ptr: int = 0, *,
                           slice=None, rays=None, options=None, stream: int = 0):
         """Device-buffer isosurface frame enqueued on `stream` (a hipStream_t as int): rgba_ptr (W*H*4 bytes), index_ptr (W*H bytes) and / or
         hit_ptr (W*H*16 bytes, 16-byte aligned), 0 = not wanted."""
-        sp = slice if slice is not None else make_slice_params()
-        cp = cam.params(width, height)
-        rs = rays if rays is not None else analytic_rays(cam)
-        self._chk(self.lib.vv_render_iso(self.h, width, height, C.byref(sp), C.byref(cp), C.byref(rs),
-                                         C.byref(options) if options is not None else None, int(level),
+        self._chk(self.lib.vv_render_iso(self.h, width, height, *self._frame_args(width, height, cam, slice, rays, options), int(level),
                                          rgba_ptr or None, index_ptr or None, hit_ptr or None, 1, stream))
 
     # vv_render_projection (no reference counterpart)
@@ -511,28 +495,15 @@ class Context:
         (row 0 = bottom), or a tuple with index uint8 [H, W] (return_index) and stat uint32 [H, W, 2] (return_stat) behind it: (ordinal of the
         extremum among the ray's executed samples, counted samples) for PROJ_MAX / PROJ_MIN, (sum, counted samples) for PROJ_MEAN.  Pixels the
         frame does not write keep `fill` in every byte of all images."""
-        out = np.full((height, width, 4), fill, np.uint8)
-        idx = np.full((height, width), fill, np.uint8) if return_index else None
-        stat = np.full((height, width, 8), fill, np.uint8).view(np.uint32) if return_stat else None
-        sp = slice if slice is not None else make_slice_params()
-        cp = cam.params(width, height)
-        rs = rays if rays is not None else analytic_rays(cam)
-        self._chk(self.lib.vv_render_projection(self.h, width, height, C.byref(sp), C.byref(cp), C.byref(rs),
-                                                C.byref(options) if options is not None else None, int(mode),
-                                                out.ctypes.data, idx.ctypes.data if return_index else None,
-                                                stat.ctypes.data if return_stat else None, 0, None))
-        res = (out,) + ((idx,) if return_index else ()) + ((stat,) if return_stat else ())
-        return res if len(res) > 1 else out
+        ptrs, res = self._host_images(width, height, fill, (return_index, (), np.uint8), (return_stat, (8,), np.uint32))
+        self._chk(self.lib.vv_render_projection(self.h, width, height, *self._frame_args(width, height, cam, slice, rays, options), int(mode), *ptrs, 0, None))
+        return res
 
     def render_projection_device(self, width: int, height: int, cam: Camera, mode: int, rgba_ptr: int = 0, index_ptr: int = 0, stat_ptr: int = 0, *,
                                  slice=None, rays=None, options=None, stream: int = 0):
         """Device-buffer projection frame enqueued on `stream` (a hipStream_t as int): rgba_ptr (W*H*4 bytes), index_ptr (W*H bytes) and / or
         stat_ptr (W*H*8 bytes, 8-byte aligned), 0 = not wanted."""
-        sp = slice if slice is not None else make_slice_params()
-        cp = cam.params(width, height)
-        rs = rays if rays is not None else analytic_rays(cam)
-        self._chk(self.lib.vv_render_projection(self.h, width, height, C.byref(sp), C.byref(cp), C.byref(rs),
-                                                C.byref(options) if options is not None else None, int(mode),
+        self._chk(self.lib.vv_render_projection(self.h, width, height, *self._frame_args(width, height, cam, slice, rays, options), int(mode),
                                                 rgba_ptr or None, index_ptr or None, stat_ptr or None, 1, stream))
 
     def classify_indices(self, index: np.ndarray, tf: Optional[np.ndarray] = None) -> np.ndarray:
