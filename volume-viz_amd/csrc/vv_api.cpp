@@ -28,6 +28,9 @@ struct vv_knobs {
     int bricked = -1, zpair = -1, zfast = -1, force_big = 0;
     int block_w = -1, tail = -1, rect = -1, lpt = -1, lpt_run = -1, phong_bricks = -1;
     int hist_blocks = -1;                   // VV_HIST_BLOCKS: cap on hist_kernel's grid (tests drive its grid-stride loop with it)
+    // finalize_layout: VV_PITCH_PAD = bytes of row padding (0 or anything that is no number: rows stay dense; not a multiple of 16 in 16..4096: the default),
+    // VV_PITCH_FORCE (set: any row length is padded), VV_PITCH_ROWS = extra rows per slice (0..64, anything else: the default)
+    int pitch_pad = 32, pitch_rows = -1; bool pitch_force = false;
     static int geti(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
     void read()
     {
@@ -38,6 +41,9 @@ struct vv_knobs {
         zfast = geti("VV_ZFAST", -1); force_big = getenv("VV_FORCE_BIG") != nullptr;
         rect = geti("VV_RECT", -1); lpt = geti("VV_LPT", -1); lpt_run = geti("VV_LPT_RUN", -1); phong_bricks = geti("VV_PHONG_BRICKS", -1);
         hist_blocks = geti("VV_HIST_BLOCKS", -1);
+        const int pad = geti("VV_PITCH_PAD", 32);
+        pitch_pad = pad <= 0 ? 0 : ((pad >= 16 && pad <= 4096 && pad % 16 == 0) ? pad : 32);
+        pitch_force = getenv("VV_PITCH_FORCE") != nullptr; pitch_rows = geti("VV_PITCH_ROWS", -1);
     }
 };
 
@@ -51,6 +57,22 @@ struct layout_copy {
     // what the sampler needs (VolumeView): bytes per row and per slab (pair copies), per row and per slice (z-fastest), per brick row and per brick layer / 64
     uint32_t row = 0; uint64_t slab = 0;
 };
+
+// The context's scratch buffers: device memory that a call grows to what it needs and the next call reuses.
+enum {
+    SC_RAD,         // frames: one radius per slab (rad_kernel -> march kernels)
+    SC_ORDER,       // frames: StripMap::order of the frame in flight
+    SC_FRAME,       // RGBA image of a host-buffer frame / of vv_classify_indices
+    SC_INDEX,       // index image of a host-buffer MIP / iso / projection frame, of vv_classify_indices and of vv_histogram_indices
+    SC_HIT,         // iso: hit records of a host-buffer frame
+    SC_STAT,        // projection: stat records of a host-buffer frame
+    SC_IMG,         // the two first-pass images: of a host image ray source, of a host-buffer vv_first_pass
+    SC_SLICE,       // the image of a host-buffer slice, both images of a slab slice
+    SC_GEN,         // per-axis tables of the ellipsoid generator
+    SC_TF_ARG,      // vv_classify_indices: the caller's table
+    SC_N
+};
+struct scratch_buf { void *p = nullptr; size_t cap = 0; };
 
 struct vv_context {
     int device = 0;
@@ -72,17 +94,7 @@ struct vv_context {
     // transfer function
     float4 *d_tf = nullptr; bool tf_gray = false; bool have_tf = false;
     bool tf_alpha_unit = false;          // every opacity of the table lies in [0, 1]: accumulated opacity never decreases
-    // scratch
-    float *d_rad = nullptr; size_t rad_cap = 0;
-    uint32_t *d_order = nullptr; size_t order_cap = 0;      // StripMap::order of the frame in flight
-    uint8_t *d_frame = nullptr; size_t frame_cap = 0;
-    uint8_t *d_index = nullptr; size_t index_cap = 0;       // MIP / iso: index image of a host-buffer frame / of vv_classify_indices
-    uint8_t *d_hit = nullptr; size_t hit_cap = 0;           // iso: hit records of a host-buffer frame
-    uint8_t *d_stat = nullptr; size_t stat_cap = 0;         // projection: stat records of a host-buffer frame
-    float4 *d_tf_arg = nullptr;                             // vv_classify_indices: the caller's table
-    uint8_t *d_img = nullptr; size_t img_cap = 0;
-    float *d_slice = nullptr; size_t slice_cap = 0;
-    float *d_gen = nullptr; size_t gen_cap = 0;       // per-axis tables of the ellipsoid generator
+    scratch_buf scratch[SC_N];                              // grown on demand (ensure), freed and counted in loops over the table
     // launch-policy estimate taken from device-resident first-pass images (vv_render, synchronous calls), kept while the view stays
     struct view_key_t { float cam[8]; const void *front, *back; int img_w, img_h, W, H; } view_key;
     bool view_key_valid = false, view_est_ok = false; float view_side[3] = {0, 0, 0}, view_px_cube = 0.f;
@@ -107,6 +119,7 @@ static std::string g_err;
 static const size_t kHistResultOffset = kHistAccWords * sizeof(unsigned long long);
 static const size_t kHistScratchBytes = kHistResultOffset + sizeof(vv_histogram);
 static_assert(sizeof(vv_histogram) == 2072 && sizeof(unsigned long long) == 8, "vv_histogram layout (include/volviz.h)");
+static const size_t kStageBytes = 64u << 20;      // streamed upload: pinned / device staging buffers (vv_context::pin, d_stage)
 
 static int fail(vv_context *c, int code, const std::string &msg)
 {
@@ -135,12 +148,102 @@ static void drop_copies(vv_context *c)
     c->view_key_valid = false;             // (a new volume: the launch-policy estimate taken from first-pass images is re-taken)
 }
 
-static int ensure(vv_context *c, void **p, size_t *cap, size_t need)
+// ---- the linear volume: checked, given up and allocated in one place each (the loaders, the streamed upload, vv_shutdown) -------------------
+// `who`: the caller's message prefix; bad_dims / bad_type: its texts for those two findings
+static int check_volume(vv_context *c, const char *who, const char *bad_dims, const char *bad_type, int vtype, int nx, int ny, int nz)
 {
-    if (*cap >= need && *p) return VV_OK;
-    if (*p) { HIPCHK(c, hipFree(*p)); *p = nullptr; *cap = 0; }
-    HIPCHK(c, hipMalloc(p, need));
-    *cap = need;
+    const std::string w(who);
+    if (nx < 1 || ny < 1 || nz < 1) return fail(c, VV_ERR_INVALID, w + bad_dims);
+    if (vtype != VV_VOXEL_U8 && vtype != VV_VOXEL_F32) return fail(c, VV_ERR_INVALID, w + bad_type);
+    const size_t vsz = vtype == VV_VOXEL_F32 ? 4 : 1;
+    if ((size_t)nx * ny * vsz > 0xFFFFFFF0ull) return fail(c, VV_ERR_INVALID, w + "one slice must stay below 4 GiB");
+    if ((size_t)nx * vsz >= (1u << 24) || ny >= (1 << 24) || nz >= (1 << 24))
+        return fail(c, VV_ERR_INVALID, w + "a volume row must be below 16 MiB and each dimension below 2^24");
+    return VV_OK;
+}
+
+// Gives up the loaded volume and its copies: later calls report VV_ERR_NO_VOLUME until the next load.  (The reference leaks its old volume.)
+static int release_volume(vv_context *c)
+{
+    drop_copies(c);
+    void *old = c->d_vol;
+    c->d_vol = nullptr; c->nx = c->ny = c->nz = 0; c->vol_bytes = 0;
+    if (old) HIPCHK(c, hipFree(old));
+    return VV_OK;
+}
+
+// Allocates the (dense) linear volume and sets its geometry.  Behind the voxels lie one slice + two rows + 4096 bytes, zeroed on `st`: weight-0
+// corner fetches of edge samples land there instead of needing index clamps (see vv_device.h VolumeView).
+static int alloc_volume(vv_context *c, int vtype, int nx, int ny, int nz, hipStream_t st)
+{
+    const size_t vsz = vtype == VV_VOXEL_F32 ? 4 : 1;
+    const size_t bytes = (size_t)nx * ny * nz * vsz, pad = (size_t)nx * ny * vsz + 2 * (size_t)nx * vsz + 4096;
+    HIPCHK(c, hipMalloc(&c->d_vol, bytes + pad));
+    HIPCHK(c, hipMemsetAsync((char *)c->d_vol + bytes, 0, pad, st));
+    c->vol_bytes = bytes; c->vtype = vtype; c->nx = nx; c->ny = ny; c->nz = nz;
+    c->row_pitch = (size_t)nx * vsz; c->slice_pitch = c->row_pitch * ny; c->alloc_bytes = bytes + pad;
+    return VV_OK;
+}
+
+static int ensure(vv_context *c, int id, size_t need)
+{
+    scratch_buf &s = c->scratch[id];
+    if (s.cap >= need && s.p) return VV_OK;
+    if (s.p) { HIPCHK(c, hipFree(s.p)); s.p = nullptr; s.cap = 0; }
+    HIPCHK(c, hipMalloc(&s.p, need));
+    s.cap = need;
+    return VV_OK;
+}
+
+// ---- host-or-device buffers of the calls that are not frames --------------------------------------------------------------------------------
+// One buffer of a call: the caller's pointer and size, and where it lives.  A device buffer is used where it is.  A host buffer gets a place on
+// the device -- `home` if the call has a fixed one, else the next bytes of scratch entry `scratch` (the host buffers of a call that name the
+// same entry lie one after another in list order) -- which the caller's bytes are copied into before the kernels (`in`: data the kernel reads,
+// or an output whose skipped elements must keep the caller's bytes) and / or copied back from behind them (`out`).  Zero-byte buffers are not staged.
+struct CallBuf {
+    void *user; size_t bytes;
+    bool host, in, out;
+    int scratch; void *home;
+    void *dev;                          // stage_call: where the kernels read / write
+};
+
+// Before the kernels: sets the device, picks the stream (*st), gives every host buffer its place and enqueues the uploads in list order.
+static int stage_call(vv_context *c, void *stream, hipStream_t *st, CallBuf *b, int n)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    *st = pick_stream(c, stream);
+    size_t need[SC_N] = {}, off[8];
+    bool staged = false;
+    assert(n <= 8);
+    for (int i = 0; i < n; ++i) {
+        b[i].dev = b[i].user;
+        if (!b[i].host || !b[i].bytes) continue;
+        staged = true;
+        if (!b[i].home) { off[i] = need[b[i].scratch]; need[b[i].scratch] += b[i].bytes; }
+    }
+    if (!staged) return VV_OK;                  // every buffer is on the device or empty: used where it is
+    for (int id = 0; id < SC_N; ++id)
+        if (need[id]) { int rc = ensure(c, id, need[id]); if (rc) return rc; }
+    for (int i = 0; i < n; ++i) {
+        if (!b[i].host || !b[i].bytes) continue;
+        b[i].dev = b[i].home ? b[i].home : (char *)c->scratch[b[i].scratch].p + off[i];
+        if (b[i].in) HIPCHK(c, hipMemcpyAsync(b[i].dev, b[i].user, b[i].bytes, hipMemcpyHostToDevice, *st));
+    }
+    return VV_OK;
+}
+
+// Behind the kernels: their launch errors, the downloads in list order, and the one rule of who waits: a call with a host output returns when the
+// caller's buffer is filled; a call whose outputs stay on the device waits only when `stream` is NULL (with a stream it has only enqueued).
+static int finish_call(vv_context *c, void *stream, hipStream_t st, const CallBuf *b, int n)
+{
+    HIPCHK(c, hipGetLastError());
+    bool host_out = false;
+    for (int i = 0; i < n; ++i) {
+        if (!b[i].host || !b[i].out) continue;
+        host_out = true;
+        if (b[i].bytes) HIPCHK(c, hipMemcpyAsync(b[i].user, b[i].dev, b[i].bytes, hipMemcpyDeviceToHost, st));
+    }
+    if (host_out || !stream) HIPCHK(c, hipStreamSynchronize(st));
     return VV_OK;
 }
 
@@ -272,15 +375,25 @@ static bool ensure_bricks(vv_context *c, hipStream_t st)
         launch_build_bricks(c->vtype, c->d_vol, c->row_pitch, c->slice_pitch, p, c->nx, c->ny, c->nz, st); });
 }
 
+// The launch policy's two questions about the loaded volume (choose_launch, where the measurements behind them are, and vv_prepare_layouts):
+// may unshaded frames take the pair copies (u8, or f32 up to 512 MiB), and is the volume big enough for the bricked / z-fastest copy to pay?
+static bool pair_copies_allowed(const vv_context *c) { return c->vtype == VV_VOXEL_U8 || c->vol_bytes <= (512ull << 20); }
+static bool big_enough_for_copies(const vv_context *c) { return (size_t)c->nx * c->ny * c->nz >= (1ull << 21); }
+
+// The addressing limits of a pair copy of `bytes` whose rows run along a dimension of n_fast voxels (z-pair: nx, x-pair: nz)
+static bool pair_copy_addressable(const vv_context *c, int n_fast, size_t bytes)
+{
+    return (size_t)(c->ny + 1) * ((size_t)n_fast + 1) * 8 < (1ull << 32) && ((size_t)n_fast + 1) * 8 < (1u << 24) &&
+           !(c->vtype == VV_VOXEL_U8 && bytes >= (1ull << 32));                // u8 sampler: 32-bit offsets
+}
+
 static bool ensure_zpair(vv_context *c, hipStream_t st)
 {
     layout_copy &cp = c->copies[CP_ZPAIR];
     if (cp.valid) return true;
     uint32_t rb = 0, sb = 0;
     const size_t bytes = zpair_copy_bytes(c->vtype, c->nx, c->ny, c->nz, &rb, &sb);
-    if ((size_t)(c->ny + 1) * ((size_t)c->nx + 1) * 8 >= (1ull << 32) || ((size_t)c->nx + 1) * 8 >= (1u << 24) ||
-        (c->vtype == VV_VOXEL_U8 && bytes >= (1ull << 32)))                // u8 sampler: 32-bit offsets
-        return copy_refused(c, CP_ZPAIR);
+    if (!pair_copy_addressable(c, c->nx, bytes)) return copy_refused(c, CP_ZPAIR);
     cp.row = rb; cp.slab = sb;
     return build_copy(c, CP_ZPAIR, bytes, 32, bytes, 0, st, [&](void *p) {
         launch_build_zpair(c->vtype, c->d_vol, c->row_pitch, c->slice_pitch, p, c->nx, c->ny, c->nz, st); });
@@ -306,7 +419,7 @@ static bool ensure_zfast(vv_context *c, hipStream_t st)
         launch_build_zfast(c->vtype, c->d_vol, (uint32_t)c->row_pitch, (uint64_t)c->slice_pitch, p, (uint32_t)row, (uint64_t)slice, c->nx, c->ny, c->nz, st); });
 }
 
-// The x-pair copy (the z-pair copy with x and z exchanged; built from the z-fastest copy): the limits of ensure_zpair with the roles swapped.
+// The x-pair copy (the z-pair copy with x and z exchanged; built from the z-fastest copy).
 static bool ensure_xpair(vv_context *c, hipStream_t st)
 {
     layout_copy &cp = c->copies[CP_XPAIR];
@@ -314,9 +427,7 @@ static bool ensure_xpair(vv_context *c, hipStream_t st)
     if (!ensure_zfast(c, st)) return false;
     uint32_t rb = 0, sb = 0;
     const size_t bytes = zpair_copy_bytes(c->vtype, c->nz, c->ny, c->nx, &rb, &sb);
-    if ((size_t)(c->ny + 1) * ((size_t)c->nz + 1) * 8 >= (1ull << 32) || ((size_t)c->nz + 1) * 8 >= (1u << 24) ||
-        (c->vtype == VV_VOXEL_U8 && bytes >= (1ull << 32)))                // u8 sampler: 32-bit offsets
-        return copy_refused(c, CP_XPAIR);
+    if (!pair_copy_addressable(c, c->nz, bytes)) return copy_refused(c, CP_XPAIR);
     cp.row = rb; cp.slab = sb;
     const layout_copy &zf = c->copies[CP_ZFAST];
     return build_copy(c, CP_XPAIR, bytes, 32, bytes, 1u << CP_ZFAST, st, [&](void *p) {
@@ -357,7 +468,7 @@ int vv_init(int device, vv_context **out)
         hipMalloc((void **)&c->d_hist, kHistScratchBytes) != hipSuccess ||
         hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess ||
         hipMalloc((void **)&c->d_tf, 256 * sizeof(float4)) != hipSuccess) {
-        delete c;
+        vv_shutdown(c);                           // (gives back whatever was created before the failure)
         return fail(nullptr, VV_ERR_DEVICE, "vv_init: device set-up failed");
     }
     *out = c;
@@ -368,20 +479,11 @@ int vv_shutdown(vv_context *c)
 {
     if (!c) return VV_OK;
     hipSetDevice(c->device);
-    hipStreamSynchronize(c->stream);
-    if (c->d_vol) hipFree(c->d_vol);
-    drop_copies(c);
+    if (c->stream) hipStreamSynchronize(c->stream);
+    (void)release_volume(c);
     if (c->d_tf) hipFree(c->d_tf);
-    if (c->d_rad) hipFree(c->d_rad);
-    if (c->d_order) hipFree(c->d_order);
-    if (c->d_frame) hipFree(c->d_frame);
-    if (c->d_index) hipFree(c->d_index);
-    if (c->d_hit) hipFree(c->d_hit);
-    if (c->d_stat) hipFree(c->d_stat);
-    if (c->d_tf_arg) hipFree(c->d_tf_arg);
-    if (c->d_img) hipFree(c->d_img);
-    if (c->d_slice) hipFree(c->d_slice);
-    if (c->d_gen) hipFree(c->d_gen);
+    for (scratch_buf &s : c->scratch)
+        if (s.p) hipFree(s.p);
     if (c->d_counter) hipFree(c->d_counter);
     if (c->d_hist) hipFree(c->d_hist);
     for (int i = 0; i < 2; ++i) {
@@ -422,29 +524,14 @@ static int install_volume(vv_context *c, const void *src, bool src_on_device, in
                           int nx, int ny, int nz, const float tf[1024], hipStream_t s)
 {
     if (!c || !src) return fail(c, VV_ERR_INVALID, "load_volume: NULL argument");
-    if (nx < 1 || ny < 1 || nz < 1) return fail(c, VV_ERR_INVALID, "load_volume: dims must be >= 1");
-    if (vtype != VV_VOXEL_U8 && vtype != VV_VOXEL_F32) return fail(c, VV_ERR_INVALID, "load_volume: bad voxel type");
-    const size_t vsz = vtype == VV_VOXEL_F32 ? 4 : 1;
-    const size_t bytes = (size_t)nx * ny * nz * vsz;
-    if ((size_t)nx * ny * vsz > 0xFFFFFFF0ull)
-        return fail(c, VV_ERR_INVALID, "load_volume: one slice must stay below 4 GiB");
-    if ((size_t)nx * vsz >= (1u << 24) || nx >= (1 << 24) || ny >= (1 << 24) || nz >= (1 << 24))
-        return fail(c, VV_ERR_INVALID, "load_volume: a volume row must be below 16 MiB and each dimension below 2^24");
+    int rc = check_volume(c, "load_volume: ", "dims must be >= 1", "bad voxel type", vtype, nx, ny, nz);
+    if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     c->knobs.read();
-    // one slice + one row + 16 bytes of zero padding: weight-0 corner fetches of edge
-    // samples land here instead of needing index clamps (see vv_device.h VolumeView)
-    const size_t pad = (size_t)nx * ny * vsz + 2 * (size_t)nx * vsz + 4096;
-    drop_copies(c);
-    if (c->d_vol) { HIPCHK(c, hipFree(c->d_vol)); c->d_vol = nullptr; }   // the reference leaks here
-    HIPCHK(c, hipMalloc(&c->d_vol, bytes + pad));
     hipStream_t st = pick_stream(c, s);
-    HIPCHK(c, hipMemsetAsync((char *)c->d_vol + bytes, 0, pad, st));
-    if (src_on_device) HIPCHK(c, hipMemcpyAsync(c->d_vol, src, bytes, hipMemcpyDeviceToDevice, st));
-    else { HIPCHK(c, hipMemcpyAsync(c->d_vol, src, bytes, hipMemcpyHostToDevice, st)); }
-    c->vol_bytes = bytes; c->vtype = vtype; c->nx = nx; c->ny = ny; c->nz = nz;
-    c->row_pitch = (size_t)nx * vsz; c->slice_pitch = c->row_pitch * ny; c->alloc_bytes = bytes + pad;
-    { int rc = finalize_layout(c, st); if (rc) return rc; }
+    if ((rc = release_volume(c)) != VV_OK || (rc = alloc_volume(c, vtype, nx, ny, nz, st)) != VV_OK) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->d_vol, src, c->vol_bytes, src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    if ((rc = finalize_layout(c, st)) != VV_OK) return rc;
     if (!src_on_device || !s) HIPCHK(c, hipStreamSynchronize(st));
     if (tf) return vv_set_transfer_function(c, tf);
     return VV_OK;
@@ -472,10 +559,10 @@ int vv_prepare_layouts(vv_context *c, int which, void *stream)
     if (which & ~(VV_LAYOUT_BRICKED | VV_LAYOUT_ZPAIR | VV_LAYOUT_ZFAST | VV_LAYOUT_POLICY)) return fail(c, VV_ERR_INVALID, "vv_prepare_layouts: unknown layout bit");
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = pick_stream(c, stream);
-    const bool pair_ok = c->vtype == VV_VOXEL_U8 || c->vol_bytes <= (512ull << 20);          // (the z-pair / x-pair conditions of vv_render)
+    const bool pair_ok = pair_copies_allowed(c);          // (the z-pair / x-pair conditions of vv_render)
     if (which & VV_LAYOUT_POLICY) {
         // every copy vv_render's policy can pick for this volume, in the order of what an orbit needs most: oblique views, side views, the pair copies
-        if ((size_t)c->nx * c->ny * c->nz >= (1ull << 21)) which |= VV_LAYOUT_BRICKED | VV_LAYOUT_ZFAST;
+        if (big_enough_for_copies(c)) which |= VV_LAYOUT_BRICKED | VV_LAYOUT_ZFAST;
         if (pair_ok) which |= VV_LAYOUT_ZPAIR;
     }
     int built = 0;
@@ -529,7 +616,10 @@ int vv_device_bytes(const vv_context *c, unsigned long long out[4])
     out[0] = c->d_vol ? c->alloc_bytes : 0;
     out[1] = copy_bytes(c, CP_BRICKS);
     out[2] = copy_bytes(c, CP_ZPAIR) + copy_bytes(c, CP_ZFAST) + copy_bytes(c, CP_XPAIR);
-    out[3] = c->rad_cap + c->frame_cap + c->index_cap + c->hit_cap + c->stat_cap + (c->d_tf_arg ? 4096 : 0) + c->img_cap + c->slice_cap + 4096 + 8 * sizeof(unsigned long long) + kHistScratchBytes;
+    // tables and scratch: the fixed allocations of vv_init (transfer function, counters, histogram scratch), the scratch table, the streamed upload's staging
+    out[3] = 256 * sizeof(float4) + 16 * sizeof(unsigned long long) + kHistScratchBytes;
+    for (const scratch_buf &s : c->scratch) out[3] += s.cap;
+    for (const uint8_t *stage : c->d_stage) out[3] += stage ? kStageBytes : 0;
     return VV_OK;
 }
 
@@ -544,29 +634,17 @@ int vv_debug_counters(vv_context *c, unsigned long long out[16])
 }
 
 // ---- streamed upload ---------------------------------------------------------------------
-static const size_t kStageBytes = 64u << 20;      // pinned / device staging buffers
-
 int vv_load_volume_stream_begin(vv_context *c, int vtype, int nx, int ny, int nz, const float tf[1024])
 {
     if (!c) return fail(nullptr, VV_ERR_INVALID, "stream_begin: NULL context");
-    if (nx < 1 || ny < 1 || nz < 1 || (vtype != VV_VOXEL_U8 && vtype != VV_VOXEL_F32))
-        return fail(c, VV_ERR_INVALID, "stream_begin: bad dims / voxel type");
-    const size_t vsz = vtype == VV_VOXEL_F32 ? 4 : 1;
-    if ((size_t)nx * ny * vsz > 0xFFFFFFF0ull) return fail(c, VV_ERR_INVALID, "stream_begin: one slice must stay below 4 GiB");
-    if ((size_t)nx * vsz >= (1u << 24) || ny >= (1 << 24) || nz >= (1 << 24))
-        return fail(c, VV_ERR_INVALID, "stream_begin: a volume row must be below 16 MiB and each dimension below 2^24");
+    int rc = check_volume(c, "stream_begin: ", "bad dims / voxel type", "bad dims / voxel type", vtype, nx, ny, nz);
+    if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     c->knobs.read();
-    const size_t bytes = (size_t)nx * ny * nz * vsz, pad = (size_t)nx * ny * vsz + 2 * (size_t)nx * vsz + 4096;
-    drop_copies(c);
-    if (c->d_vol) { HIPCHK(c, hipFree(c->d_vol)); c->d_vol = nullptr; }
-    HIPCHK(c, hipMalloc(&c->d_vol, bytes + pad));
     if (!c->copy_stream) HIPCHK(c, hipStreamCreate(&c->copy_stream));
     if (!c->promo_stream) HIPCHK(c, hipStreamCreate(&c->promo_stream));
-    HIPCHK(c, hipMemsetAsync((char *)c->d_vol + bytes, 0, pad, c->copy_stream));
+    if ((rc = release_volume(c)) != VV_OK || (rc = alloc_volume(c, vtype, nx, ny, nz, c->copy_stream)) != VV_OK) return rc;
     c->src_last = -1;
-    c->vol_bytes = bytes; c->vtype = vtype; c->nx = nx; c->ny = ny; c->nz = nz;
-    c->row_pitch = (size_t)nx * vsz; c->slice_pitch = c->row_pitch * ny; c->alloc_bytes = bytes + pad;
     c->streaming = true;
     if (tf) return vv_set_transfer_function(c, tf);
     return VV_OK;
@@ -655,6 +733,7 @@ int vv_load_volume_stream_end(vv_context *c)
     HIPCHK(c, hipStreamSynchronize(c->copy_stream));
     HIPCHK(c, hipStreamSynchronize(c->promo_stream));
     c->streaming = false; c->src_last = -1;
+    c->knobs.read();                      // (the pitch knobs are taken as they stand when the volume is complete, as before they moved into vv_knobs)
     { int rc = finalize_layout(c, c->copy_stream); if (rc) return rc; }
     HIPCHK(c, hipStreamSynchronize(c->copy_stream));
     return VV_OK;
@@ -689,9 +768,8 @@ int vv_load_volume_t3d(vv_context *c, const char *path, int header, int vtype, c
     int r3 = vv_load_volume_stream_end(c);
     if (rc || r3) {
         // a partly filled volume must not be rendered: drop it, later calls report VV_ERR_NO_VOLUME
-        drop_copies(c);
-        if (c->d_vol) { (void)hipFree(c->d_vol); c->d_vol = nullptr; }
-        c->nx = c->ny = c->nz = 0; c->vol_bytes = 0; c->streaming = false;
+        (void)release_volume(c);
+        c->streaming = false;
         if (rc == VV_ERR_IO) return fail(c, VV_ERR_IO, "vv_load_volume_t3d: file shorter than its header says");
         return rc ? rc : r3;
     }
@@ -716,18 +794,19 @@ int vv_volume_dims(const vv_context *c, int dims[3], int *vtype)
 // (+3 % by itself); C3 + Phong 2.52 -> 2.46 ms; 512^3 0.71 -> 0.66 ms and C2 0.245 -> 0.224 ms on the linear path;
 // u8 1024^3 0.88 -> 0.77 ms on the linear path (= its z-pair copy), u8 + Phong -1 %; other edge lengths gain 1 %
 // (not re-pitched).
-// VV_PITCH_PAD=0 disables, VV_PITCH_PAD=<bytes> sets the padding, VV_PITCH_FORCE=1 pads any row length.
+// VV_PITCH_PAD=0 disables, VV_PITCH_PAD=<bytes> sets the padding, VV_PITCH_FORCE=1 pads any row length (vv_knobs, read by the caller just before).
 static int finalize_layout(vv_context *c, hipStream_t st)
 {
-    size_t pad_bytes = 32;
-    if (const char *e = getenv("VV_PITCH_PAD")) { int t = atoi(e); if (t <= 0) return VV_OK; if (t >= 16 && t <= 4096 && t % 16 == 0) pad_bytes = (size_t)t; }
+    const vv_knobs &K = c->knobs;
+    if (K.pitch_pad == 0) return VV_OK;
+    const size_t pad_bytes = (size_t)K.pitch_pad;
     const size_t dense_row = c->row_pitch;
-    if (dense_row % 1024 != 0 && !getenv("VV_PITCH_FORCE")) return VV_OK;
+    if (dense_row % 1024 != 0 && !K.pitch_force) return VV_OK;
     if (dense_row % 16 != 0) return VV_OK;
     const size_t row = dense_row + pad_bytes;
     size_t rows = (size_t)c->ny;
     if ((rows * row) % 4096 == 0) rows += 1;
-    if (const char *e = getenv("VV_PITCH_ROWS")) { int t = atoi(e); if (t >= 0 && t <= 64) rows = (size_t)c->ny + (size_t)t; }
+    if (K.pitch_rows >= 0 && K.pitch_rows <= 64) rows = (size_t)c->ny + (size_t)K.pitch_rows;
     const size_t slice = rows * row;
     if (slice > 0xFFFFFFF0ull || row >= (1u << 24)) return VV_OK;
     const size_t bytes = slice * (size_t)c->nz, pad = slice + 2 * row + 4096;
@@ -831,7 +910,7 @@ static bool choose_launch(vv_context *c, MarchArgs &A, const camera_params *cam,
     bool use_zfast = false;
     if (have_basis && A.strips.tile_log2w == 3) {
         const float ax = fabsf(P.side[0]) , ay = fabsf(P.side[1]), az = fabsf(P.side[2]);
-        use_zfast = az >= 0.97f * sqrtf(ax * ax + ay * ay + az * az) && (size_t)c->nx * c->ny * c->nz >= (1ull << 21);
+        use_zfast = az >= 0.97f * sqrtf(ax * ax + ay * ay + az * az) && big_enough_for_copies(c);
         if (K.zfast >= 0) use_zfast = K.zfast != 0;
     }
     // Phong frames of f32 volumes beyond the caches sample the bricked copy from every direction: march_phong_kernel's blocks are 16 pixels wide whatever the
@@ -897,7 +976,7 @@ static bool choose_launch(vv_context *c, MarchArgs &A, const camera_params *cam,
     // built on first use if HBM has room (1.25x an f32 volume, 2x a u8 volume).  VV_BRICKED=0/1 overrides the policy.
     // Measured: 1024^3 rotated 3.85 -> 1.65 ms (f32), 3.17 -> 0.99 ms (u8); C2 (256^3) -19 %, C1 (128^3) -9 %;
     // only volumes far below the frame's sampling density lose (64^3 at 1080p, step 1/512: +10 %).
-    bool use_bricks = (A.strips.tile_log2w == 3 || phong_bricks) && (size_t)c->nx * c->ny * c->nz >= (1ull << 21);
+    bool use_bricks = (A.strips.tile_log2w == 3 || phong_bricks) && big_enough_for_copies(c);
     if (K.bricked >= 0) use_bricks = K.bricked != 0;
     if (use_zfast) use_bricks = false;
     if (use_bricks) use_bricks = take_copy(c, CP_BRICKS, st);
@@ -913,15 +992,13 @@ static bool choose_launch(vv_context *c, MarchArgs &A, const camera_params *cam,
     //        1024^3 (rays of different z phase stop sharing slices in L2): used up to 512 MiB;
     //   u8 : -8 % (256^3), -12 % (512^3), -4 % (1024^3): used whenever the copy stays below 4 GiB;
     //   Phong path: 0...-3 %: not used.                                  VV_ZPAIR=0/1 overrides.
-    bool use_zpair = !use_bricks && A.strips.tile_log2w == 5 && !shading->phongShading &&
-                     (c->vtype == VV_VOXEL_U8 || c->vol_bytes <= (512ull << 20));
+    bool use_zpair = !use_bricks && A.strips.tile_log2w == 5 && !shading->phongShading && pair_copies_allowed(c);
     if (K.zpair >= 0) use_zpair = K.zpair != 0 && !use_bricks;
     if (use_zfast) use_zpair = false;
     if (use_zpair) use_zpair = take_copy(c, CP_ZPAIR, st);
     // x-pair copy (speed only): the same two-gather form for side views -- the z-pair copy with x and z exchanged, handed to the kernel in the
     // z-pair fields of the view -- under the z-pair copy's conditions (unshaded, u8 or f32 up to 512 MiB).  Follows VV_ZPAIR=0.
-    const bool use_xpair = use_zfast && !shading->phongShading && K.zpair != 0 && (c->vtype == VV_VOXEL_U8 || c->vol_bytes <= (512ull << 20)) &&
-                           take_copy(c, CP_XPAIR, st);
+    const bool use_xpair = use_zfast && !shading->phongShading && K.zpair != 0 && pair_copies_allowed(c) && take_copy(c, CP_XPAIR, st);
     const int valid_after = copies_valid();
     if (valid_after > valid_before) c->builds_in_render += valid_after - valid_before;
     // The kernel build.  Linear volumes beyond the caches take the 64-bit-addressing build in Phong frames even below 4 GiB: the other one is compiled
@@ -978,10 +1055,10 @@ static void launch_build(FrameKind kind, const MarchArgs &A, hipStream_t st) { a
 struct FrameImage {
     void *host;                         // the caller's buffer (on the device when out_on_device), or null: not asked for
     size_t px_bytes;                    // bytes per pixel
-    uint8_t **scratch; size_t *cap;     // the context's staging buffer of a host-buffer frame
+    int scratch;                        // the context's staging buffer of a host-buffer frame (SC_*)
     unsigned align;                     // of the device pointer the kernels write through (a record is written in one store)
     const char *misaligned;             // vv_last_error text of a misaligned device pointer
-    uint8_t *dev;                       // where the kernels write: `host` itself, or *scratch
+    uint8_t *dev;                       // where the kernels write: `host` itself, or the scratch entry
 };
 
 // What the stages of render_frame hand on to each other.
@@ -1119,11 +1196,12 @@ static int view_knowledge(vv_context *c, Frame &F, const camera_params *cam, con
             P.front_img = rays->front; P.back_img = rays->back;
         }
         else {
-            int rc = ensure(c, (void **)&c->d_img, &c->img_cap, 2 * ib);
+            int rc = ensure(c, SC_IMG, 2 * ib);
             if (rc) return rc;
-            HIPCHK(c, hipMemcpyAsync(c->d_img, rays->front, ib, hipMemcpyHostToDevice, st));
-            HIPCHK(c, hipMemcpyAsync(c->d_img + ib, rays->back, ib, hipMemcpyHostToDevice, st));
-            P.front_img = c->d_img; P.back_img = c->d_img + ib;
+            uint8_t *d_img = (uint8_t *)c->scratch[SC_IMG].p;
+            HIPCHK(c, hipMemcpyAsync(d_img, rays->front, ib, hipMemcpyHostToDevice, st));
+            HIPCHK(c, hipMemcpyAsync(d_img + ib, rays->back, ib, hipMemcpyHostToDevice, st));
+            P.front_img = d_img; P.back_img = d_img + ib;
         }
         // no hint: the images themselves say how screen x runs through the volume and how dense the rays are.  Host images are
         // read in place; device images only by a synchronous call (an enqueue-only call must not wait for the stream), and the
@@ -1231,9 +1309,9 @@ static int tile_order(vv_context *c, Frame &F, const vv_ray_source *rays)
     // caches lose 1-6 % (the heaviest tiles marching together move more bytes), oblique views gain or lose up to 15 % with the camera: there the strips stay.
     const bool want = c->knobs.lpt > 0 ? true : (A.strips.tile_log2w == 5 && !beyond_caches && (long long)wr * ns >= 1024);      // (C1's 576 tiles: +2 %, the sort outlasts the rad pre-pass)
     if (c->knobs.lpt != 0 && want && !A.phong && rays->mode == VV_RAYS_ANALYTIC && W >= 2 && H >= 2 && units >= 8 && units <= 1024 && (long long)(wr + 1) * (ns + 1) <= 24576) {     // (rad_kernel: kMaxUnits, kMaxPoints)
-        const int rc = ensure(c, (void **)&c->d_order, &c->order_cap, std::max((size_t)order_words(A.strips), (size_t)65536) * sizeof(uint32_t));
+        const int rc = ensure(c, SC_ORDER, std::max((size_t)order_words(A.strips), (size_t)65536) * sizeof(uint32_t));
         if (rc) return rc;
-        A.strips.order = c->d_order; A.order_out = c->d_order;
+        A.strips.order = A.order_out = (uint32_t *)c->scratch[SC_ORDER].p;
     } else A.strips.order_run = 1;
     return VV_OK;
 }
@@ -1246,9 +1324,9 @@ static int stage_images(vv_context *c, Frame &F, int out_on_device)
     for (FrameImage &im : F.img) {
         im.dev = (uint8_t *)im.host;
         if (out_on_device || !im.host) continue;
-        int rc = ensure(c, (void **)im.scratch, im.cap, npx * im.px_bytes);
+        int rc = ensure(c, im.scratch, npx * im.px_bytes);
         if (rc) return rc;
-        im.dev = *im.scratch;
+        im.dev = (uint8_t *)c->scratch[im.scratch].p;
         if (!F.whole) HIPCHK(c, hipMemcpyAsync(im.dev, im.host, npx * im.px_bytes, hipMemcpyHostToDevice, F.st));
     }
     for (const FrameImage &im : F.img)
@@ -1312,17 +1390,17 @@ static int render_frame(vv_context *c, int W, int H, const slice_params *slice, 
     A.gray = c->tf_gray; A.phong = shading->phongShading;
     tiles_under_rect(c, F, rays);
     A.tf = c->d_tf; A.fill_tf = kind == FRAME_ISO ? nullptr : A.tf;
-    if ((rc = ensure(c, (void **)&c->d_rad, &c->rad_cap, (size_t)P.nbx * P.nby * sizeof(float))) != VV_OK) return rc;
+    if ((rc = ensure(c, SC_RAD, (size_t)P.nbx * P.nby * sizeof(float))) != VV_OK) return rc;
     if ((rc = tile_order(c, F, rays)) != VV_OK) return rc;
-    A.rad = c->d_rad; A.rad_out = c->d_rad;
+    A.rad = A.rad_out = (float *)c->scratch[SC_RAD].p;
     A.counter = c->d_counter;
 
     F.whole = P.count <= 1 && P.rb == 0 && P.re == P.nby && W >= 2 && H >= 2;
     const FrameImage images[4] = {
-        {rgba_out,  4,  &c->d_frame, &c->frame_cap, 4,  "vv_render: output buffer must be 4-byte aligned", nullptr},
-        {index_out, 1,  &c->d_index, &c->index_cap, 1,  "", nullptr},
-        {hit_out,   16, &c->d_hit,   &c->hit_cap,   16, "vv_render_iso: a device hit_out must be 16-byte aligned", nullptr},                  // (iso_kernel writes a record in one store)
-        {stat_out,  8,  &c->d_stat,  &c->stat_cap,  8,  "vv_render_projection: a device stat_out must be 8-byte aligned", nullptr},          // (proj_kernel likewise)
+        {rgba_out,  4,  SC_FRAME, 4,  "vv_render: output buffer must be 4-byte aligned", nullptr},
+        {index_out, 1,  SC_INDEX, 1,  "", nullptr},
+        {hit_out,   16, SC_HIT,   16, "vv_render_iso: a device hit_out must be 16-byte aligned", nullptr},                  // (iso_kernel writes a record in one store)
+        {stat_out,  8,  SC_STAT,  8,  "vv_render_projection: a device stat_out must be 8-byte aligned", nullptr},          // (proj_kernel likewise)
     };
     memcpy(F.img, images, sizeof images);
     if ((rc = stage_images(c, F, out_on_device)) != VV_OK) return rc;
@@ -1419,34 +1497,17 @@ int vv_classify_indices(vv_context *c, const uint8_t *index, size_t n, const flo
     if (!index || !rgba_out) return fail(c, VV_ERR_INVALID, "vv_classify_indices: NULL argument");
     if (!tf && !c->have_tf) return fail(c, VV_ERR_NO_VOLUME, "vv_classify_indices: no transfer function loaded");
     if (tf) for (int i = 0; i < 1024; ++i) if (!std::isfinite(tf[i])) return fail(c, VV_ERR_INVALID, "vv_classify_indices: transfer function must be finite");
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = pick_stream(c, stream);
-    const float4 *d_tf = c->d_tf;
-    if (tf) {
-        if (!c->d_tf_arg) HIPCHK(c, hipMalloc((void **)&c->d_tf_arg, 1024 * sizeof(float)));
-        HIPCHK(c, hipMemcpyAsync(c->d_tf_arg, tf, 1024 * sizeof(float), hipMemcpyHostToDevice, st));
-        d_tf = c->d_tf_arg;
-    }
-    const uint8_t *d_idx = index;
-    uint8_t *d_out = rgba_out;
-    if (!on_device && n) {
-        int rc = ensure(c, (void **)&c->d_index, &c->index_cap, n);
-        if (rc) return rc;
-        rc = ensure(c, (void **)&c->d_frame, &c->frame_cap, n * 4);
-        if (rc) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->d_index, index, n, hipMemcpyHostToDevice, st));
-        d_idx = c->d_index; d_out = c->d_frame;
-    }
-    if (((uintptr_t)d_out & 3) != 0) return fail(c, VV_ERR_INVALID, "vv_classify_indices: output buffer must be 4-byte aligned");
-    launch_mip_classify(d_idx, n, d_tf, (uint32_t *)d_out, st);
-    HIPCHK(c, hipGetLastError());
-    if (!on_device) {
-        if (n) HIPCHK(c, hipMemcpyAsync(rgba_out, d_out, n * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-    } else if (!stream) {
-        HIPCHK(c, hipStreamSynchronize(st));
-    }
-    return VV_OK;
+    hipStream_t st;
+    CallBuf b[3] = {
+        {(void *)tf,    tf ? 1024 * sizeof(float) : 0, true, true, false, SC_TF_ARG, nullptr, nullptr},     // (the caller's table is on the host whatever on_device says)
+        {(void *)index, n,     !on_device, true,  false, SC_INDEX, nullptr, nullptr},
+        {rgba_out,      n * 4, !on_device, false, true,  SC_FRAME, nullptr, nullptr},
+    };
+    int rc = stage_call(c, stream, &st, b, 3);
+    if (rc) return rc;
+    if (((uintptr_t)b[2].dev & 3) != 0) return fail(c, VV_ERR_INVALID, "vv_classify_indices: output buffer must be 4-byte aligned");
+    launch_mip_classify((const uint8_t *)b[1].dev, n, tf ? (const float4 *)b[0].dev : c->d_tf, (uint32_t *)b[2].dev, st);
+    return finish_call(c, stream, st, b, 3);
 }
 
 // ---- first pass images ------------------------------------------------------------------
@@ -1458,8 +1519,6 @@ int vv_first_pass(vv_context *c, int W, int H, const camera_params *cam, const v
     if (rays->mode != VV_RAYS_ANALYTIC) return fail(c, VV_ERR_INVALID, "vv_first_pass: needs an analytic ray source");
     for (int a = 0; a < 3; ++a)
         if (!(cam->scale[a] > 0.f) || !std::isfinite(cam->scale[a])) return fail(c, VV_ERR_INVALID, "vv_first_pass: camera scale must be finite and > 0");
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = pick_stream(c, stream);
     FrameParams P;
     memset(&P, 0, sizeof P);
     P.W = W; P.H = H;
@@ -1467,21 +1526,12 @@ int vv_first_pass(vv_context *c, int W, int H, const camera_params *cam, const v
     int rc = camera_basis(c, P, cam, rays, W, H);
     if (rc) return rc;
     const size_t ib = (size_t)W * H * 4;
-    uint8_t *df = front, *db = back;
-    if (!out_on_device) {
-        rc = ensure(c, (void **)&c->d_img, &c->img_cap, 2 * ib);
-        if (rc) return rc;
-        df = c->d_img; db = c->d_img + ib;
-    }
-    if (((uintptr_t)df & 3) || ((uintptr_t)db & 3)) return fail(c, VV_ERR_INVALID, "vv_first_pass: images must be 4-byte aligned");
-    launch_first_pass(P, (uint32_t *)df, (uint32_t *)db, st);
-    HIPCHK(c, hipGetLastError());
-    if (!out_on_device) {
-        HIPCHK(c, hipMemcpyAsync(front, df, ib, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemcpyAsync(back, db, ib, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-    } else if (!stream) HIPCHK(c, hipStreamSynchronize(st));
-    return VV_OK;
+    hipStream_t st;
+    CallBuf b[2] = {{front, ib, !out_on_device, false, true, SC_IMG, nullptr, nullptr}, {back, ib, !out_on_device, false, true, SC_IMG, nullptr, nullptr}};
+    if ((rc = stage_call(c, stream, &st, b, 2)) != VV_OK) return rc;
+    if (((uintptr_t)b[0].dev & 3) || ((uintptr_t)b[1].dev & 3)) return fail(c, VV_ERR_INVALID, "vv_first_pass: images must be 4-byte aligned");
+    launch_first_pass(P, (uint32_t *)b[0].dev, (uint32_t *)b[1].dev, st);
+    return finish_call(c, stream, st, b, 2);
 }
 
 int vv_debug_screen_rect(int W, int H, const camera_params *cam, const vv_ray_source *rays, double out[4])
@@ -1533,44 +1583,54 @@ unsigned long long vv_last_sample_count(vv_context *c)
 }
 
 // ---- slice view: invoke_slice_kernel / invoke_advanced_slice_kernel, kernel.cu:506-541 ----
+extern "C++" {
+// SliceArgs and SlabArgs name the image, the position and the filter alike: the fields of either that the four entry points share.  `trans`: the matrix of the
+// free-form views, or null for a canonical view at (dx, dy, dz) in `orientation`.
+template <class Args>
+static Args slice_args(size_t height, size_t width, float dx, float dy, float dz, int orientation, const float *trans, const float scale[3], int filter)
+{
+    Args S; memset(&S, 0, sizeof S);
+    S.height = height; S.width = width; S.dx = dx; S.dy = dy; S.dz = dz;
+    S.orientation = orientation; S.advanced = trans != nullptr;
+    S.tex8 = filter != VV_FILTER_EXACT;
+    for (int a = 0; a < 3; ++a) S.scale[a] = scale[a];
+    if (trans) memcpy(S.trans, trans, 16 * sizeof(float));
+    return S;
+}
+static bool slice_size_ok(size_t height, size_t width) { return height >= 1 && width >= 1 && height <= 65535u * 16 && width <= 65535u * 16; }
+
+// Runs slice_kernel or slab_kernel (`launch`: gets the device images and the stream) on the loaded volume: one image, or image + aux.  Host images go
+// through the slice scratch (instead of the reference's cudaMalloc / cudaFree per call, kernel.cu:508-518), one after the other, and are uploaded
+// first: elements the kernel skips keep the caller's bytes.
+template <class Args, class Launch>
+static int run_planar(vv_context *c, Args &S, float *buffer, int32_t *aux, int out_on_device, void *stream, Launch launch)
+{
+    const size_t bytes = S.height * S.width * sizeof(float);        // of either image
+    S.V = view_of(c, MB_LINEAR); S.V_type = c->vtype;
+    hipStream_t st;
+    CallBuf b[2] = {{buffer, bytes, !out_on_device, true, true, SC_SLICE, nullptr, nullptr}, {aux, aux ? bytes : 0, !out_on_device, true, true, SC_SLICE, nullptr, nullptr}};
+    int rc = stage_call(c, stream, &st, b, 2);
+    if (rc) return rc;
+    launch((float *)b[0].dev, (int32_t *)b[1].dev, st);
+    return finish_call(c, stream, st, b, 2);
+}
+} // extern "C++"
+
 static int run_slice(vv_context *c, SliceArgs &S, float *buffer, int out_on_device, void *stream)
 {
     if (!c) return fail(nullptr, VV_ERR_INVALID, "vv_slice: NULL context");
     if (!buffer) return fail(c, VV_ERR_INVALID, "vv_slice: NULL buffer");
     if (!c->d_vol) return fail(c, VV_ERR_NO_VOLUME, "vv_slice: no volume loaded");
-    if (S.height < 1 || S.width < 1 || S.height > 65535u * 16 || S.width > 65535u * 16)
-        return fail(c, VV_ERR_INVALID, "vv_slice: bad buffer size");
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = pick_stream(c, stream);
-    const size_t bytes = S.height * S.width * sizeof(float);
-    S.V = view_of(c, MB_LINEAR); S.V_type = c->vtype;
-    float *d = buffer;
-    if (!out_on_device) {
-        // persistent scratch instead of the reference's cudaMalloc/cudaFree per call (kernel.cu:508-518)
-        int rc = ensure(c, (void **)&c->d_slice, &c->slice_cap, bytes);
-        if (rc) return rc;
-        d = c->d_slice;
-        HIPCHK(c, hipMemcpyAsync(d, buffer, bytes, hipMemcpyHostToDevice, st));   // elements the kernel skips keep caller bytes
-    }
-    S.buffer = d;
-    launch_slice(S, st);
-    HIPCHK(c, hipGetLastError());
-    if (!out_on_device) {
-        HIPCHK(c, hipMemcpyAsync(buffer, d, bytes, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-    } else if (!stream) HIPCHK(c, hipStreamSynchronize(st));
-    return VV_OK;
+    if (!slice_size_ok(S.height, S.width)) return fail(c, VV_ERR_INVALID, "vv_slice: bad buffer size");
+    return run_planar(c, S, buffer, nullptr, out_on_device, stream, [&S](float *d, int32_t *, hipStream_t st) { S.buffer = d; launch_slice(S, st); });
 }
 
 int vv_slice(vv_context *c, float *buffer, size_t height, size_t width, float dx, float dy, float dz,
              int orientation, const float scale[3], int legacy, int filter, int out_on_device, void *stream)
 {
     if (!scale) return fail(c, VV_ERR_INVALID, "vv_slice: NULL scale");
-    SliceArgs S; memset(&S, 0, sizeof S);
-    S.height = height; S.width = width; S.dx = dx; S.dy = dy; S.dz = dz;
-    S.orientation = orientation; S.legacy = legacy; S.advanced = 0;
-    S.tex8 = filter != VV_FILTER_EXACT;
-    for (int a = 0; a < 3; ++a) S.scale[a] = scale[a];
+    SliceArgs S = slice_args<SliceArgs>(height, width, dx, dy, dz, orientation, nullptr, scale, filter);
+    S.legacy = legacy;
     return run_slice(c, S, buffer, out_on_device, stream);
 }
 
@@ -1578,11 +1638,7 @@ int vv_slice_advanced(vv_context *c, float *buffer, size_t height, size_t width,
                       const float scale[3], int filter, int out_on_device, void *stream)
 {
     if (!scale || !trans) return fail(c, VV_ERR_INVALID, "vv_slice_advanced: NULL argument");
-    SliceArgs S; memset(&S, 0, sizeof S);
-    S.height = height; S.width = width; S.advanced = 1;
-    S.tex8 = filter != VV_FILTER_EXACT;
-    for (int a = 0; a < 3; ++a) S.scale[a] = scale[a];
-    memcpy(S.trans, trans, 16 * sizeof(float));
+    SliceArgs S = slice_args<SliceArgs>(height, width, 0.f, 0.f, 0.f, 0, trans, scale, filter);
     return run_slice(c, S, buffer, out_on_device, stream);
 }
 
@@ -1594,36 +1650,11 @@ static int run_slab(vv_context *c, SlabArgs &S, float *buffer, int32_t *aux, con
         return fail(c, VV_ERR_INVALID, "vv_slice_slab: mode must be VV_SLAB_MAX, VV_SLAB_MIN or VV_SLAB_MEAN");
     if (slab->samples < 1 || slab->samples > VV_SLAB_MAX_SAMPLES) return fail(c, VV_ERR_INVALID, "vv_slice_slab: samples must lie in 1..1024");
     if (!(slab->thickness >= 0.f) || !std::isfinite(slab->thickness)) return fail(c, VV_ERR_INVALID, "vv_slice_slab: thickness must be finite and >= 0");
-    if (S.height < 1 || S.width < 1 || S.height > 65535u * 16 || S.width > 65535u * 16)
-        return fail(c, VV_ERR_INVALID, "vv_slice_slab: bad buffer size");
+    if (!slice_size_ok(S.height, S.width)) return fail(c, VV_ERR_INVALID, "vv_slice_slab: bad buffer size");
     if (out_on_device && ((uintptr_t)aux & 3) != 0) return fail(c, VV_ERR_INVALID, "vv_slice_slab: a device aux must be 4-byte aligned");
     if (!c->d_vol) return fail(c, VV_ERR_NO_VOLUME, "vv_slice_slab: no volume loaded");
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = pick_stream(c, stream);
-    const size_t bytes = S.height * S.width * sizeof(float);        // of either image
-    S.V = view_of(c, MB_LINEAR); S.V_type = c->vtype;
     S.mode = slab->mode; S.samples = slab->samples; S.thickness = slab->thickness;
-    float *d = buffer; int32_t *da = aux;
-    if (!out_on_device) {
-        // both images in the slice scratch; elements the kernel skips keep the caller's bytes, as in run_slice
-        int rc = ensure(c, (void **)&c->d_slice, &c->slice_cap, aux ? 2 * bytes : bytes);
-        if (rc) return rc;
-        d = c->d_slice;
-        HIPCHK(c, hipMemcpyAsync(d, buffer, bytes, hipMemcpyHostToDevice, st));
-        if (aux) {
-            da = (int32_t *)(c->d_slice + S.height * S.width);
-            HIPCHK(c, hipMemcpyAsync(da, aux, bytes, hipMemcpyHostToDevice, st));
-        }
-    }
-    S.buffer = d; S.aux = da;
-    launch_slab(S, st);
-    HIPCHK(c, hipGetLastError());
-    if (!out_on_device) {
-        HIPCHK(c, hipMemcpyAsync(buffer, d, bytes, hipMemcpyDeviceToHost, st));
-        if (aux) HIPCHK(c, hipMemcpyAsync(aux, da, bytes, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-    } else if (!stream) HIPCHK(c, hipStreamSynchronize(st));
-    return VV_OK;
+    return run_planar(c, S, buffer, aux, out_on_device, stream, [&S](float *d, int32_t *da, hipStream_t st) { S.buffer = d; S.aux = da; launch_slab(S, st); });
 }
 
 int vv_slice_slab(vv_context *c, float *buffer, int32_t *aux, size_t height, size_t width, float dx, float dy, float dz,
@@ -1633,11 +1664,7 @@ int vv_slice_slab(vv_context *c, float *buffer, int32_t *aux, size_t height, siz
     if (!scale || !slab) return fail(c, VV_ERR_INVALID, "vv_slice_slab: NULL argument");
     if (orientation != VV_SAGITTAL && orientation != VV_HORIZONTAL && orientation != VV_CORONAL)
         return fail(c, VV_ERR_INVALID, "vv_slice_slab: orientation must be VV_SAGITTAL, VV_HORIZONTAL or VV_CORONAL");
-    SlabArgs S; memset(&S, 0, sizeof S);
-    S.height = height; S.width = width; S.dx = dx; S.dy = dy; S.dz = dz;
-    S.orientation = orientation; S.advanced = 0;
-    S.tex8 = filter != VV_FILTER_EXACT;
-    for (int a = 0; a < 3; ++a) S.scale[a] = scale[a];
+    SlabArgs S = slice_args<SlabArgs>(height, width, dx, dy, dz, orientation, nullptr, scale, filter);
     return run_slab(c, S, buffer, aux, slab, out_on_device, stream);
 }
 
@@ -1646,22 +1673,17 @@ int vv_slice_advanced_slab(vv_context *c, float *buffer, int32_t *aux, size_t he
 {
     if (!c) return fail(nullptr, VV_ERR_INVALID, "vv_slice_advanced_slab: NULL context");
     if (!scale || !trans || !slab) return fail(c, VV_ERR_INVALID, "vv_slice_advanced_slab: NULL argument");
-    SlabArgs S; memset(&S, 0, sizeof S);
-    S.height = height; S.width = width; S.advanced = 1; S.orientation = VV_SAGITTAL;
-    S.tex8 = filter != VV_FILTER_EXACT;
-    for (int a = 0; a < 3; ++a) S.scale[a] = scale[a];
-    memcpy(S.trans, trans, 16 * sizeof(float));
+    SlabArgs S = slice_args<SlabArgs>(height, width, 0.f, 0.f, 0.f, VV_SAGITTAL, trans, scale, filter);
     return run_slab(c, S, buffer, aux, slab, out_on_device, stream);
 }
 
 // ---- histograms (include/volviz.h: vv_volume_histogram) ------------------------------------
-// accumulator zeroed, counted (unless there is nothing to count), turned into `out` / `counts`: all on `st`
+// accumulator zeroed, counted (unless there is nothing to count), turned into `out` / `counts`: all on `st` (finish_call checks the launches)
 static int run_hist(vv_context *c, const HistRuns *runs, int vtype, unsigned long long voxels, vv_histogram *d_out, unsigned long long *d_counts, hipStream_t st)
 {
     HIPCHK(c, hipMemsetAsync(c->d_hist, 0, kHistAccWords * sizeof(unsigned long long), st));
     if (runs) launch_hist(*runs, c->n_cu, c->knobs.hist_blocks, c->d_hist, st);
     launch_hist_finish(c->d_hist, vtype, voxels, d_out, d_counts, st);
-    HIPCHK(c, hipGetLastError());
     return VV_OK;
 }
 
@@ -1679,8 +1701,10 @@ int vv_volume_histogram(vv_context *c, const int box_lo[3], const int box_hi[3],
             lo[a] = box_lo[a]; hi[a] = box_hi[a];
             if (!(0 <= lo[a] && lo[a] < hi[a] && hi[a] <= dims[a])) return fail(c, VV_ERR_INVALID, "vv_volume_histogram: the box must satisfy 0 <= lo < hi <= dims on every axis");
         }
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = pick_stream(c, stream);
+    hipStream_t st;
+    CallBuf b = {out, sizeof(vv_histogram), !out_on_device, false, true, 0, (char *)c->d_hist + kHistResultOffset, nullptr};
+    int rc = stage_call(c, stream, &st, &b, 1);
+    if (rc) return rc;
     // the box as runs of the linear layout: its rows; whole slices of it where the rows are dense and taken whole; the whole box where the slices are too
     const size_t size = c->vtype == VV_VOXEL_F32 ? 4 : 1;
     const size_t bx = (size_t)(hi[0] - lo[0]), by = (size_t)(hi[1] - lo[1]), bz = (size_t)(hi[2] - lo[2]);
@@ -1697,14 +1721,8 @@ int vv_volume_histogram(vv_context *c, const int box_lo[3], const int box_hi[3],
     // what launch_hist is promised: the last voxel of the box lies inside the volume, which ends more than 16 bytes before its allocation does
     const size_t last = (size_t)(hi[2] - 1) * c->slice_pitch + (size_t)(hi[1] - 1) * c->row_pitch + (size_t)hi[0] * size;
     if (((uintptr_t)c->d_vol & 15) != 0 || last + 16 > c->alloc_bytes) return fail(c, VV_ERR_DEVICE, "vv_volume_histogram: volume allocation is not what the kernel expects");
-    vv_histogram *d_out = out_on_device ? out : (vv_histogram *)((char *)c->d_hist + kHistResultOffset);
-    int rc = run_hist(c, &R, c->vtype, (unsigned long long)(bx * by * bz), d_out, nullptr, st);
-    if (rc) return rc;
-    if (!out_on_device) {
-        HIPCHK(c, hipMemcpyAsync(out, d_out, sizeof(vv_histogram), hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-    } else if (!stream) HIPCHK(c, hipStreamSynchronize(st));
-    return VV_OK;
+    if ((rc = run_hist(c, &R, c->vtype, (unsigned long long)(bx * by * bz), (vv_histogram *)b.dev, nullptr, st)) != VV_OK) return rc;
+    return finish_call(c, stream, st, &b, 1);
 }
 
 int vv_histogram_indices(vv_context *c, const uint8_t *index, size_t n, unsigned long long counts[256], int on_device, void *stream)
@@ -1712,35 +1730,49 @@ int vv_histogram_indices(vv_context *c, const uint8_t *index, size_t n, unsigned
     if (!c) return fail(nullptr, VV_ERR_INVALID, "vv_histogram_indices: NULL context");
     if (!counts || (!index && n)) return fail(c, VV_ERR_INVALID, "vv_histogram_indices: NULL argument");
     if (on_device && ((uintptr_t)counts & 7) != 0) return fail(c, VV_ERR_INVALID, "vv_histogram_indices: device counts must be 8-byte aligned");
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = pick_stream(c, stream);
-    const uint8_t *d_idx = index;
-    unsigned long long *d_counts = counts;
-    if (!on_device) {
-        if (n) {
-            int rc = ensure(c, (void **)&c->d_index, &c->index_cap, n);
-            if (rc) return rc;
-            HIPCHK(c, hipMemcpyAsync(c->d_index, index, n, hipMemcpyHostToDevice, st));
-            d_idx = c->d_index;
-        }
-        d_counts = (unsigned long long *)((char *)c->d_hist + kHistResultOffset);
-    }
+    hipStream_t st;
+    CallBuf b[2] = {
+        {(void *)index, n, !on_device, true, false, SC_INDEX, nullptr, nullptr},
+        {counts, 256 * sizeof(unsigned long long), !on_device, false, true, 0, (char *)c->d_hist + kHistResultOffset, nullptr},
+    };
+    int rc = stage_call(c, stream, &st, b, 2);
+    if (rc) return rc;
     HistRuns R;
     memset(&R, 0, sizeof R);
-    R.data0 = d_idx; R.vtype = VV_VOXEL_U8; R.tight = 1;          // one run of n bytes in a buffer whose surroundings are not ours to read
+    R.data0 = b[0].dev; R.vtype = VV_VOXEL_U8; R.tight = 1;          // one run of n bytes in a buffer whose surroundings are not ours to read
     R.run_voxels = n; R.rps = 1; R.n_slices = 1;
-    int rc = run_hist(c, n ? &R : nullptr, VV_VOXEL_U8, n, nullptr, d_counts, st);
-    if (rc) return rc;
-    if (!on_device) {
-        HIPCHK(c, hipMemcpyAsync(counts, d_counts, 256 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-    } else if (!stream) HIPCHK(c, hipStreamSynchronize(st));
-    return VV_OK;
+    if ((rc = run_hist(c, n ? &R : nullptr, VV_VOXEL_U8, n, nullptr, (unsigned long long *)b[1].dev, st)) != VV_OK) return rc;
+    return finish_call(c, stream, st, b, 2);
 }
 
 // ---- generator: VolumeGenerator::drawEllipsoid / drawDefaultBrain ------------------------
 static int generate_impl(vv_context *c, uint8_t *out, int out_on_device, int nx, int ny, int nz, int n,
-                         const float *centers, const float *axes, const uint8_t *colors, int in_place, void *stream);
+                         const float *centers, const float *axes, const uint8_t *colors, int in_place, void *stream)
+{
+    if (!c) return fail(nullptr, VV_ERR_INVALID, "vv_generate_ellipsoids: NULL context");
+    if (!out || nx < 1 || ny < 1 || nz < 1 || n < 0 || n > kMaxEllipsoids || (n > 0 && (!centers || !axes || !colors)))
+        return fail(c, VV_ERR_INVALID, "vv_generate_ellipsoids: bad argument (n <= 64)");
+    if ((((unsigned long long)nx + 15ull) / 16ull) * (unsigned long long)ny >= (1ull << 31))
+        return fail(c, VV_ERR_INVALID, "vv_generate_ellipsoids: a slice must have fewer than 2^31 16-voxel chunks");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = pick_stream(c, stream);
+    // A host volume goes through a device buffer of this call's own, not through the scratch table: a volume-sized buffer must not stay resident in the
+    // context.  Freed on every path below; the download and the wait are finish_call's.
+    CallBuf b = {out, (size_t)nx * ny * nz, !out_on_device, in_place != 0, true, 0, nullptr, out};
+    void *tmp = nullptr;
+    if (b.host) {
+        HIPCHK(c, hipMalloc(&tmp, b.bytes)); b.dev = tmp;
+        if (b.in && hipMemcpyAsync(b.dev, out, b.bytes, hipMemcpyHostToDevice, st) != hipSuccess) { hipFree(tmp); return fail(c, VV_ERR_DEVICE, "vv_draw_ellipsoid: upload failed"); }
+    }
+    int rc = ((uintptr_t)b.dev & 15) != 0 ? fail(c, VV_ERR_INVALID, "vv_generate_ellipsoids: device buffer must be 16-byte aligned") : VV_OK;
+    if (!rc) rc = ensure(c, SC_GEN, generate_scratch_floats(nx, ny, nz, n) * sizeof(float));
+    if (!rc) {
+        launch_generate_ellipsoids((uint8_t *)b.dev, nx, ny, nz, n, centers, axes, colors, in_place, (float *)c->scratch[SC_GEN].p, st);
+        rc = finish_call(c, stream, st, &b, 1);
+    }
+    if (tmp) hipFree(tmp);
+    return rc;
+}
 
 int vv_generate_ellipsoids(vv_context *c, uint8_t *out, int out_on_device, int nx, int ny, int nz, int n,
                            const float *centers, const float *axes, const uint8_t *colors, void *stream)
@@ -1752,37 +1784,6 @@ int vv_draw_ellipsoid(vv_context *c, uint8_t *vol, int vol_on_device, int nx, in
                       const float center[3], const float axes[3], uint8_t color, void *stream)
 {
     return generate_impl(c, vol, vol_on_device, nx, ny, nz, 1, center, axes, &color, 1, stream);
-}
-
-static int generate_impl(vv_context *c, uint8_t *out, int out_on_device, int nx, int ny, int nz, int n,
-                         const float *centers, const float *axes, const uint8_t *colors, int in_place, void *stream)
-{
-    if (!c) return fail(nullptr, VV_ERR_INVALID, "vv_generate_ellipsoids: NULL context");
-    if (!out || nx < 1 || ny < 1 || nz < 1 || n < 0 || n > kMaxEllipsoids || (n > 0 && (!centers || !axes || !colors)))
-        return fail(c, VV_ERR_INVALID, "vv_generate_ellipsoids: bad argument (n <= 64)");
-    if ((((unsigned long long)nx + 15ull) / 16ull) * (unsigned long long)ny >= (1ull << 31))
-        return fail(c, VV_ERR_INVALID, "vv_generate_ellipsoids: a slice must have fewer than 2^31 16-voxel chunks");
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = pick_stream(c, stream);
-    const size_t bytes = (size_t)nx * ny * nz;
-    uint8_t *d = out;
-    void *tmp = nullptr;
-    if (!out_on_device) {
-        HIPCHK(c, hipMalloc(&tmp, bytes)); d = (uint8_t *)tmp;
-        if (in_place && hipMemcpyAsync(d, out, bytes, hipMemcpyHostToDevice, st) != hipSuccess) { hipFree(tmp); return fail(c, VV_ERR_DEVICE, "vv_draw_ellipsoid: upload failed"); }
-    }
-    if (((uintptr_t)d & 15) != 0) { if (tmp) hipFree(tmp); return fail(c, VV_ERR_INVALID, "vv_generate_ellipsoids: device buffer must be 16-byte aligned"); }
-    {
-        int rc = ensure(c, (void **)&c->d_gen, &c->gen_cap, generate_scratch_floats(nx, ny, nz, n) * sizeof(float));
-        if (rc) { if (tmp) hipFree(tmp); return rc; }
-    }
-    launch_generate_ellipsoids(d, nx, ny, nz, n, centers, axes, colors, in_place, c->d_gen, st);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess && !out_on_device) e = hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && (!out_on_device || !stream)) e = hipStreamSynchronize(st);
-    if (tmp) hipFree(tmp);
-    if (e != hipSuccess) return fail(c, VV_ERR_DEVICE, std::string("vv_generate_ellipsoids: ") + hipGetErrorString(e));
-    return VV_OK;
 }
 
 int vv_generate_default_brain(vv_context *c, uint8_t *out, int out_on_device, int nx, int ny, int nz, void *stream)
@@ -1808,9 +1809,7 @@ int vv_promote_u8_to_f32(vv_context *c, const uint8_t *dev_in, float *dev_out, s
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = pick_stream(c, stream);
     launch_promote_u8_f32(dev_in, dev_out, n, st);
-    HIPCHK(c, hipGetLastError());
-    if (!stream) HIPCHK(c, hipStreamSynchronize(st));
-    return VV_OK;
+    return finish_call(c, stream, st, nullptr, 0);
 }
 
 int vv_generate_noise_u8(vv_context *c, uint8_t *dev_out, int nx, int ny, int nz, uint32_t seed, void *stream)
@@ -1819,9 +1818,7 @@ int vv_generate_noise_u8(vv_context *c, uint8_t *dev_out, int nx, int ny, int nz
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = pick_stream(c, stream);
     launch_noise_u8(dev_out, nx, ny, nz, seed, st);
-    HIPCHK(c, hipGetLastError());
-    if (!stream) HIPCHK(c, hipStreamSynchronize(st));
-    return VV_OK;
+    return finish_call(c, stream, st, nullptr, 0);
 }
 
 } // extern "C"

@@ -554,9 +554,7 @@ void launch_generate_ellipsoids(uint8_t *out, int nx, int ny, int nz, int n,
     size_t blocks = (total + 255) / 256;
     // blocks of 256 chunks, grid-stride beyond 65536 of them: busy and empty rows mix better over many short blocks (drawDefaultBrain at 1024^3: 1.03 ms with
     // 1024 blocks, 0.50 with 8192, 0.46 with 65536, 0.51 with one block per 256 chunks; the fill alone 0.26 / 0.27 / 0.20 / 0.22 ms)
-    size_t cap = 65536;
-    if (const char *e = getenv("VV_GEN_BLOCKS")) { const long v = atol(e); if (v >= 256) cap = (size_t)v; }     // (experiment knob)
-    if (blocks > cap) blocks = cap;
+    if (blocks > 65536) blocks = 65536;
     if (blocks == 0) return;
     // rows of whole waves (a multiple of 1024 voxels) of a fresh volume take the interval form
     if (!in_place && n > 0 && xchunks % 64 == 0 && nx % 16 == 0) {
@@ -584,8 +582,7 @@ void launch_generate_ellipsoids(uint8_t *out, int nx, int ny, int nz, int n,
         if (rows_ok == 1 && n <= 8 && lds <= 80u * 1024u && segments < (1ull << 28) && (segs == 1 || segs == 2 || segs == 4) && !getenv("VV_GEN_NO_LDS")) {
             int dev = 0, cus = 256;
             if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-            unsigned threads = 1024;
-            if (const char *e = getenv("VV_GEN_THREADS")) { const long v = atol(e); if (v == 256 || v == 512 || v == 1024) threads = (unsigned)v; }   // (experiment knob)
+            const unsigned threads = 1024;
             size_t nb = (size_t)cus * (2048 / threads);
             if (nb > (segments + 15) / 16) nb = (segments + 15) / 16;
             RowsArgs A;
@@ -668,9 +665,8 @@ size_t brick_copy_bytes(int vtype, int nx, int ny, int nz, uint32_t *sy, uint32_
     const size_t nbx = xcol ? (size_t)nx / bxv + 1 : ((size_t)nx + bxv - 1) / bxv, nby = (size_t)ny / 4 + 1, nbz = (size_t)nz / bzv + 1;
     size_t row = nbx * brick;                                     // brick sizes are multiples of 64
     // a row of bricks that is a multiple of 4 KiB gets 64 bytes more (same cache-channel effect as the
-    // linear pitch, smaller: rotated C3 -1...-4 %, + Phong -4 %); VV_BRICK_PAD=<bytes, multiple of 64> / 0 overrides
-    size_t pad = (vtype == VV_VOXEL_F32 && row % 4096 == 0) ? (BrickGeom<VV_VOXEL_F32>::brick % 128 == 0 ? 128 : 64) : 0;      // u8 bricks (one line each): +7 % with it
-    if (const char *e = getenv("VV_BRICK_PAD")) { int t = atoi(e); if (t >= 0 && t <= 4096 && t % 64 == 0) pad = (size_t)t; }
+    // linear pitch, smaller: rotated C3 -1...-4 %, + Phong -4 %)
+    const size_t pad = (vtype == VV_VOXEL_F32 && row % 4096 == 0) ? (BrickGeom<VV_VOXEL_F32>::brick % 128 == 0 ? 128 : 64) : 0;      // u8 bricks (one line each): +7 % with it
     if (nx >= (1 << 20)) { if (sy) *sy = 0xFFFFFFFFu; if (sz64) *sz64 = 0xFFFFFFFFu; return ~(size_t)0 >> 1; }      // (brick_x_offset's range; ensure_bricks then takes the linear path)
     row += pad;
     const size_t layer = nby * row;
@@ -746,8 +742,7 @@ void launch_repitch(const void *dense, void *pitched, size_t row_bytes, size_t n
 size_t zpair_copy_bytes(int vtype, int nx, int ny, int nz, uint32_t *row_bytes, uint32_t *slab_bytes)
 {
     const size_t rec = vtype == VV_VOXEL_F32 ? 8 : 2;
-    size_t row = (((size_t)nx + 1) * rec + 3) & ~(size_t)3;
-    if (const char *e = getenv("VV_ZPAIR_PAD")) { int t = atoi(e); if (t > 0 && t <= 4096 && t % 8 == 0) row += (size_t)t; }   // experiment knob (no effect measured)
+    const size_t row = (((size_t)nx + 1) * rec + 3) & ~(size_t)3;
     const size_t slab = ((size_t)ny + 1) * row;
     if (row_bytes) *row_bytes = (uint32_t)row;
     if (slab_bytes) *slab_bytes = (uint32_t)slab;
