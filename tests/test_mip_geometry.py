@@ -30,8 +30,10 @@ import functools
 import numpy as np
 import pytest
 
+import iso_model as IM
 import mip_oracle as MO
 import oracle_lib as O
+import proj_model as PM
 import volviz_amd as vv
 
 CAM_A = vv.Camera.orbit(3.0, 1.0, 0.6)
@@ -513,3 +515,51 @@ def test_mip_instruments_equal_the_march(ctx, cam, env, code):
     assert np.array_equal(mip[2], march[2]) and mip[2].sum() > 0, (int(mip[2].sum()), int(march[2].sum()))
     assert np.array_equal(mip[3], march[3]) and mip[3].sum() > 0, (int(mip[3].sum()), int(march[3].sum()))
     assert mip[2].sum() >= 0.5 * brick_bits                                                       # the frame sees most of the volume
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("cam,env,code", [(CAM_A, {"VV_BRICKED": "1"}, 2), (CAM_AXIS, {"VV_ZPAIR": "0"}, 0)], ids=["oblique-bricked", "axis-linear"])
+def test_reducer_kinds_instruments_equal_mip(ctx, cam, env, code):
+    """proj_kernel<INSTR> in its three modes and iso_kernel<INSTR> at a level no sample reaches execute the samples of mip_kernel<INSTR>, in its trips:
+    equal counts, equal slots, the same touched bricks and the same touched lines.  (The volume's values are halved: every index stays far below the level.)"""
+    import torch
+    nx, ny, nz = 48, 40, 56
+    vol = np.ascontiguousarray(_f32(O.noise_u8(nx, ny, nz, 3)) * np.float32(0.5))
+    W, H, LEVEL = 120, 90, 200
+    tf = _table()
+    okw = dict(step=1 / 64)
+    n_want = MO.executed_samples(vol, W, H, cam, options_kw=okw)
+    iso = IM.render_cam(vol, tf, W, H, cam, LEVEL, **okw)
+    assert n_want > 0 and iso["count"] == n_want and not iso["index"].any() and np.isnan(iso["shade"]).all(), (n_want, iso["count"])     # no pixel has a hit
+    assert PM.render_cam(vol, tf, W, H, cam, PM.PROJ_MEAN, **okw)["count"] == n_want
+    dev = torch.device("cuda", 0)
+    with MO.knobs(ctx, env):
+        ctx.load_volume(vol, tf)
+        ctx.render_mip(W, H, cam, options=vv.make_options(**okw))                                  # (builds the copy)
+        assert ctx.last_launch()["layout"] == code
+        line_bits = max(ctx.device_bytes()[:3]) // 128 + 64
+        brick_bits = ((nx + 7) // 8) * ((ny + 7) // 8) * ((nz + 7) // 8)
+        rgba = torch.zeros(H * W, dtype=torch.int32, device=dev)
+        index = torch.zeros(H * W, dtype=torch.uint8, device=dev)
+        record = torch.zeros(H * W * 4, dtype=torch.float32, device=dev)                          # the stat image (8 bytes a pixel) or the hit image (16)
+        frames = [("mip", 2, lambda o: ctx.render_mip_device(W, H, cam, rgba.data_ptr(), index.data_ptr(), options=o))]
+        frames += [(f"proj {m}", 4, lambda o, m=m: ctx.render_projection_device(W, H, cam, m, rgba.data_ptr(), index.data_ptr(), record.data_ptr(), options=o))
+                   for m in (vv.PROJ_MAX, vv.PROJ_MIN, vv.PROJ_MEAN)]
+        frames += [("iso", 3, lambda o: ctx.render_iso_device(W, H, cam, LEVEL, rgba.data_ptr(), index.data_ptr(), record.data_ptr(), options=o))]
+        got = {}
+        for kind, phong, call in frames:
+            bricks = torch.zeros((brick_bits + 31) // 32, dtype=torch.int32, device=dev)
+            lines = torch.zeros((line_bits + 31) // 32, dtype=torch.int32, device=dev)
+            torch.cuda.synchronize()
+            call(vv.make_options(count_samples=True, touched_bricks=bricks.data_ptr(), touched_lines=lines.data_ptr(), touched_line_bits=line_bits, **okw))
+            torch.cuda.synchronize()
+            lay = ctx.last_launch()
+            assert lay["layout"] == code and lay["phong"] == phong, (kind, lay)
+            got[kind] = (ctx.last_sample_count(), int(ctx.debug_counters()[1]), np.unpackbits(bricks.cpu().numpy().view(np.uint8)),
+                         np.unpackbits(lines.cpu().numpy().view(np.uint8)))
+    mip = got.pop("mip")
+    assert mip[0] == n_want and mip[1] >= mip[0] and mip[2].sum() >= 0.5 * brick_bits and mip[3].sum() > 0, (mip[0], mip[1], int(mip[2].sum()), int(mip[3].sum()))
+    for kind, g in got.items():
+        print(f"instruments {env} {kind}: samples {g[0]} / {mip[0]}, slots {g[1]} / {mip[1]}, bricks {int(g[2].sum())} / {int(mip[2].sum())}, lines {int(g[3].sum())} / {int(mip[3].sum())}")
+        assert g[0] == mip[0] and g[1] == mip[1], (kind, g[:2], mip[:2])
+        assert np.array_equal(g[2], mip[2]) and np.array_equal(g[3], mip[3]), (kind, int(g[2].sum()), int(mip[2].sum()), int(g[3].sum()), int(mip[3].sum()))

@@ -116,7 +116,7 @@ __device__ __noinline__ void mark_sample_lines(const InstrArgs &I, const VolumeV
 #endif
 }
 
-// Instrumented frames only: one sample of march_kernel / mip_kernel, `live` when its lane executes it.  Counts it, marks its 8^3 bricks when it lies in
+// Instrumented frames only: one sample of march_kernel / mip_kernel / iso_kernel / proj_kernel, `live` when its lane executes it.  Counts it, marks its 8^3 bricks when it lies in
 // the volume, and the lines its gathers touch (InstrArgs::lines_all: those of idle lanes and out-of-volume samples too).
 template <int VOXEL, bool TEX8>
 __device__ __forceinline__ void instrument_sample(const InstrArgs &I, const VolumeView &V, float tx, float ty, float tz, bool live, unsigned long long &executed)
