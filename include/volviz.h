@@ -543,6 +543,14 @@ unsigned long long vv_last_sample_count(vv_context *ctx);        /* executed sam
 int                vv_debug_last_launch(vv_context *ctx, int out[8]);  /* what the launch policy chose for the last vv_render (developer aid): wave tile log2 width,
                                                                        * block log2 width, samples per trip, LDS reserve, layout (0 linear, 1 linear/64-bit, 2 bricked,
                                                                        * 3 z-pair, 4 z-fastest, 5 x-pair), view known to the policy (0 / 1), density x 1000, kernel family (0 unshaded, 1 Phong, 2 MIP: vv_render_mip, 3 isosurface: vv_render_iso, 4 projection: vv_render_projection) */
+/* A resident layout as it lies in HBM (developer aid; what tests/test_footprint.py holds the copy builders and the touched_lines instrument to).
+ * `layout`: the codes of vv_debug_last_launch (0 and 1 name the same allocation).  geom = {allocation bytes, the zeroed bytes behind the layout
+ * included, or 0 when the layout is not resident; row stride; slice stride; nx; ny; nz; voxel type; 0}, the strides being the fields the kernels
+ * address with: row_bytes / slice_bytes of the linear layout, bytes per row of bricks / bytes per layer of bricks in 64-byte units, bytes per row /
+ * per slab of records of a pair copy, bytes per row / per slice of the z-fastest copy.  The allocation is then copied to host_dst (`capacity` bytes),
+ * synchronously on the context's stream; host_dst NULL with capacity 0 asks for the geometry alone.  Builds nothing and changes no state.
+ * Errors: NULL ctx / geom, a layout outside 0..5, a capacity below geom[0]: VV_ERR_INVALID; no volume: VV_ERR_NO_VOLUME.   */
+int                vv_debug_read_layout(vv_context *ctx, int layout, unsigned long long geom[8], void *host_dst, size_t capacity);
 /* The rectangle of pixel coordinates (x_min, x_max, y_min, y_max, margin included) outside of which vv_render lets its pre-pass write (0,0,0,0) instead of
  * marching (analytic ray sources): returns 1 and fills out[4], or 0 when this camera gets no rectangle (a cube corner at or behind the eye's plane, a
  * margin wider than the frame).  Needs no device and no context: tests/test_host.py checks it against the oracle's ray-box test pixel by pixel. */

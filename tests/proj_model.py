@@ -30,26 +30,20 @@ def mean_half_up(s, n):
     return np.where(n > 0, (2 * s + n) // np.maximum(2 * n, 1), 0)
 
 
-def render(vol, tf, W, H, mode, *, cam_origin, look=None, up=(0, 1, 0), fov_y=45.0, scale=(1, 1, 1), aspect=0.0, quantize8=False,
-           images=None, slice_type=SLICE_NONE, plane=(.5, .5, .5, 0, 0, 1), step=None, filt=FILTER_TEX8, slab_rows=(0, 0), shard=None,
-           fill=0):
-    """One projection frame.  Returns a dict: rgba [H, W, 4] uint8, index [H, W] uint8 and stat [H, W, 2] uint32, each over `fill`
-    bytes; written [H, W] bool; count, the samples executed; and, for the tests' own conditions, e and n [H, W] int64 (executed
-    and counted samples per pixel) and ties [H, W] int64 (MAX / MIN: how many counted samples attain the extremum)."""
-    assert mode in (PROJ_MAX, PROJ_MIN, PROJ_MEAN)
-    nz, ny, nx = vol.shape
+def owned_rays(dims, W, H, *, cam_origin, look=None, up=(0, 1, 0), fov_y=45.0, scale=(1, 1, 1), aspect=0.0, quantize8=False, images=None,
+               slice_type=SLICE_NONE, plane=(.5, .5, .5, 0, 0, 1), step=None, slab_rows=(0, 0), shard=None):
+    """The rays of a reducer frame over a volume of dims (nx, ny, nz) that march -- those whose slab writes their pixel -- after the witness's
+    set-up, and 1 / scale; (None, None) for a frame without rays.  A highlighted plane (SLICE_PLANE) is ignored, as the reducer frames do."""
+    nx, ny, nz = dims
     if step is None or not np.any(np.asarray(step, f32) != 0):
         step = f32(1) / np.array([nx, ny, nz], f32)
     else:
         step = np.asarray([step] * 3 if np.isscalar(step) else step, f32)
     if slice_type == SLICE_PLANE:
         slice_type = SLICE_NONE
-    out = dict(rgba=np.full((H, W, 4), fill, np.uint8), index=np.full((H, W), fill, np.uint8),
-               stat=np.full((H, W, 8), fill, np.uint8).view(np.uint32), written=np.zeros((H, W), bool), count=0,
-               e=np.zeros((H, W), np.int64), n=np.zeros((H, W), np.int64), ties=np.zeros((H, W), np.int64))
     R = frame_rays(W, H, slab_rows, shard)
     if len(R["x"]) == 0:
-        return out
+        return None, None
     if images is not None:
         front, back = image_endpoints(W, H, R["x"], R["y"], images[0], images[1])
     else:
@@ -57,16 +51,13 @@ def render(vol, tf, W, H, mode, *, cam_origin, look=None, up=(0, 1, 0), fov_y=45
             look = -np.asarray(cam_origin, f32)
         front, back = analytic_endpoints(W, H, R["x"], R["y"], cam_origin, look, up, fov_y, scale, aspect, quantize8)
     setup(R, front, back, cam_origin, step, slice_type, plane)
-    inv_scale = f32(1) / np.asarray(scale, f32)
     own = R["owned"]
-    R = {k: v[own] for k, v in R.items()}                      # the radius is the slab's (set-up saw every ray); only owned rays march
-    rays = len(R["x"])
-    e = np.zeros(rays, np.int64)                                # executed samples so far
-    n = np.zeros(rays, np.int64)                                # counted samples so far
-    s = np.zeros(rays, np.int64)                                # MEAN: their sum
-    ext = np.zeros(rays, np.int64)                              # MAX / MIN: the extremum so far (meaningful where n > 0),
-    ordinal = np.zeros(rays, np.int64)                          # the ordinal of the first sample that attained it,
-    ties = np.zeros(rays, np.int64)                             # and how many counted samples equal it
+    return {k: v[own] for k, v in R.items()}, f32(1) / np.asarray(scale, f32)      # the radius is the slab's (set-up saw every ray); only owned rays march
+
+
+def march(R, inv_scale):
+    """The march loop of a reducer frame over the rays R, chunk by chunk: yields (act, t, runs) -- the indices of the rays that start the chunk, the
+    texture coordinates [len(act), 30, 3] of its samples and which of them are executed [len(act), 30] (a prefix of the chunk).  No ray ends early."""
     dist = R["dist0"].copy()
     alive = ~R["dead"] & ~R["cut"]
     with np.errstate(all="ignore"):
@@ -83,7 +74,34 @@ def render(vol, tf, W, H, mode, *, cam_origin, look=None, up=(0, 1, 0), fov_y=45
             i1 = np.arange(1, SAMPLES + 1, dtype=f32)[None, :]
             stop = (i1 * sstep[:, None] + d[:, None]) > upper[:, None]           # the sample is executed unless this, or an earlier one, holds
             runs = np.cumsum(stop, axis=1) == 0
-            t = _to_tex(pos, inv_scale)
+            yield act, _to_tex(pos, inv_scale), runs
+            dist[act] = d + sstep * f32(SAMPLES)
+
+
+def render(vol, tf, W, H, mode, *, cam_origin, look=None, up=(0, 1, 0), fov_y=45.0, scale=(1, 1, 1), aspect=0.0, quantize8=False,
+           images=None, slice_type=SLICE_NONE, plane=(.5, .5, .5, 0, 0, 1), step=None, filt=FILTER_TEX8, slab_rows=(0, 0), shard=None,
+           fill=0):
+    """One projection frame.  Returns a dict: rgba [H, W, 4] uint8, index [H, W] uint8 and stat [H, W, 2] uint32, each over `fill`
+    bytes; written [H, W] bool; count, the samples executed; and, for the tests' own conditions, e and n [H, W] int64 (executed
+    and counted samples per pixel) and ties [H, W] int64 (MAX / MIN: how many counted samples attain the extremum)."""
+    assert mode in (PROJ_MAX, PROJ_MIN, PROJ_MEAN)
+    nz, ny, nx = vol.shape
+    out = dict(rgba=np.full((H, W, 4), fill, np.uint8), index=np.full((H, W), fill, np.uint8),
+               stat=np.full((H, W, 8), fill, np.uint8).view(np.uint32), written=np.zeros((H, W), bool), count=0,
+               e=np.zeros((H, W), np.int64), n=np.zeros((H, W), np.int64), ties=np.zeros((H, W), np.int64))
+    R, inv_scale = owned_rays((nx, ny, nz), W, H, cam_origin=cam_origin, look=look, up=up, fov_y=fov_y, scale=scale, aspect=aspect, quantize8=quantize8,
+                              images=images, slice_type=slice_type, plane=plane, step=step, slab_rows=slab_rows, shard=shard)
+    if R is None:
+        return out
+    rays = len(R["x"])
+    e = np.zeros(rays, np.int64)                                # executed samples so far
+    n = np.zeros(rays, np.int64)                                # counted samples so far
+    s = np.zeros(rays, np.int64)                                # MEAN: their sum
+    ext = np.zeros(rays, np.int64)                              # MAX / MIN: the extremum so far (meaningful where n > 0),
+    ordinal = np.zeros(rays, np.int64)                          # the ordinal of the first sample that attained it,
+    ties = np.zeros(rays, np.int64)                             # and how many counted samples equal it
+    with np.errstate(all="ignore"):
+        for act, t, runs in march(R, inv_scale):
             k = classify(vol, t, filt).astype(np.int64)
             counted = runs & _in_bounds(t)
             for i in range(SAMPLES):                            # march order: a later sample replaces only if strictly better
@@ -100,7 +118,6 @@ def render(vol, tf, W, H, mode, *, cam_origin, look=None, up=(0, 1, 0), fov_y=45
                     ties[a] = np.where(new, 1, ties[a] + same)
                 n[a] += c
             e[act] += runs.sum(axis=1)
-            dist[act] = d + sstep * f32(SAMPLES)
     if mode == PROJ_MEAN:
         v = mean_half_up(s, n)
         first_word = np.where(n > 0, s, 0)

@@ -18,8 +18,10 @@ import os
 import numpy as np
 import pytest
 
+import footprint_model as FM
 import oracle_lib as O
 import volviz_amd as vv
+import witness as Wt
 from golden.make_fixtures import ellipsoid_cases, frame_cases, PLANE_POINT, PLANE_NORMAL
 
 pytestmark = pytest.mark.gpu
@@ -1288,12 +1290,30 @@ def test_touched_lines_instrument(ctx, monkeypatch):
     import torch
     n = 32
     vol = O.noise_u8(n, n, n, 3).astype(np.float32) / np.float32(255)
-    tf = vv.transfer_preset(vv.TF_HEAD)                        # low opacity: no ray terminates early
+    tf = vv.transfer_preset(vv.TF_HEAD)                        # low opacity: few rays terminate early
     W = H = 300
     cam = vv.Camera(origin=(0.0, 0.0, -3.0))
     dev = torch.device("cuda", 0)
     frame = torch.zeros(H * W, dtype=torch.int32, device=dev)
     counts = {}
+
+    class LineModel:
+        """tests/footprint_model.py over the frame's executed samples -- the witness's own march, since some rays of this table do pass the threshold --:
+        the compulsory lines of both layouts, accumulated chunk by chunk."""
+        def __init__(self):
+            self.count = 0
+            self.geom = {k: FM.dense_geom(k, vol.dtype, (n, n, n)) for k in ("linear", "bricked")}
+            self.bits = {k: g["alloc"] // 128 + 64 for k, g in self.geom.items()}
+            self.words = {k: np.zeros((b + 31) // 32, np.uint32) for k, b in self.bits.items()}
+
+        def __call__(self, tex, ran, started):
+            t = tex[ran]
+            self.count += len(t)
+            for k in self.words:
+                self.words[k] |= FM.lines(t, k, vol.dtype, self.geom[k], (n, n, n), self.bits[k])
+    model = LineModel()
+    _, model_count = Wt.render(vol, tf, W, H, cam_origin=cam.origin, look=cam.look(), up=cam.up, fov_y=cam.fov_y, scale=cam.scale, step=1 / 128, visit=model)
+    assert model_count == model.count
     monkeypatch.setenv("VV_ZPAIR", "0")                        # (the policy would give this small unshaded front view the z-pair copy)
     for env in ({"VV_BRICKED": "0"}, {"VV_BRICKED": "1"}):
         for k, v in env.items():
@@ -1301,14 +1321,20 @@ def test_touched_lines_instrument(ctx, monkeypatch):
         ctx.load_volume(vol, tf)
         ctx.render_device(W, H, cam, frame.data_ptr(), options=vv.make_options(step=1 / 128))       # (builds the copy)
         bits = max(ctx.device_bytes()[:3]) // 128 + 64
-        got = []
+        assert bits == model.bits["bricked" if env["VV_BRICKED"] == "1" else "linear"]
+        got, words = [], []
         for every in (False, True):
             bm = torch.zeros((bits + 31) // 32, dtype=torch.int32, device=dev)
-            o = vv.make_options(step=1 / 128, touched_lines=bm.data_ptr(), touched_line_bits=bits, touched_lines_all=every)
+            o = vv.make_options(step=1 / 128, touched_lines=bm.data_ptr(), touched_line_bits=bits, touched_lines_all=every, count_samples=True)
             ctx.render_device(W, H, cam, frame.data_ptr(), options=o)
             torch.cuda.synchronize()
+            words.append(bm.cpu().numpy().view(np.uint32))
             got.append(np.unpackbits(bm.cpu().numpy().view(np.uint8)))
         assert np.all(got[1] >= got[0]), env                                   # issued contains compulsory
+        # ... and the compulsory set is the footprint model's, word for word
+        layout = "bricked" if env["VV_BRICKED"] == "1" else "linear"
+        assert ctx.last_sample_count() == model.count, (env, ctx.last_sample_count(), model.count)
+        assert np.array_equal(words[0], model.words[layout]), (env, int(got[0].sum()), FM.bit_count(model.words[layout]))
         counts[env["VV_BRICKED"]] = int(got[0].sum())
         assert ctx.last_launch()["layout"] == (2 if env["VV_BRICKED"] == "1" else 0)
         brick_total_lines = ctx.layout_state()["bricked"] // 128

@@ -359,9 +359,9 @@ def setup(R, front, back, cam_origin, step, slice_type, plane):
 # ---------------------------------------------------------------------------------------------------------------------
 # 4.-6. the march
 # ---------------------------------------------------------------------------------------------------------------------
-def _chunk_indices(vol, R, dist, inv_scale, filt, both_paths):
+def _chunk_indices(vol, R, dist, inv_scale, filt, both_paths, visit=None):
     """The 32 classification indices of every ray's chunk starting at `dist` (kernel.cu:126-145: the position accumulates
-    one step at a time); [rays, 32]."""
+    one step at a time); [rays, 32].  `visit`, if given, is called with the chunk's texture coordinates [rays, 32, 3]."""
     n = len(dist)
     pos = np.empty((n, CHUNK, 3), f32)
     with np.errstate(all="ignore"):
@@ -370,6 +370,8 @@ def _chunk_indices(vol, R, dist, inv_scale, filt, both_paths):
             pos[:, i] = p
             p = p + R["sdir"]
         tp = _to_tex(pos, inv_scale)
+    if visit is not None:
+        visit(tp)
     idx = classify(vol, tp, filt)
     if both_paths is not None and vol.dtype == np.uint8 and filt == FILTER_TEX8:
         alt = np.where(_in_bounds(tp), index_int(vol, tp), np.uint8(0))
@@ -380,10 +382,12 @@ def _chunk_indices(vol, R, dist, inv_scale, filt, both_paths):
 
 def render(vol, tf, W, H, *, cam_origin, look=None, up=(0, 1, 0), fov_y=45.0, fov_x=None, scale=(1, 1, 1), aspect=0.0, quantize8=False,
            images=None, slice_type=SLICE_NONE, plane=(.5, .5, .5, 0, 0, 1), phong=False, step=None, ert_threshold=0.0,
-           filt=FILTER_TEX8, ert_mode=ERT_REFERENCE, slab_rows=(0, 0), shard=None, fill=0, mip=False, both_paths=None):
+           filt=FILTER_TEX8, ert_mode=ERT_REFERENCE, slab_rows=(0, 0), shard=None, fill=0, mip=False, both_paths=None, visit=None):
     """One frame.  Compositing: (rgba [H, W, 4] uint8 over `fill`, executed samples).  mip=True: (rgba, index [H, W] uint8,
     executed samples) of the maximum-intensity projection.  `both_paths`: a dict with "samples" and "differ"
-    that receives the comparison of the fma path with the integer path on every u8 / TEX8 sample."""
+    that receives the comparison of the fma path with the integer path on every u8 / TEX8 sample.  `visit`: called once per
+    chunk with (texture coordinates [rays, 32, 3] of the rays that march, executed [rays, 32] bool: the samples of the chunk
+    that ran, started [rays] bool: the rays that began the chunk); nothing the frame returns depends on it."""
     nz, ny, nx = vol.shape
     table = np.ascontiguousarray(tf, f32).reshape(256, 4)
     if step is None or not np.any(np.asarray(step, f32) != 0):
@@ -433,7 +437,9 @@ def render(vol, tf, W, H, *, cam_origin, look=None, up=(0, 1, 0), fov_y=45.0, fo
             if not active.any():
                 break
             idx = np.zeros((n, CHUNK), np.uint8)
-            idx[march] = _chunk_indices(vol, sub, dist[march], inv_scale, filt, both_paths)
+            seen = []                                           # visit: the chunk's texture coordinates and which of its samples ran
+            idx[march] = _chunk_indices(vol, sub, dist[march], inv_scale, filt, both_paths, seen.append if visit is not None else None)
+            ran = np.zeros((n, CHUNK), bool) if visit is not None else None
             running = active.copy()                             # inside the 30-sample loop of this chunk
             for i in range(1, CHUNK - 1):
                 vd = f32(i) * R["sstep"] + dist
@@ -441,6 +447,8 @@ def render(vol, tf, W, H, *, cam_origin, look=None, up=(0, 1, 0), fov_y=45.0, fo
                 if not running.any():
                     break
                 count += int(running.sum())
+                if ran is not None:
+                    ran[:, i] = running
                 if mip:
                     best = np.where(running, np.maximum(best, idx[:, i]), best)
                     continue
@@ -471,6 +479,8 @@ def render(vol, tf, W, H, *, cam_origin, look=None, up=(0, 1, 0), fov_y=45.0, fo
                 running &= ~over                                # `break` leaves the inner loop only (pin 4)
                 if ert_mode == ERT_TRUE:
                     stopped |= over
+            if visit is not None:
+                visit(seen[0], ran[march], active[march])
             dist = dist + R["sstep"] * f32(30)
     own = R["owned"]
     px, py = R["x"][own], R["y"][own]

@@ -52,6 +52,7 @@ struct vv_knobs {
 enum { CP_BRICKS = 0, CP_ZPAIR = 1, CP_ZFAST = 2, CP_XPAIR = 3, CP_N = 4 };
 struct layout_copy {
     void *ptr = nullptr; size_t bytes = 0;
+    size_t alloc = 0;                       // bytes + the zeroed bytes behind them (vv_debug_read_layout)
     bool valid = false, failed = false;     // failed: not tried again until the next volume load (or an explicit vv_prepare_layouts)
     unsigned long long last_used = 0;       // when a frame last sampled it (the least recently used copy is evicted first)
     // what the sampler needs (VolumeView): bytes per row and per slab (pair copies), per row and per slice (z-fastest), per brick row and per brick layer / 64
@@ -314,7 +315,7 @@ static void copy_drop(vv_context *c, int k)
 {
     layout_copy &cp = c->copies[k];
     if (cp.ptr) (void)hipFree(cp.ptr);               // (hipFree waits for the device: frames still in flight on a caller's stream have finished with it)
-    cp.ptr = nullptr; cp.valid = false; cp.bytes = 0;
+    cp.ptr = nullptr; cp.valid = false; cp.bytes = 0; cp.alloc = 0;
 }
 // Room for `need` more bytes of copies?  `keep`: bit mask of copies that must stay (the ones the frame being set up samples or builds from).
 static bool make_room(vv_context *c, size_t need, unsigned keep)
@@ -352,7 +353,7 @@ static bool build_copy(vv_context *c, int k, size_t bytes, size_t pad, size_t ze
         hipMalloc(&cp.ptr, bytes + pad) == hipSuccess) {
         if (hipMemsetAsync((char *)cp.ptr + zero_from, 0, bytes + pad - zero_from, st) == hipSuccess) {
             build(cp.ptr);
-            if (hipGetLastError() == hipSuccess && hipStreamSynchronize(st) == hipSuccess) { cp.bytes = bytes; cp.valid = true; return true; }
+            if (hipGetLastError() == hipSuccess && hipStreamSynchronize(st) == hipSuccess) { cp.bytes = bytes; cp.alloc = bytes + pad; cp.valid = true; return true; }
         }
         (void)hipFree(cp.ptr);
     }
@@ -1552,6 +1553,33 @@ int vv_debug_last_launch(vv_context *c, int out[8])
 {
     if (!c || !out) return VV_ERR_INVALID;
     memcpy(out, c->last_launch, sizeof c->last_launch);
+    return VV_OK;
+}
+
+// A resident layout as it lies in HBM (developer aid, tests/test_footprint.py): geom = {allocation bytes (the zeroed bytes behind the copy included;
+// 0: not resident, nothing is copied), the layout's two VolumeView strides -- row_bytes / slice_bytes, b_sy / b_sz64 (64-byte units), zp_row_bytes /
+// zp_slab_bytes, zf_row_bytes / zf_slice_bytes --, nx, ny, nz, voxel type, 0}; then the allocation is copied to host_dst on the context's stream and
+// waited for (host_dst NULL with capacity 0: the geometry alone).  `layout`: the codes of vv_debug_last_launch (0 and 1 are the same allocation).  Builds nothing, changes no state.
+int vv_debug_read_layout(vv_context *c, int layout, unsigned long long geom[8], void *host_dst, size_t capacity)
+{
+    if (!c) return fail(nullptr, VV_ERR_INVALID, "vv_debug_read_layout: NULL context");
+    if (!geom) return fail(c, VV_ERR_INVALID, "vv_debug_read_layout: NULL geom");
+    if (layout < 0 || layout > 5) return fail(c, VV_ERR_INVALID, "vv_debug_read_layout: unknown layout");
+    if (!c->d_vol) return fail(c, VV_ERR_NO_VOLUME, "vv_debug_read_layout: no volume loaded");
+    static const int copy_of[] = {-1, -1, CP_BRICKS, CP_ZPAIR, CP_ZFAST, CP_XPAIR};
+    const void *src = c->d_vol;
+    unsigned long long g[8] = {c->alloc_bytes, c->row_pitch, c->slice_pitch, (unsigned long long)c->nx, (unsigned long long)c->ny, (unsigned long long)c->nz,
+                               (unsigned long long)c->vtype, 0};
+    if (copy_of[layout] >= 0) {
+        const layout_copy &cp = c->copies[copy_of[layout]];
+        src = cp.ptr; g[0] = cp.valid ? cp.alloc : 0; g[1] = cp.valid ? cp.row : 0; g[2] = cp.valid ? cp.slab : 0;
+    }
+    memcpy(geom, g, sizeof g);
+    if (g[0] == 0 || (!host_dst && capacity == 0)) return VV_OK;           // (NULL, 0: the geometry alone)
+    if (!host_dst || capacity < g[0]) return fail(c, VV_ERR_INVALID, "vv_debug_read_layout: host_dst is NULL or smaller than the allocation (geom[0])");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(host_dst, src, g[0], hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return VV_OK;
 }
 

@@ -29,9 +29,9 @@ constexpr float kEps = 1e-6f;
 struct f3 { float x, y, z; };
 __device__ __forceinline__ f3 mk3(float x, float y, float z) { return f3{x, y, z}; }
 
-// Volume as laid out in HBM: linear, x fastest, rows/slices contiguous, with one
-// row + one slice + 16 bytes of zero padding past the end so that the (weight-0)
-// upper corner of an edge sample may be fetched without clamping the index.
+// Volume as laid out in HBM: linear, x fastest, rows row_bytes and slices slice_bytes apart (dense, or padded by
+// finalize_layout: the padding is zero), with one slice + two rows + 4096 bytes of zero padding past the end so that
+// the (weight-0) upper corner of an edge sample may be fetched without clamping the index.
 struct VolumeView {
     const void *data;
     int nx, ny, nz;
@@ -49,7 +49,8 @@ struct VolumeView {
     uint32_t b_sz64;        // bytes per layer of bricks (nby * b_sy) in 64-byte units
     // Optional z-pair copy for views along the memory axis (built on first use):
     // record (x, y, z) = { v(x,y,z), v(x,y,z+1) } (8 bytes for f32, 2 bytes for u8), x fastest, rows of nx+1 records, slabs of
-    // ny+1 rows, nz slabs; indices beyond the volume clamp.  The two x-neighbouring records of a row
+    // ny+1 rows, nz slabs; indices beyond the volume clamp; 32 zero bytes behind the last slab.  u8 rows of an even nx end in one more
+    // record of padding whose content is unspecified (no gather reads it).  The two x-neighbouring records of a row
     // are the four corners (x..x+1, y, z..z+1) of a sample: one 16-byte gather per row instead of
     // two 8-byte gathers, i.e. 2 gathers per sample instead of 4 (a wave-wide gather costs the same
     // 16 cycles for 8 and for 16 bytes per lane, profiles/EXPERIMENTS.md part B section 4).  2x the volume in HBM.
@@ -631,7 +632,15 @@ __device__ __forceinline__ float ph_sqrt_core(float x)
 }
 // (both swept against binary64 over these ranges on the GPU: host/device_math_check.hip)
 
-// Instrumentation of a (never timed) frame: what the roofline's byte model is counted from.
+// Instrumentation of a (never timed) frame: what the roofline's byte model is counted from.  What is marked, per kernel family (held word for word
+// to tests/footprint_model.py by tests/test_footprint.py):
+//   march_kernel, mip_kernel, proj_kernel   every executed sample that lies in the volume (texture coordinates in [0, 1)^3): the 8^3 bricks under its
+//                                           2 x 2 x 2 footprint, upper corners clamped to n - 1, and the lines under the loads fetch_any() issues from its
+//                                           base texel.  A composite frame's rays that end early mark nothing beyond their last executed sample.
+//   iso_kernel                              the same for the samples up to and including the hit; the six gradient gathers mark lines under lines_all only.
+//   march_phong_kernel                      not the executed samples but the cache entries 1..30 that a compositing ray refreshes in a chunk it begins and that
+//                                           lie in the volume -- a superset of its executed samples, within the 30 entries of every such chunk.
+//   lines_all = 1 (and the pairs)           every gather the kernel issues: idle lanes, samples outside the volume, entries 0 / 31 and apron threads too.
 struct InstrArgs {
     uint32_t *bricks;        // 1 bit per 8^3-voxel brick of the volume touched by an executed in-volume sample (SURVEY 8d's algorithmic bytes), or NULL
     uint32_t *lines;         // 1 bit per 128-byte line of the layout this frame SAMPLES (offsets from the layout's base), or NULL

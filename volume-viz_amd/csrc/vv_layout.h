@@ -117,7 +117,9 @@ __device__ __noinline__ void mark_sample_lines(const InstrArgs &I, const VolumeV
 }
 
 // Instrumented frames only: one sample of march_kernel / mip_kernel / iso_kernel / proj_kernel, `live` when its lane executes it.  Counts it, marks its 8^3 bricks when it lies in
-// the volume, and the lines its gathers touch (InstrArgs::lines_all: those of idle lanes and out-of-volume samples too).
+// the volume, and the lines its gathers touch (InstrArgs::lines_all: those of idle lanes and out-of-volume samples too).  The rule: bricks and, under lines_all = 0,
+// lines are marked for `live && inv` samples and for no others -- an executed sample outside [0, 1)^3 is counted but marks nothing (it classifies to 0 whatever it
+// loads), a lane that is predicated off marks nothing although its gathers are issued.  march_phong_kernel has its own rule (`need`, vv_raymarch.hip; InstrArgs).
 template <int VOXEL, bool TEX8>
 __device__ __forceinline__ void instrument_sample(const InstrArgs &I, const VolumeView &V, float tx, float ty, float tz, bool live, unsigned long long &executed)
 {

@@ -114,11 +114,11 @@ EXPORTS = [
     "vv_load_volume_stream_begin", "vv_load_volume_stream_slices", "vv_load_volume_stream_end", "vv_load_volume_t3d",
     "vv_load_volume_stream_slices_async", "vv_load_volume_stream_wait_source", "vv_dataset_preset", "vv_debug_last_launch", "vv_set_frame_timing", "vv_debug_screen_rect",
     "vv_render_mip", "vv_classify_indices", "vv_render_iso", "vv_slice_slab", "vv_slice_advanced_slab",
-    "vv_volume_histogram", "vv_histogram_indices", "vv_render_projection",
+    "vv_volume_histogram", "vv_histogram_indices", "vv_render_projection", "vv_debug_read_layout",
 ]
 # entry points a variant library built from an earlier tree (A/B tools, load_library(path)) may lack
 _NEWER_EXPORTS = ("vv_render_mip", "vv_classify_indices", "vv_render_iso", "vv_slice_slab", "vv_slice_advanced_slab",
-                  "vv_volume_histogram", "vv_histogram_indices", "vv_render_projection")
+                  "vv_volume_histogram", "vv_histogram_indices", "vv_render_projection", "vv_debug_read_layout")
 
 _lib = None
 _libs = {}
@@ -195,6 +195,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.vv_cut_plane_drag.argtypes = [vp, vp, vp, i, i, i, i]
     lib.vv_debug_counters.argtypes = [vp, vp]
     lib.vv_debug_last_launch.argtypes = [vp, vp]
+    if hasattr(lib, "vv_debug_read_layout"):
+        lib.vv_debug_read_layout.argtypes = [vp, i, vp, vp, sz]
     lib.vv_set_frame_timing.argtypes = [vp, i]
     lib.vv_debug_screen_rect.argtypes = [i, i, C.POINTER(camera_params), C.POINTER(vv_ray_source), C.POINTER(C.c_double * 4)]
     lib.vv_reread_env.argtypes = [vp]
@@ -550,6 +552,17 @@ class Context:
         self._chk(self.lib.vv_debug_last_launch(self.h, out))
         k = ("tile_log2w", "blk_log2w", "unroll", "lds_reserve", "layout", "view_known", "density_x1000", "phong")     # phong: 0 unshaded, 1 Phong, 2 MIP, 3 isosurface, 4 projection
         return dict(zip(k, list(out)))
+
+    def read_layout(self, code: int):
+        """vv_debug_read_layout: the resident layout `code` (last_launch()["layout"]'s codes) as it lies in HBM: (uint8 array of the whole allocation,
+        the zeroed bytes behind the layout included; dict of its geometry).  The array is empty and alloc_bytes 0 when the layout is not resident."""
+        geom = np.zeros(8, np.uint64)
+        self._chk(self.lib.vv_debug_read_layout(self.h, int(code), geom.ctypes.data, None, 0))
+        raw = np.zeros(int(geom[0]), np.uint8)
+        if raw.size:
+            self._chk(self.lib.vv_debug_read_layout(self.h, int(code), geom.ctypes.data, raw.ctypes.data, raw.size))
+        k = ("alloc_bytes", "row", "slice", "nx", "ny", "nz", "voxel_type")   # row / slice: the layout's two VolumeView strides (bricked: slice in 64-byte units)
+        return raw, dict(zip(k, (int(v) for v in geom)))
 
     def reread_env(self):
         """vv_reread_env: pick up VV_* knobs changed since the last volume load."""
