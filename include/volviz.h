@@ -411,6 +411,56 @@ int  vv_volume_histogram(vv_context *ctx, const int box_lo[3], const int box_hi[
 int  vv_histogram_indices(vv_context *ctx, const uint8_t *index, size_t n,
                           unsigned long long counts[256], int on_device, void *stream);
 
+/* ---- derived volumes: a box of the loaded volume cropped, reduced by whole factors, windowed and converted (no reference counterpart) ----
+ * vv_derive_volume makes another volume out of the loaded one where it lies, in HBM, whatever put it there: `out` receives a dense volume, x
+ * fastest, of m_x * m_y * m_z voxels of out_type, m_a = ceil((hi_a - lo_a) / f_a) (vv_derive_dims), ready for vv_load_volume_device /
+ * vv_load_volume_* on this or another context.
+ *  1. CELL: output voxel (X, Y, Z) covers the source voxels with lo_a + X_a f_a <= x_a < min(lo_a + (X_a + 1) f_a, hi_a); n is their number
+ *     (n >= 1).  Cells at the high end of the box are partial: the voxels they lack are not zeros, they do not count.
+ *  2. REDUCTION, in storage units, giving r.
+ *     u8 source, MEAN: r = (2 s + n) / (2 n) in integers, s the cell's sum: the mean rounded half up (the rule of VV_PROJ_MEAN).
+ *     u8 source, MAX / MIN: the largest / smallest byte.
+ *     f32 source, MEAN: acc starts as the cell's first voxel (lowest z, then lowest y, then lowest x); every other voxel is added in memory order
+ *     (x fastest, then y, then z), one binary32 add each, no contraction; r = acc / (float)n, IEEE division.  n == 1: r is the voxel bit for
+ *     bit.  Sums that leave the binary32 range are +-Inf as IEEE addition says; a NaN in the cell gives a NaN (which one is not specified).
+ *     f32 source, MAX / MIN: a bit-for-bit copy of the greatest / least non-NaN voxel of the cell under the total order of bit patterns of
+ *     vv_volume_histogram's rule 2 (-0.0 below +0.0, +-Inf take part, denormals are values like any other: integer keys are compared).  A cell
+ *     of NaNs only: r = 0x7FC00000.
+ *  3. UNIT SCALE, WINDOW, OUTPUT TYPE: binary32, in the order written, no contraction.
+ *     window = 0:  u8 -> u8: out = r.  u8 -> f32: out = r / 255, correctly rounded (the promotion of vv_promote_u8_to_f32 and of the streamed
+ *     upload).  f32 -> f32: out = r.  f32 -> u8: out = the classification index of r, vv_volume_histogram's rule 1.
+ *     window = 1:  u = r (f32 source) or (float)r (u8 source); w = (u - win_lo) / (win_hi - win_lo): two subtractions and one IEEE division, so
+ *     w is exactly 0 at win_lo and exactly 1 at win_hi.  f32 out: out = w, not clamped (the classification saturates; a NaN stays a NaN).
+ *     u8 out: out = the classification index of w.  win_lo / win_hi are in storage units, those of vv_histogram.vmin / vmax (u8: 0..255).
+ *  4. What follows: (a) factor (1, 1, 1), no window, out_type = the volume's type: `out` is the box of the volume as it was loaded, byte for
+ *     byte -- the read-back (MAX / MIN write a NaN voxel as 0x7FC00000).  (b) factor 1, f32 -> u8, no window: the byte at a voxel is that
+ *     voxel's histogram bin, so vv_volume_histogram of the derived volume, once loaded, has the counts of the source box.  (c) Nothing depends on
+ *     the pitch of the source in HBM, on the launch geometry, on how the volume was loaded or on what `out` held.  (d) No byte outside the box
+ *     is read as data (the padding of a re-pitched volume never shows); no byte beyond m_x m_y m_z voxels of `out` is written.
+ *  5. BOX: box_lo inclusive, box_hi exclusive, in voxels (x, y, z), 0 <= lo < hi <= dims on every axis; all six values 0 = the whole volume.
+ *     factor: source voxels per output voxel and axis, 1..8; 0 is read as 1.
+ *  6. `stream` / out_on_device as for vv_volume_histogram: NULL = the context's stream, the call returns when the work is complete; any other
+ *     handle with a device `out` only enqueues.  A host `out` is staged through a device buffer of the call's own, allocated at the output's
+ *     size and released before the call returns (not kept in the context: the 2x reduction of a 2048^3 f32 volume is 4 GiB).  The context's
+ *     volume, table, layout copies and residency state are not touched; vv_last_frame_ms keeps its value.
+ *  7. Errors, in this order.  VV_ERR_INVALID: NULL ctx / d / out / out_dims.  VV_ERR_NO_VOLUME: no volume loaded (vv_derive_dims too: the box is
+ *     measured against the volume).  VV_ERR_INVALID: a box outside rule 5; a factor outside 0..8; a mode or out_type outside its enum; window
+ *     not 0 or 1; a window whose win_lo, win_hi or win_hi - win_lo (binary32) is not finite or whose difference is not > 0; capacity (bytes)
+ *     below the output's bytes; a device f32 `out` that is not 4-byte aligned.  VV_ERR_NOMEM: the staging buffer of a host `out` could not be
+ *     allocated.  A failed call leaves the context usable and `out` untouched.                                                              */
+typedef enum { VV_REDUCE_MEAN = 0, VV_REDUCE_MAX = 1, VV_REDUCE_MIN = 2 } vv_reduce_mode;
+typedef struct vv_derive {
+    int   box_lo[3], box_hi[3];  /* voxels (x, y, z), lo inclusive, hi exclusive, 0 <= lo < hi <= dims; all six 0 = the whole volume */
+    int   factor[3];             /* source voxels per output voxel and axis, 1..8; 0 is read as 1 */
+    int   mode;                  /* vv_reduce_mode */
+    int   out_type;              /* VV_VOXEL_U8 or VV_VOXEL_F32, whatever the loaded volume's type */
+    int   window;                /* 0 = none; 1 = map [win_lo, win_hi] onto [0, 1] */
+    float win_lo, win_hi;        /* storage units, those of vv_histogram.vmin / vmax (u8 volumes: 0..255) */
+} vv_derive;                     /* 56 bytes */
+int  vv_derive_dims(const vv_context *ctx, const vv_derive *d, int out_dims[3]);   /* host only; m_a = ceil((hi_a - lo_a) / f_a) */
+int  vv_derive_volume(vv_context *ctx, const vv_derive *d, void *out, size_t capacity,
+                      int out_on_device, void *stream);
+
 /* The first pass on its own (firstpass.vert:6, firstpass.frag:4, glwidget.cpp:198-228): the
  * RGBA8 images the reference's two FBOs would hold for this camera -- cube-space entry (front
  * faces) and exit (back faces) positions, UNORM8-rounded, alpha 255 where a face is visible and

@@ -28,6 +28,7 @@ struct vv_knobs {
     int bricked = -1, zpair = -1, zfast = -1, force_big = 0;
     int block_w = -1, tail = -1, rect = -1, lpt = -1, lpt_run = -1, phong_bricks = -1;
     int hist_blocks = -1;                   // VV_HIST_BLOCKS: cap on hist_kernel's grid (tests drive its grid-stride loop with it)
+    int derive_blocks = -1;                 // VV_DERIVE_BLOCKS: the same for derive_kernel
     // finalize_layout: VV_PITCH_PAD = bytes of row padding (0 or anything that is no number: rows stay dense; not a multiple of 16 in 16..4096: the default),
     // VV_PITCH_FORCE (set: any row length is padded), VV_PITCH_ROWS = extra rows per slice (0..64, anything else: the default)
     int pitch_pad = 32, pitch_rows = -1; bool pitch_force = false;
@@ -40,7 +41,7 @@ struct vv_knobs {
         block_w = geti("VV_BLOCK_W", -1); tail = geti("VV_TAIL", -1);
         zfast = geti("VV_ZFAST", -1); force_big = getenv("VV_FORCE_BIG") != nullptr;
         rect = geti("VV_RECT", -1); lpt = geti("VV_LPT", -1); lpt_run = geti("VV_LPT_RUN", -1); phong_bricks = geti("VV_PHONG_BRICKS", -1);
-        hist_blocks = geti("VV_HIST_BLOCKS", -1);
+        hist_blocks = geti("VV_HIST_BLOCKS", -1); derive_blocks = geti("VV_DERIVE_BLOCKS", -1);
         const int pad = geti("VV_PITCH_PAD", 32);
         pitch_pad = pad <= 0 ? 0 : ((pad >= 16 && pad <= 4096 && pad % 16 == 0) ? pad : 32);
         pitch_force = getenv("VV_PITCH_FORCE") != nullptr; pitch_rows = geti("VV_PITCH_ROWS", -1);
@@ -1771,6 +1772,92 @@ int vv_histogram_indices(vv_context *c, const uint8_t *index, size_t n, unsigned
     R.run_voxels = n; R.rps = 1; R.n_slices = 1;
     if ((rc = run_hist(c, n ? &R : nullptr, VV_VOXEL_U8, n, nullptr, (unsigned long long *)b[1].dev, st)) != VV_OK) return rc;
     return finish_call(c, stream, st, b, 2);
+}
+
+// ---- derived volumes (include/volviz.h: vv_derive_volume) ----------------------------------
+// The checks vv_derive_dims and vv_derive_volume share, in the order of the header's rule 7 (behind the NULL checks): the box (lo, hi), the
+// factors (f, 0 read as 1) and the output's extents (m).
+static int derive_check(const vv_context *c, vv_context *err_to, const char *who, const vv_derive *d, int lo[3], int hi[3], int f[3], int m[3])
+{
+    const std::string w(who);
+    if (!c->d_vol) return fail(err_to, VV_ERR_NO_VOLUME, w + ": no volume loaded");
+    const int dims[3] = {c->nx, c->ny, c->nz};
+    bool whole = true;
+    for (int a = 0; a < 3; ++a) whole = whole && d->box_lo[a] == 0 && d->box_hi[a] == 0;
+    for (int a = 0; a < 3; ++a) {
+        lo[a] = whole ? 0 : d->box_lo[a]; hi[a] = whole ? dims[a] : d->box_hi[a];
+        if (!(0 <= lo[a] && lo[a] < hi[a] && hi[a] <= dims[a])) return fail(err_to, VV_ERR_INVALID, w + ": the box must satisfy 0 <= lo < hi <= dims on every axis (or be all zeros)");
+    }
+    for (int a = 0; a < 3; ++a) {
+        if (d->factor[a] < 0 || d->factor[a] > 8) return fail(err_to, VV_ERR_INVALID, w + ": factors must lie in 1..8 (0 is read as 1)");
+        f[a] = d->factor[a] ? d->factor[a] : 1;
+        m[a] = (hi[a] - lo[a] + f[a] - 1) / f[a];
+    }
+    if (d->mode != VV_REDUCE_MEAN && d->mode != VV_REDUCE_MAX && d->mode != VV_REDUCE_MIN)
+        return fail(err_to, VV_ERR_INVALID, w + ": mode must be VV_REDUCE_MEAN, VV_REDUCE_MAX or VV_REDUCE_MIN");
+    if (d->out_type != VV_VOXEL_U8 && d->out_type != VV_VOXEL_F32) return fail(err_to, VV_ERR_INVALID, w + ": out_type must be VV_VOXEL_U8 or VV_VOXEL_F32");
+    if (d->window != 0 && d->window != 1) return fail(err_to, VV_ERR_INVALID, w + ": window must be 0 or 1");
+    if (d->window) {
+        const volatile float span = d->win_hi - d->win_lo;            // binary32, as the kernel takes it
+        if (!std::isfinite(d->win_lo) || !std::isfinite(d->win_hi) || !std::isfinite((float)span) || !(span > 0.f))
+            return fail(err_to, VV_ERR_INVALID, w + ": win_lo and win_hi must be finite with a finite win_hi - win_lo > 0");
+    }
+    return VV_OK;
+}
+
+int vv_derive_dims(const vv_context *c, const vv_derive *d, int out_dims[3])
+{
+    if (!c) return fail(nullptr, VV_ERR_INVALID, "vv_derive_dims: NULL context");
+    vv_context *e = const_cast<vv_context *>(c);                    // (the message alone)
+    if (!d || !out_dims) return fail(e, VV_ERR_INVALID, "vv_derive_dims: NULL argument");
+    int lo[3], hi[3], f[3], m[3];
+    const int rc = derive_check(c, e, "vv_derive_dims", d, lo, hi, f, m);
+    if (rc) return rc;
+    for (int a = 0; a < 3; ++a) out_dims[a] = m[a];
+    return VV_OK;
+}
+
+int vv_derive_volume(vv_context *c, const vv_derive *d, void *out, size_t capacity, int out_on_device, void *stream)
+{
+    if (!c) return fail(nullptr, VV_ERR_INVALID, "vv_derive_volume: NULL context");
+    if (!d || !out) return fail(c, VV_ERR_INVALID, "vv_derive_volume: NULL argument");
+    int lo[3], hi[3], f[3], m[3];
+    int rc = derive_check(c, c, "vv_derive_volume", d, lo, hi, f, m);
+    if (rc) return rc;
+    const size_t osize = d->out_type == VV_VOXEL_F32 ? 4 : 1, bytes = (size_t)m[0] * m[1] * m[2] * osize;
+    if (capacity < bytes) return fail(c, VV_ERR_INVALID, "vv_derive_volume: capacity is below the output's bytes (vv_derive_dims)");
+    if (out_on_device && d->out_type == VV_VOXEL_F32 && ((uintptr_t)out & 3) != 0) return fail(c, VV_ERR_INVALID, "vv_derive_volume: a device f32 out must be 4-byte aligned");
+    HIPCHK(c, hipSetDevice(c->device));
+    // A host volume goes through a device buffer of this call's own, as the generator's: a volume-sized buffer must not stay resident in the context.
+    // stage_call finds it as the buffer's fixed home; it is freed on every path below.
+    void *tmp = nullptr;
+    if (!out_on_device && hipMalloc(&tmp, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, VV_ERR_NOMEM, "vv_derive_volume: no device memory for the staging buffer of a host out");
+    }
+    hipStream_t st;
+    CallBuf b = {out, bytes, !out_on_device, false, true, 0, tmp, nullptr};
+    if ((rc = stage_call(c, stream, &st, &b, 1)) == VV_OK) {
+        const size_t size = c->vtype == VV_VOXEL_F32 ? 4 : 1;
+        DeriveArgs A;
+        memset(&A, 0, sizeof A);
+        A.src0 = (const char *)c->d_vol + (size_t)lo[2] * c->slice_pitch + (size_t)lo[1] * c->row_pitch + (size_t)lo[0] * size;
+        A.out = b.dev;
+        A.row_pitch = c->row_pitch; A.slice_pitch = c->slice_pitch;
+        for (int a = 0; a < 3; ++a) { A.b[a] = (uint32_t)(hi[a] - lo[a]); A.f[a] = (uint32_t)f[a]; A.m[a] = (uint32_t)m[a]; }
+        A.src_type = c->vtype; A.out_type = d->out_type; A.mode = d->mode; A.window = d->window;
+        A.win_lo = d->win_lo; A.win_hi = d->win_hi;
+        // what launch_derive is promised: the allocation starts 16-byte aligned and holds the box's last voxel; what lies behind that voxel is its to read
+        const size_t last = (size_t)(hi[2] - 1) * c->slice_pitch + (size_t)(hi[1] - 1) * c->row_pitch + (size_t)hi[0] * size;
+        if (((uintptr_t)c->d_vol & 15) != 0 || last > c->alloc_bytes) rc = fail(c, VV_ERR_DEVICE, "vv_derive_volume: volume allocation is not what the kernel expects");
+        else {
+            A.slack = c->alloc_bytes - last;
+            launch_derive(A, c->n_cu, c->knobs.derive_blocks, st);
+            rc = finish_call(c, stream, st, &b, 1);
+        }
+    }
+    if (tmp) (void)hipFree(tmp);
+    return rc;
 }
 
 // ---- generator: VolumeGenerator::drawEllipsoid / drawDefaultBrain ------------------------

@@ -604,17 +604,7 @@ void launch_generate_ellipsoids(uint8_t *out, int nx, int ny, int nz, int n,
 // ---------------------------------------------------------------------------
 // u8 -> f32 promotion (v / 255), 16 voxels per thread
 // ---------------------------------------------------------------------------
-// b / 255.f for a byte b without the division: q0 = b * c, r = fma(-q0, 255, b), q = fma(r, c, q0) with c = fl(1 / 255) is the correctly
-// rounded quotient for every b in 0..255 (checked exhaustively against exact rational arithmetic): one conversion + three full-rate
-// instructions instead of a ~10-instruction IEEE division.
-__device__ __forceinline__ float byte_over_255(float b)
-{
-#pragma clang fp contract(off)
-    const float c = 1.0f / 255.0f;
-    const float q0 = b * c;
-    const float r = __builtin_fmaf(-q0, 255.0f, b);
-    return __builtin_fmaf(r, c, q0);
-}
+// (byte_over_255: vv_device.h)
 // One dword (4 voxels) per lane and trip: a wave reads 256 contiguous bytes and writes 1 KB contiguous (the first version converted 16 voxels
 // per lane: four stores of 16 bytes 64 bytes apart per lane, and sixteen divisions: 1.75 ms per GiB of voxels).
 __global__ __launch_bounds__(256) void promote_kernel(const uint8_t *__restrict__ in, float *__restrict__ out, size_t n)

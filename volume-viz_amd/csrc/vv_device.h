@@ -572,6 +572,20 @@ __device__ __forceinline__ uint32_t index_of(float L)
     float s = (VOXEL == VV_VOXEL_F32) ? L * 255.0f : L;
     return min((uint32_t)s, 255u);                  // v_cvt_u32_f32 saturates; NaN -> 0
 }
+// total-order key of a binary32 bit pattern: negative values complemented, the others get the top bit (vv_hist.hip, vv_derive.hip)
+__device__ __forceinline__ uint32_t hist_key(uint32_t u) { return u ^ ((uint32_t)((int32_t)u >> 31) | 0x80000000u); }
+__device__ __forceinline__ uint32_t hist_key_inverse(uint32_t k) { return (k & 0x80000000u) ? k ^ 0x80000000u : ~k; }
+// b / 255.f for a byte b without the division (the u8 -> f32 promotion: vv_aux.hip, vv_derive.hip): q0 = b * c, r = fma(-q0, 255, b),
+// q = fma(r, c, q0) with c = fl(1 / 255) is the correctly rounded quotient for every b in 0..255 (checked exhaustively against exact rational
+// arithmetic): one conversion + three full-rate instructions instead of a ~10-instruction IEEE division.
+__device__ __forceinline__ float byte_over_255(float b)
+{
+#pragma clang fp contract(off)
+    const float c = 1.0f / 255.0f;
+    const float q0 = b * c;
+    const float r = __builtin_fmaf(-q0, 255.0f, b);
+    return __builtin_fmaf(r, c, q0);
+}
 // ... without the bounds test (the caller applies it)
 template <int VOXEL, class CT>
 __device__ __forceinline__ uint32_t classify_raw(const CT &C)

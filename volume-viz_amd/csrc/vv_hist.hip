@@ -48,10 +48,7 @@ struct HistKernelArgs {
     unsigned long long *acc;
 };
 
-// total-order key of a binary32 bit pattern: negative values complemented, the others get the top bit
-__device__ __forceinline__ uint32_t hist_key(uint32_t u) { return u ^ ((uint32_t)((int32_t)u >> 31) | 0x80000000u); }
-__device__ __forceinline__ uint32_t hist_key_inverse(uint32_t k) { return (k & 0x80000000u) ? k ^ 0x80000000u : ~k; }
-
+// (hist_key / hist_key_inverse, the total-order keys of binary32 bit patterns: vv_device.h)
 template <int VOXEL, bool VEC>
 __global__ __launch_bounds__(64 * kHistWaves) void hist_kernel(HistKernelArgs A)
 {

@@ -131,6 +131,19 @@ constexpr int kHistAccNan = 256, kHistAccKeys = 257, kHistAccWords = 258;
 void launch_hist(const HistRuns &r, int n_cu, int max_blocks /* <= 0: kHistBlocksPerCU per CU */, unsigned long long *acc, hipStream_t s);
 void launch_hist_finish(const unsigned long long *acc, int vtype, unsigned long long voxels, vv_histogram *out, unsigned long long *counts /* used when out is null */,
                         hipStream_t s);
+// derived volumes (vv_derive.hip): a box of the linear volume reduced cell by cell into a dense volume at `out` (vv_derive of include/volviz.h, checked by
+// the caller).  src0: the box's first voxel; b / f / m: the box's extents, the factors (1..8) and the output's extents in voxels (x, y, z),
+// m = ceil(b / f).  The caller vouches that the box lies inside one allocation that extends `slack` bytes beyond the box's last voxel (vector loads
+// are taken only where they are aligned and stay inside it), and that `out` holds m[0] * m[1] * m[2] voxels of out_type.
+struct DeriveArgs {
+    const void *src0; void *out;
+    uint64_t row_pitch, slice_pitch;        // of the source, bytes
+    uint32_t b[3], f[3], m[3];
+    int src_type, out_type, mode, window;   // vv_voxel_type (2 x), vv_reduce_mode, 0 / 1
+    float win_lo, win_hi;
+    uint64_t slack;
+};
+void launch_derive(const DeriveArgs &a, int n_cu, int max_blocks /* <= 0: a CU's full complement of waves per CU */, hipStream_t s);
 void launch_first_pass(const FrameParams &P, uint32_t *front, uint32_t *back, hipStream_t s);
 
 size_t generate_scratch_floats(int nx, int ny, int nz, int n);

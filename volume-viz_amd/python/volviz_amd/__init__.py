@@ -31,6 +31,7 @@ ERT_REFERENCE, ERT_TRUE = 0, 1
 SLAB_MAX, SLAB_MIN, SLAB_MEAN = 0, 1, 2          # vv_slab_mode
 SLAB_MAX_SAMPLES = 1024
 PROJ_MAX, PROJ_MIN, PROJ_MEAN = 0, 1, 2          # vv_proj_mode
+REDUCE_MEAN, REDUCE_MAX, REDUCE_MIN = 0, 1, 2    # vv_reduce_mode
 RAYS_IMAGES, RAYS_ANALYTIC = 0, 1
 TF_ENGINE, TF_HEAD, TF_MRI = 0, 1, 2
 # `stream` arguments: 0/None = the context's own stream, synchronous; STREAM_DEFAULT_ASYNC = the device's default (null)
@@ -83,6 +84,11 @@ class vv_histogram(C.Structure):          # 2072 bytes
                 ("vmin", C.c_float), ("vmax", C.c_float)]
 
 
+class vv_derive(C.Structure):             # 56 bytes
+    _fields_ = [("box_lo", C.c_int * 3), ("box_hi", C.c_int * 3), ("factor", C.c_int * 3), ("mode", C.c_int),
+                ("out_type", C.c_int), ("window", C.c_int), ("win_lo", C.c_float), ("win_hi", C.c_float)]
+
+
 @dataclass
 class Histogram:
     """vv_histogram as numpy values: counts uint64[256], voxels, nan_voxels, vmin / vmax as np.float32 (bit for bit what the library wrote)."""
@@ -115,10 +121,12 @@ EXPORTS = [
     "vv_load_volume_stream_slices_async", "vv_load_volume_stream_wait_source", "vv_dataset_preset", "vv_debug_last_launch", "vv_set_frame_timing", "vv_debug_screen_rect",
     "vv_render_mip", "vv_classify_indices", "vv_render_iso", "vv_slice_slab", "vv_slice_advanced_slab",
     "vv_volume_histogram", "vv_histogram_indices", "vv_render_projection", "vv_debug_read_layout",
+    "vv_derive_dims", "vv_derive_volume",
 ]
 # entry points a variant library built from an earlier tree (A/B tools, load_library(path)) may lack
 _NEWER_EXPORTS = ("vv_render_mip", "vv_classify_indices", "vv_render_iso", "vv_slice_slab", "vv_slice_advanced_slab",
-                  "vv_volume_histogram", "vv_histogram_indices", "vv_render_projection", "vv_debug_read_layout")
+                  "vv_volume_histogram", "vv_histogram_indices", "vv_render_projection", "vv_debug_read_layout",
+                  "vv_derive_dims", "vv_derive_volume")
 
 _lib = None
 _libs = {}
@@ -171,6 +179,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     if hasattr(lib, "vv_volume_histogram"):
         lib.vv_volume_histogram.argtypes = [vp, C.POINTER(i * 3), C.POINTER(i * 3), vp, i, vp]
         lib.vv_histogram_indices.argtypes = [vp, vp, sz, vp, i, vp]
+    if hasattr(lib, "vv_derive_volume"):
+        lib.vv_derive_dims.argtypes = [vp, C.POINTER(vv_derive), C.POINTER(i * 3)]
+        lib.vv_derive_volume.argtypes = [vp, C.POINTER(vv_derive), vp, sz, i, vp]
     lib.vv_generate_ellipsoids.argtypes = [vp, vp, i, i, i, i, i, vp, vp, vp, vp]
     lib.vv_generate_default_brain.argtypes = [vp, vp, i, i, i, i, vp]
     lib.vv_draw_ellipsoid.argtypes = [vp, vp, i, i, i, i, vp, vp, C.c_uint8, vp]
@@ -682,6 +693,54 @@ class Context:
     def histogram_indices_device(self, index_ptr: int, n: int, counts_ptr: int, stream: int = 0):
         """vv_histogram_indices on device buffers (n index bytes -> 256 uint64, 8-byte aligned), enqueued on `stream`."""
         self._chk(self.lib.vv_histogram_indices(self.h, index_ptr or None, n, counts_ptr or None, 1, stream or None))
+
+    # vv_derive_dims / vv_derive_volume (no reference counterpart)
+    def volume_type(self) -> int:
+        """The loaded volume's voxel type (vv_volume_dims)."""
+        dims, vt = (C.c_int * 3)(), C.c_int()
+        self._chk(self.lib.vv_volume_dims(self.h, C.byref(dims), C.byref(vt)))
+        return int(vt.value)
+
+    def _derive(self, box, factor, mode, out_type, window) -> vv_derive:
+        """box = ((x0, y0, z0), (x1, y1, z1)) or None = the whole volume; factor: an int or (fx, fy, fz); out_type None = the volume's type;
+        window = (win_lo, win_hi) or None."""
+        d = vv_derive()
+        if box is not None:
+            d.box_lo[:] = [int(v) for v in box[0]]
+            d.box_hi[:] = [int(v) for v in box[1]]
+        d.factor[:] = [int(factor)] * 3 if np.isscalar(factor) else [int(v) for v in factor]
+        d.mode = int(mode)
+        d.out_type = self.volume_type() if out_type is None else int(out_type)
+        if window is not None:
+            d.window, d.win_lo, d.win_hi = 1, float(window[0]), float(window[1])
+        return d
+
+    def derive_dims(self, box=None, factor=1):
+        """vv_derive_dims: (mx, my, mz) of the volume derive() makes of this box and factor."""
+        d = self._derive(box, factor, REDUCE_MEAN, VOXEL_U8, None)
+        m = (C.c_int * 3)()
+        self._chk(self.lib.vv_derive_dims(self.h, C.byref(d), C.byref(m)))
+        return int(m[0]), int(m[1]), int(m[2])
+
+    def derive(self, box=None, factor=1, mode=REDUCE_MEAN, out_type=None, window=None, prefill=None) -> np.ndarray:
+        """vv_derive_volume into a host array [mz, my, mx] of uint8 or float32.  `prefill`: the byte the buffer holds before the call (the
+        result does not depend on it)."""
+        d = self._derive(box, factor, mode, out_type, window)
+        m = (C.c_int * 3)()
+        self._chk(self.lib.vv_derive_dims(self.h, C.byref(d), C.byref(m)))
+        out = np.empty((m[2], m[1], m[0]), np.float32 if d.out_type == VOXEL_F32 else np.uint8)
+        if prefill is not None:
+            out.view(np.uint8)[...] = prefill
+        self._chk(self.lib.vv_derive_volume(self.h, C.byref(d), out.ctypes.data, out.nbytes, 0, None))
+        return out
+
+    def derive_device(self, out_ptr: int, capacity: int, box=None, factor=1, mode=REDUCE_MEAN, out_type=None, window=None, stream: int = 0):
+        """vv_derive_volume into a device buffer of `capacity` bytes, enqueued on `stream`; returns (mx, my, mz)."""
+        d = self._derive(box, factor, mode, out_type, window)
+        m = (C.c_int * 3)()
+        self._chk(self.lib.vv_derive_dims(self.h, C.byref(d), C.byref(m)))
+        self._chk(self.lib.vv_derive_volume(self.h, C.byref(d), out_ptr or None, int(capacity), 1, stream or None))
+        return int(m[0]), int(m[1]), int(m[2])
 
     # VolumeGenerator::drawEllipsoid x n / drawDefaultBrain (volumegenerator.cpp:31-119)
     def generate_ellipsoids(self, nx: int, ny: int, nz: int, centers, axes, colors) -> np.ndarray:
