@@ -461,6 +461,60 @@ int  vv_derive_dims(const vv_context *ctx, const vv_derive *d, int out_dims[3]);
 int  vv_derive_volume(vv_context *ctx, const vv_derive *d, void *out, size_t capacity,
                       int out_on_device, void *stream);
 
+/* ---- neighbourhood filters ("stencils"): a box of the loaded volume smoothed, median-filtered or turned into its gradient magnitude (no
+ * reference counterpart; vv_filter is the trilinear model, these calls look at a voxel's neighbours) ----
+ * vv_stencil_volume filters the loaded volume where it lies, in HBM: `out` receives a dense volume, x fastest, of the box's extents hi - lo (no
+ * reduction) in out_type, ready for vv_load_volume_device / vv_load_volume_* on this or another context.
+ *  1. SOURCE VALUE AND EDGES: u(x, y, z) is the voxel in storage units as binary32: an f32 voxel itself, (float)byte for u8.  Every coordinate a
+ *     stencil reaches is clamped to [0, n_a - 1] of the VOLUME, not of the box (edge replication): a box inside the volume sees its true
+ *     neighbours outside the box, and the result for a box is the crop of the result for the whole volume, bit for bit.
+ *  2. ARITHMETIC: binary32, in the order written, one rounding per operation, no contraction, denormals kept (vv_derive_volume's stage 3).
+ *  3. VV_STENCIL_SEPARABLE: three passes, x then y then z: P_x = conv_x(u), P_y = conv_y(P_x), r = conv_z(P_y).  Each intermediate is a binary32
+ *     value defined at every voxel of the volume; the clamp of rule 1 applies to the axis of the pass.  One pass with radius R and taps t:
+ *     acc = t[0] * c, then for k = 1..R in order acc = acc + t[k] * (v(-k) + v(+k)): the pair's sum, then the product, then the add.  R = 0: the
+ *     pass is the identity, bit for bit (no multiplication by t[0]).  taps[a][k] with k > radius[a] are ignored.
+ *  4. VV_STENCIL_MEDIAN: the 27 values of the clamped 3x3x3 neighbourhood (at an edge values repeat), ordered as bytes (u8) or by the total order
+ *     of binary32 bit patterns of vv_volume_histogram's rule 2 (f32: a NaN takes part by its pattern, positive-sign NaNs above +Inf, negative-sign
+ *     ones below -Inf); r is a bit-for-bit copy of the 14th smallest.  No floating-point comparison is made.
+ *  5. VV_STENCIL_GRADMAG: g_a = u(+e_a) - u(-e_a) with clamped coordinates (at a face a one-sided difference, unscaled); G_a = g_a * gscale[a];
+ *     r = sqrtf((G_x * G_x + G_y * G_y) + G_z * G_z), IEEE sqrtf.  gscale (0, 0, 0) is read as (1, 1, 1).
+ *  6. OUTPUT: f32 -> f32: out = r.  f32 -> u8: out = the classification index of r (vv_volume_histogram's rule 1; a NaN gives 0).  u8 -> f32:
+ *     out = r / 255.0f, IEEE division (MEDIAN: the promotion of vv_promote_u8_to_f32).  u8 -> u8, MEDIAN: out = r.  u8 -> u8, SEPARABLE and
+ *     GRADMAG: 0 if r is NaN or r < 0.5f; 255 if r >= 254.5f; otherwise (int)(r + 0.5f): one binary32 add, then truncation (this sequence of
+ *     operations is the rule, not "round half up" as mathematics).
+ *  7. What follows: (a) the crop identity of rule 1.  (b) SEPARABLE with radius (0, 0, 0) equals vv_derive_volume at factor 1, MEAN, no window,
+ *     the same box and out_type, byte for byte, for all four type pairs.  (c) Nothing depends on the pitch of the source in HBM, on the 64-bit
+ *     addressing build, on the launch geometry, on how the volume was loaded or on what `out` held.  (d) No byte beyond the output's voxels is
+ *     written, no byte outside the volume's allocation is read, and the padding of a re-pitched volume is never read as data: clamping is by
+ *     coordinates.  (e) Results are the same from run to run.
+ *  8. `stream` / out_on_device as for vv_derive_volume.  A host `out` is staged through a device buffer of the call's own, sized to the output
+ *     and released before the call returns.  A device-`out` call allocates no device memory and uses no volume-sized temporary: the three passes
+ *     are one launch (a 1024^3 f32 intermediate would be 4 GiB beside a volume and its copies, which are under a budget).  The context's volume,
+ *     table, layout copies and residency state are not touched; vv_last_frame_ms keeps its value.
+ *  9. Errors, in this order.  VV_ERR_INVALID: NULL ctx / s / out.  VV_ERR_NO_VOLUME: no volume loaded.  VV_ERR_INVALID, each in turn: a box
+ *     outside vv_derive's rule 5; a kind or out_type outside its enum; SEPARABLE: a radius outside 0..VV_STENCIL_MAX_RADIUS, or a tap with index
+ *     <= its radius that is not finite; GRADMAG: a gscale that is not finite; capacity (bytes) below the output's bytes; a device f32 `out` that
+ *     is not 4-byte aligned; a device `out` whose byte range overlaps the context's linear volume allocation (the pass is not in place).
+ *     VV_ERR_NOMEM: the staging buffer of a host `out` could not be allocated.  A failed call writes nothing and leaves the context usable.
+ * vv_stencil_taps fills taps[0..radius] (the rest with 0) for one axis; host only.  VV_TAPS_BOX: every tap 1.0f / (2 R + 1).  VV_TAPS_BINOMIAL:
+ * tap k = C(2 R, R + k) / 4^R, exact dyadics.  VV_TAPS_GAUSS: w_k = exp(-k^2 / (2 sigma^2)) in binary64, normalised by w_0 + 2 w_1 + ... + 2 w_R
+ * (summed in that order), rounded once to binary32; sigma must be finite and > 0 (the other shapes ignore it).  VV_ERR_INVALID: a shape outside
+ * the enum, a radius outside 0..VV_STENCIL_MAX_RADIUS, a bad sigma, NULL taps.                                                              */
+typedef enum { VV_STENCIL_SEPARABLE = 0, VV_STENCIL_MEDIAN = 1, VV_STENCIL_GRADMAG = 2 } vv_stencil_kind;
+#define VV_STENCIL_MAX_RADIUS 4
+typedef struct vv_stencil {
+    int   box_lo[3], box_hi[3];  /* as vv_derive: lo inclusive, hi exclusive, all six 0 = the whole volume */
+    int   kind;                  /* vv_stencil_kind */
+    int   out_type;              /* VV_VOXEL_U8 or VV_VOXEL_F32, whatever the loaded volume's type */
+    int   radius[3];             /* SEPARABLE: taps per side on x, y, z, 0..VV_STENCIL_MAX_RADIUS; 0 = that axis is not filtered */
+    float taps[3][5];            /* SEPARABLE: taps[a][0] the centre, taps[a][k] at distance k on both sides */
+    float gscale[3];             /* GRADMAG: per-axis multiplier; all three 0 = (1, 1, 1) */
+} vv_stencil;                    /* 116 bytes */
+int  vv_stencil_volume(vv_context *ctx, const vv_stencil *s, void *out, size_t capacity,
+                       int out_on_device, void *stream);
+typedef enum { VV_TAPS_BOX = 0, VV_TAPS_BINOMIAL = 1, VV_TAPS_GAUSS = 2 } vv_taps_shape;
+int  vv_stencil_taps(int shape, int radius, float sigma, float taps[5]);   /* host only, no context */
+
 /* The first pass on its own (firstpass.vert:6, firstpass.frag:4, glwidget.cpp:198-228): the
  * RGBA8 images the reference's two FBOs would hold for this camera -- cube-space entry (front
  * faces) and exit (back faces) positions, UNORM8-rounded, alpha 255 where a face is visible and

@@ -29,6 +29,7 @@ struct vv_knobs {
     int block_w = -1, tail = -1, rect = -1, lpt = -1, lpt_run = -1, phong_bricks = -1;
     int hist_blocks = -1;                   // VV_HIST_BLOCKS: cap on hist_kernel's grid (tests drive its grid-stride loop with it)
     int derive_blocks = -1;                 // VV_DERIVE_BLOCKS: the same for derive_kernel
+    int stencil_blocks = -1;                // VV_STENCIL_BLOCKS: the same for the stencil kernels (their loop over (tile, z segment) items)
     // finalize_layout: VV_PITCH_PAD = bytes of row padding (0 or anything that is no number: rows stay dense; not a multiple of 16 in 16..4096: the default),
     // VV_PITCH_FORCE (set: any row length is padded), VV_PITCH_ROWS = extra rows per slice (0..64, anything else: the default)
     int pitch_pad = 32, pitch_rows = -1; bool pitch_force = false;
@@ -42,6 +43,7 @@ struct vv_knobs {
         zfast = geti("VV_ZFAST", -1); force_big = getenv("VV_FORCE_BIG") != nullptr;
         rect = geti("VV_RECT", -1); lpt = geti("VV_LPT", -1); lpt_run = geti("VV_LPT_RUN", -1); phong_bricks = geti("VV_PHONG_BRICKS", -1);
         hist_blocks = geti("VV_HIST_BLOCKS", -1); derive_blocks = geti("VV_DERIVE_BLOCKS", -1);
+        stencil_blocks = geti("VV_STENCIL_BLOCKS", -1);
         const int pad = geti("VV_PITCH_PAD", 32);
         pitch_pad = pad <= 0 ? 0 : ((pad >= 16 && pad <= 4096 && pad % 16 == 0) ? pad : 32);
         pitch_force = getenv("VV_PITCH_FORCE") != nullptr; pitch_rows = geti("VV_PITCH_ROWS", -1);
@@ -1853,6 +1855,76 @@ int vv_derive_volume(vv_context *c, const vv_derive *d, void *out, size_t capaci
         else {
             A.slack = c->alloc_bytes - last;
             launch_derive(A, c->n_cu, c->knobs.derive_blocks, st);
+            rc = finish_call(c, stream, st, &b, 1);
+        }
+    }
+    if (tmp) (void)hipFree(tmp);
+    return rc;
+}
+
+// ---- neighbourhood filters (include/volviz.h: vv_stencil_volume) ---------------------------
+int vv_stencil_volume(vv_context *c, const vv_stencil *d, void *out, size_t capacity, int out_on_device, void *stream)
+{
+    if (!c) return fail(nullptr, VV_ERR_INVALID, "vv_stencil_volume: NULL context");
+    if (!d || !out) return fail(c, VV_ERR_INVALID, "vv_stencil_volume: NULL argument");
+    if (!c->d_vol) return fail(c, VV_ERR_NO_VOLUME, "vv_stencil_volume: no volume loaded");
+    // the header's rule 9, in its order
+    const int dims[3] = {c->nx, c->ny, c->nz};
+    int lo[3], hi[3];
+    bool whole = true;
+    for (int a = 0; a < 3; ++a) whole = whole && d->box_lo[a] == 0 && d->box_hi[a] == 0;
+    for (int a = 0; a < 3; ++a) {
+        lo[a] = whole ? 0 : d->box_lo[a]; hi[a] = whole ? dims[a] : d->box_hi[a];
+        if (!(0 <= lo[a] && lo[a] < hi[a] && hi[a] <= dims[a])) return fail(c, VV_ERR_INVALID, "vv_stencil_volume: the box must satisfy 0 <= lo < hi <= dims on every axis (or be all zeros)");
+    }
+    if (d->kind != VV_STENCIL_SEPARABLE && d->kind != VV_STENCIL_MEDIAN && d->kind != VV_STENCIL_GRADMAG)
+        return fail(c, VV_ERR_INVALID, "vv_stencil_volume: kind must be VV_STENCIL_SEPARABLE, VV_STENCIL_MEDIAN or VV_STENCIL_GRADMAG");
+    if (d->out_type != VV_VOXEL_U8 && d->out_type != VV_VOXEL_F32) return fail(c, VV_ERR_INVALID, "vv_stencil_volume: out_type must be VV_VOXEL_U8 or VV_VOXEL_F32");
+    StencilArgs A;
+    memset(&A, 0, sizeof A);
+    if (d->kind == VV_STENCIL_SEPARABLE)
+        for (int a = 0; a < 3; ++a) {
+            if (d->radius[a] < 0 || d->radius[a] > VV_STENCIL_MAX_RADIUS) return fail(c, VV_ERR_INVALID, "vv_stencil_volume: radii must lie in 0..4");
+            A.radius[a] = d->radius[a];
+            for (int k = 0; k <= d->radius[a]; ++k) {
+                if (!std::isfinite(d->taps[a][k])) return fail(c, VV_ERR_INVALID, "vv_stencil_volume: the taps up to the radius must be finite");
+                A.taps[a][k] = d->taps[a][k];
+            }
+        }
+    if (d->kind == VV_STENCIL_GRADMAG) {
+        const bool unset = d->gscale[0] == 0.f && d->gscale[1] == 0.f && d->gscale[2] == 0.f;
+        for (int a = 0; a < 3; ++a) {
+            if (!std::isfinite(d->gscale[a])) return fail(c, VV_ERR_INVALID, "vv_stencil_volume: gscale must be finite");
+            A.gscale[a] = unset ? 1.f : d->gscale[a];
+        }
+    }
+    const size_t osize = d->out_type == VV_VOXEL_F32 ? 4 : 1, bytes = (size_t)(hi[0] - lo[0]) * (size_t)(hi[1] - lo[1]) * (size_t)(hi[2] - lo[2]) * osize;
+    if (capacity < bytes) return fail(c, VV_ERR_INVALID, "vv_stencil_volume: capacity is below the output's bytes");
+    if (out_on_device && d->out_type == VV_VOXEL_F32 && ((uintptr_t)out & 3) != 0) return fail(c, VV_ERR_INVALID, "vv_stencil_volume: a device f32 out must be 4-byte aligned");
+    if (out_on_device && (uintptr_t)out < (uintptr_t)c->d_vol + c->alloc_bytes && (uintptr_t)c->d_vol < (uintptr_t)out + bytes)
+        return fail(c, VV_ERR_INVALID, "vv_stencil_volume: out overlaps the loaded volume (the pass is not in place)");
+    HIPCHK(c, hipSetDevice(c->device));
+    // a host volume goes through a device buffer of this call's own, as vv_derive_volume's; a device out allocates nothing
+    void *tmp = nullptr;
+    if (!out_on_device && hipMalloc(&tmp, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, VV_ERR_NOMEM, "vv_stencil_volume: no device memory for the staging buffer of a host out");
+    }
+    hipStream_t st;
+    CallBuf b = {out, bytes, !out_on_device, false, true, 0, tmp, nullptr};
+    int rc = stage_call(c, stream, &st, &b, 1);
+    if (rc == VV_OK) {
+        const size_t size = c->vtype == VV_VOXEL_F32 ? 4 : 1;
+        A.vol = c->d_vol; A.out = b.dev;
+        A.row_pitch = c->row_pitch; A.slice_pitch = c->slice_pitch;
+        for (int a = 0; a < 3; ++a) { A.n[a] = dims[a]; A.lo[a] = lo[a]; A.b[a] = (uint32_t)(hi[a] - lo[a]); }
+        A.src_type = c->vtype; A.out_type = d->out_type; A.kind = d->kind;
+        // what launch_stencil is promised: the volume's last voxel lies inside the allocation
+        const size_t last = (size_t)(c->nz - 1) * c->slice_pitch + (size_t)(c->ny - 1) * c->row_pitch + (size_t)c->nx * size;
+        if (last > c->alloc_bytes || (size == 4 && (((uintptr_t)c->d_vol | c->row_pitch | c->slice_pitch) & 3) != 0))
+            rc = fail(c, VV_ERR_DEVICE, "vv_stencil_volume: volume allocation is not what the kernel expects");
+        else {
+            launch_stencil(A, c->n_cu, c->knobs.stencil_blocks, st);
             rc = finish_call(c, stream, st, &b, 1);
         }
     }

@@ -49,6 +49,33 @@ int vv_transfer_preset(int preset, float tf[1024])
     }
 }
 
+// include/volviz.h: the taps of one axis of a VV_STENCIL_SEPARABLE pass
+int vv_stencil_taps(int shape, int radius, float sigma, float taps[5])
+{
+    if (!taps || radius < 0 || radius > VV_STENCIL_MAX_RADIUS) return VV_ERR_INVALID;
+    if (shape != VV_TAPS_BOX && shape != VV_TAPS_BINOMIAL && shape != VV_TAPS_GAUSS) return VV_ERR_INVALID;
+    if (shape == VV_TAPS_GAUSS && !(std::isfinite(sigma) && sigma > 0.f)) return VV_ERR_INVALID;
+    float t[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    if (shape == VV_TAPS_BOX) {
+        for (int k = 0; k <= radius; ++k) t[k] = 1.0f / (float)(2 * radius + 1);
+    } else if (shape == VV_TAPS_BINOMIAL) {
+        // C(2R, R + k) / 4^R: row 2R of Pascal's triangle by additions, the quotient by a power of two is exact
+        unsigned row[2 * VV_STENCIL_MAX_RADIUS + 1] = {1};
+        for (int n = 1; n <= 2 * radius; ++n)
+            for (int i = n; i >= 1; --i) row[i] += row[i - 1];
+        for (int k = 0; k <= radius; ++k) t[k] = (float)row[radius + k] / (float)(1u << (2 * radius));
+    } else {
+        double w[5], sum = 0.0;
+        const double s = (double)sigma;
+        for (int k = 0; k <= radius; ++k) w[k] = std::exp(-(double)(k * k) / (2.0 * s * s));
+        sum = w[0];
+        for (int k = 1; k <= radius; ++k) sum += 2.0 * w[k];
+        for (int k = 0; k <= radius; ++k) t[k] = (float)(w[k] / sum);
+    }
+    memcpy(taps, t, sizeof t);
+    return VV_OK;
+}
+
 // glwidget.cpp:678-689: table and scale by the file name's ending (QString::endsWith, case-sensitive)
 int vv_dataset_preset(const char *path, int *tf_preset, float scale[3])
 {

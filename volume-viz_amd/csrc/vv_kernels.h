@@ -144,6 +144,22 @@ struct DeriveArgs {
     uint64_t slack;
 };
 void launch_derive(const DeriveArgs &a, int n_cu, int max_blocks /* <= 0: a CU's full complement of waves per CU */, hipStream_t s);
+// neighbourhood filters (vv_stencil.hip): a box of the linear volume filtered into a dense volume of the box's extents at `out` (vv_stencil of
+// include/volviz.h, checked by the caller: radii 0..VV_STENCIL_MAX_RADIUS, gscale resolved).  vol: the volume's first voxel; n: its extents;
+// lo / b: the box's low corner and extents in voxels (x, y, z).  Every voxel a stencil reaches is addressed by coordinates clamped to n: the
+// caller vouches that the n[0] x n[1] x n[2] voxels at the two pitches lie inside one allocation and that `out` holds b[0] * b[1] * b[2] voxels of
+// out_type outside it.
+struct StencilArgs {
+    const void *vol; void *out;
+    uint64_t row_pitch, slice_pitch;        // of the source, bytes
+    int32_t n[3], lo[3];
+    uint32_t b[3];
+    int src_type, out_type, kind;           // vv_voxel_type (2 x), vv_stencil_kind
+    int radius[3];
+    float taps[3][5];
+    float gscale[3];
+};
+void launch_stencil(const StencilArgs &a, int n_cu, int max_blocks /* <= 0: one block per (tile, z segment) */, hipStream_t s);
 void launch_first_pass(const FrameParams &P, uint32_t *front, uint32_t *back, hipStream_t s);
 
 size_t generate_scratch_floats(int nx, int ny, int nz, int n);

@@ -32,6 +32,9 @@ SLAB_MAX, SLAB_MIN, SLAB_MEAN = 0, 1, 2          # vv_slab_mode
 SLAB_MAX_SAMPLES = 1024
 PROJ_MAX, PROJ_MIN, PROJ_MEAN = 0, 1, 2          # vv_proj_mode
 REDUCE_MEAN, REDUCE_MAX, REDUCE_MIN = 0, 1, 2    # vv_reduce_mode
+STENCIL_SEPARABLE, STENCIL_MEDIAN, STENCIL_GRADMAG = 0, 1, 2     # vv_stencil_kind
+STENCIL_MAX_RADIUS = 4
+TAPS_BOX, TAPS_BINOMIAL, TAPS_GAUSS = 0, 1, 2    # vv_taps_shape
 RAYS_IMAGES, RAYS_ANALYTIC = 0, 1
 TF_ENGINE, TF_HEAD, TF_MRI = 0, 1, 2
 # `stream` arguments: 0/None = the context's own stream, synchronous; STREAM_DEFAULT_ASYNC = the device's default (null)
@@ -89,6 +92,11 @@ class vv_derive(C.Structure):             # 56 bytes
                 ("out_type", C.c_int), ("window", C.c_int), ("win_lo", C.c_float), ("win_hi", C.c_float)]
 
 
+class vv_stencil(C.Structure):            # 116 bytes
+    _fields_ = [("box_lo", C.c_int * 3), ("box_hi", C.c_int * 3), ("kind", C.c_int), ("out_type", C.c_int), ("radius", C.c_int * 3),
+                ("taps", (C.c_float * 5) * 3), ("gscale", C.c_float * 3)]
+
+
 @dataclass
 class Histogram:
     """vv_histogram as numpy values: counts uint64[256], voxels, nan_voxels, vmin / vmax as np.float32 (bit for bit what the library wrote)."""
@@ -121,12 +129,12 @@ EXPORTS = [
     "vv_load_volume_stream_slices_async", "vv_load_volume_stream_wait_source", "vv_dataset_preset", "vv_debug_last_launch", "vv_set_frame_timing", "vv_debug_screen_rect",
     "vv_render_mip", "vv_classify_indices", "vv_render_iso", "vv_slice_slab", "vv_slice_advanced_slab",
     "vv_volume_histogram", "vv_histogram_indices", "vv_render_projection", "vv_debug_read_layout",
-    "vv_derive_dims", "vv_derive_volume",
+    "vv_derive_dims", "vv_derive_volume", "vv_stencil_volume", "vv_stencil_taps",
 ]
 # entry points a variant library built from an earlier tree (A/B tools, load_library(path)) may lack
 _NEWER_EXPORTS = ("vv_render_mip", "vv_classify_indices", "vv_render_iso", "vv_slice_slab", "vv_slice_advanced_slab",
                   "vv_volume_histogram", "vv_histogram_indices", "vv_render_projection", "vv_debug_read_layout",
-                  "vv_derive_dims", "vv_derive_volume")
+                  "vv_derive_dims", "vv_derive_volume", "vv_stencil_volume", "vv_stencil_taps")
 
 _lib = None
 _libs = {}
@@ -182,6 +190,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     if hasattr(lib, "vv_derive_volume"):
         lib.vv_derive_dims.argtypes = [vp, C.POINTER(vv_derive), C.POINTER(i * 3)]
         lib.vv_derive_volume.argtypes = [vp, C.POINTER(vv_derive), vp, sz, i, vp]
+    if hasattr(lib, "vv_stencil_volume"):
+        lib.vv_stencil_volume.argtypes = [vp, C.POINTER(vv_stencil), vp, sz, i, vp]
+        lib.vv_stencil_taps.argtypes = [i, i, f, C.POINTER(f * 5)]
     lib.vv_generate_ellipsoids.argtypes = [vp, vp, i, i, i, i, i, vp, vp, vp, vp]
     lib.vv_generate_default_brain.argtypes = [vp, vp, i, i, i, i, vp]
     lib.vv_draw_ellipsoid.argtypes = [vp, vp, i, i, i, i, vp, vp, C.c_uint8, vp]
@@ -742,6 +753,64 @@ class Context:
         self._chk(self.lib.vv_derive_volume(self.h, C.byref(d), out_ptr or None, int(capacity), 1, stream or None))
         return int(m[0]), int(m[1]), int(m[2])
 
+    # vv_stencil_volume (no reference counterpart)
+    def _stencil(self, kind, box, out_type, radius, taps, gscale) -> vv_stencil:
+        """box and out_type as _derive; radius: an int or (rx, ry, rz); taps: None, one row of up to 5 taps for all three axes, or three rows
+        (x, y, z), taps[a][0] the centre; gscale: None (= (1, 1, 1)) or three multipliers."""
+        d = vv_stencil()
+        if box is not None:
+            d.box_lo[:] = [int(v) for v in box[0]]
+            d.box_hi[:] = [int(v) for v in box[1]]
+        d.kind = int(kind)
+        d.out_type = self.volume_type() if out_type is None else int(out_type)
+        d.radius[:] = [int(radius)] * 3 if np.isscalar(radius) else [int(v) for v in radius]
+        if taps is not None:
+            t = np.asarray(taps, np.float32)
+            rows = [t, t, t] if t.ndim == 1 else list(t)
+            for a in range(3):
+                for k, v in enumerate(np.asarray(rows[a], np.float32)[:5]):
+                    d.taps[a][k] = float(v)
+        if gscale is not None:
+            d.gscale[:] = [float(v) for v in gscale]
+        return d
+
+    def _stencil_dims(self, d: vv_stencil):
+        if not any(d.box_lo) and not any(d.box_hi):
+            dims = (C.c_int * 3)()
+            self._chk(self.lib.vv_volume_dims(self.h, C.byref(dims), None))
+            return int(dims[0]), int(dims[1]), int(dims[2])
+        return tuple(max(int(h) - int(l), 0) for l, h in zip(d.box_lo, d.box_hi))
+
+    def stencil(self, kind, box=None, out_type=None, radius=(0, 0, 0), taps=None, gscale=None, prefill=None) -> np.ndarray:
+        """vv_stencil_volume into a host array [bz, by, bx] of uint8 or float32 (the box's extents).  `prefill`: the byte the buffer holds before
+        the call (the result does not depend on it)."""
+        d = self._stencil(kind, box, out_type, radius, taps, gscale)
+        bx, by, bz = self._stencil_dims(d)
+        out = np.empty((bz, by, bx), np.float32 if d.out_type == VOXEL_F32 else np.uint8)
+        if prefill is not None:
+            out.view(np.uint8)[...] = prefill
+        self._chk(self.lib.vv_stencil_volume(self.h, C.byref(d), out.ctypes.data if out.size else None, out.nbytes, 0, None))
+        return out
+
+    def stencil_device(self, out_ptr: int, capacity: int, kind, box=None, out_type=None, radius=(0, 0, 0), taps=None, gscale=None, stream: int = 0):
+        """vv_stencil_volume into a device buffer of `capacity` bytes, enqueued on `stream`; returns the output's (bx, by, bz)."""
+        d = self._stencil(kind, box, out_type, radius, taps, gscale)
+        self._chk(self.lib.vv_stencil_volume(self.h, C.byref(d), out_ptr or None, int(capacity), 1, stream or None))
+        return self._stencil_dims(d)
+
+    def smooth(self, radius=1, shape=TAPS_BINOMIAL, sigma=0.0, box=None, out_type=None) -> np.ndarray:
+        """The volume (or a box of it) smoothed with stencil_taps(shape, r, sigma) on every axis; radius: an int or (rx, ry, rz)."""
+        r = [int(radius)] * 3 if np.isscalar(radius) else [int(v) for v in radius]
+        return self.stencil(STENCIL_SEPARABLE, box, out_type, r, [stencil_taps(shape, v, sigma) for v in r])
+
+    def median(self, box=None, out_type=None) -> np.ndarray:
+        """The 3x3x3 median of the volume (or of a box of it)."""
+        return self.stencil(STENCIL_MEDIAN, box, out_type)
+
+    def gradient_magnitude(self, gscale=None, box=None, out_type=None) -> np.ndarray:
+        """The magnitude of the central-difference gradient, each axis multiplied by gscale[a] first."""
+        return self.stencil(STENCIL_GRADMAG, box, out_type, gscale=gscale)
+
     # VolumeGenerator::drawEllipsoid x n / drawDefaultBrain (volumegenerator.cpp:31-119)
     def generate_ellipsoids(self, nx: int, ny: int, nz: int, centers, axes, colors) -> np.ndarray:
         centers = np.ascontiguousarray(centers, np.float32).reshape(-1, 3)
@@ -774,6 +843,15 @@ class Context:
 
     def promote_device(self, dev_in: int, dev_out: int, n: int, stream: int = 0):
         self._chk(self.lib.vv_promote_u8_to_f32(self.h, dev_in, dev_out, n, stream))
+
+
+def stencil_taps(shape: int, radius: int, sigma: float = 0.0) -> np.ndarray:
+    """vv_stencil_taps: float32[5], taps[0] the centre, taps[k] at distance k, zeros beyond the radius."""
+    t = (C.c_float * 5)()
+    rc = load_library().vv_stencil_taps(int(shape), int(radius), float(sigma), C.byref(t))
+    if rc != 0:
+        raise VolvizError(rc, "vv_stencil_taps: bad shape, radius or sigma")
+    return np.array(t[:], np.float32)
 
 
 def cut_plane_canonical(orientation: int, displace: float):
