@@ -515,6 +515,57 @@ int  vv_stencil_volume(vv_context *ctx, const vv_stencil *s, void *out, size_t c
 typedef enum { VV_TAPS_BOX = 0, VV_TAPS_BINOMIAL = 1, VV_TAPS_GAUSS = 2 } vv_taps_shape;
 int  vv_stencil_taps(int shape, int radius, float sigma, float taps[5]);   /* host only, no context */
 
+/* ---- resampled volumes: the loaded volume on another grid (no reference counterpart) ----
+ * vv_resample_volume samples the loaded volume where it lies, in HBM: every voxel of an output grid of dims m_x x m_y x m_z is the sample of the
+ * volume at an affinely mapped position -- an anisotropic scan made isotropic, a reoriented or zoomed volume, a level of detail that is no whole
+ * factor.  `out` receives a dense volume, x fastest, of the box's extents in out_type, ready for vv_load_volume_device / vv_load_volume_*.
+ * Everything below is binary32, in the order written, one rounding per operation, no contraction, denormals kept.
+ *  1. POSITION: inv_a = 1.0f / (float)m_a, one IEEE division made once.  Output voxel (X, Y, Z) of the GRID (not of the box):
+ *     q_a = ((float)X_a + 0.5f) * inv_a;  p_r = ((m[4r] * q_x + m[4r+1] * q_y) + m[4r+2] * q_z) + m[4r+3], r = 0, 1, 2.  p is in the texture
+ *     coordinates of vv_slice: [0, 1) spans the volume on each axis.
+ *  2. INSIDE: vv_slice's test: p_r >= 0.0f && p_r < 1.0f for all three r (a NaN is outside; -0.0f is inside and samples as 0.0f).  Outside: r = fill.
+ *  3. VALUE: VV_RESAMPLE_TEX8 / VV_RESAMPLE_EXACT: r = the trilinear value of the texture model at p under that vv_filter, in storage units
+ *     (0..255 for u8): what vv_slice filters before its / 255 -- x, then y, then z, each fma(w, b - a, a).  VV_RESAMPLE_NEAREST:
+ *     i_a = min((uint32_t)(p_a * (float)n_a), n_a - 1); r = that voxel as binary32 ((float)byte for u8); no arithmetic touches it afterwards.
+ *  4. OUTPUT (vv_stencil_volume's rule 6 for arithmetic results): f32 -> f32: r (NEAREST: the voxel's pattern, bit for bit).  f32 -> u8: the
+ *     classification index of r.  u8 -> f32: r / 255.0f, IEEE.  u8 -> u8: 0 if r is NaN or r < 0.5f; 255 if r >= 254.5f; otherwise
+ *     (int)(r + 0.5f) (NEAREST: the byte).  fill goes through the same stage.
+ *  5. LAYOUT: `out` is dense, x fastest, with the box's extents hi - lo.
+ *  6. What follows: (a) the result for a box is the crop of the whole grid's result, bit for bit.  (b) The identity m with dims = the volume's,
+ *     NEAREST and the volume's own type is the volume read back, byte for byte, for any dims up to VV_RESAMPLE_MAX_DIM ((uint32_t)(q * n) == X
+ *     and q < 1 for every X < n); so it is with TEX8 on u8 volumes (|fma(q, n, -0.5) - X| <= 2^-13: the weight rounds to 0, or to 1 on the voxel
+ *     below), and with TEX8 / EXACT on f32 volumes whose dims are powers of two (fma(q, n, -0.5) == X).  (c) Nothing depends on the pitch of the
+ *     source, on the 64-bit addressing build, on the launch geometry, on how the volume was loaded or on what `out` held.  (d) No byte beyond the
+ *     output's voxels is written, no byte outside the volume's allocation is read, padding is never data: addresses come from coordinates clamped
+ *     as the texture model clamps them, never from voxel values.  (e) Results are the same from run to run.
+ *  7. VALUE DOMAIN of f32 voxels: that of vv_load_volume_f32 under TEX8 / EXACT; NEAREST copies any pattern.
+ *  8. `stream` / out_on_device / staging as for vv_stencil_volume: a host `out` goes through a device buffer of the call's own, a device-`out`
+ *     call allocates nothing.  The linear volume is sampled (above 4 GiB with 64-bit slice bases, as vv_slice); volume, table, copies,
+ *     residency state and vv_last_frame_ms are not touched.
+ *  9. Errors, in this order.  VV_ERR_INVALID: NULL ctx / r / out.  VV_ERR_NO_VOLUME: no volume loaded.  VV_ERR_INVALID, each in turn: dims
+ *     outside 1..VV_RESAMPLE_MAX_DIM; a box that is not all zeros and not 0 <= lo < hi <= dims; a filter or out_type outside its enum; any of
+ *     m[0..11] or fill not finite; capacity (bytes) below the output's bytes (computed in 64 bits); a device f32 `out` that is not 4-byte
+ *     aligned; a device `out` whose byte range overlaps the context's linear volume allocation.  VV_ERR_NOMEM: the staging buffer of a host
+ *     `out` could not be allocated.  A refused call writes nothing and leaves the context usable.
+ * vv_resample_matrix (host only, binary64): R = Rz(euler[2]) * Ry(euler[1]) * Rx(euler[0]), angles in radians; A_rc = R_rc * (s_c / s_r) / zoom
+ * with s = scale (NULL or all zeros = (1, 1, 1)); t = centre - A * (0.5, 0.5, 0.5); m = [A | t], each entry rounded once to binary32.  Zero
+ * angles, zoom 1 and centre (0.5, 0.5, 0.5) give the identity exactly for any scale; zoom 2 gives diag 0.5 and t = 0.25.  VV_ERR_INVALID: NULL
+ * euler / centre / m, an input that is not finite, zoom not > 0, a scale component not > 0 when not all are zero.                          */
+typedef enum { VV_RESAMPLE_TEX8 = 0, VV_RESAMPLE_EXACT = 1, VV_RESAMPLE_NEAREST = 2 } vv_resample_filter;  /* 0, 1 = the values of vv_filter */
+#define VV_RESAMPLE_MAX_DIM 16384
+typedef struct vv_resample {
+    int   dims[3];               /* output grid m_x, m_y, m_z, each 1..VV_RESAMPLE_MAX_DIM */
+    int   box_lo[3], box_hi[3];  /* the part of the OUTPUT grid to compute, lo inclusive, hi exclusive; all six 0 = the whole grid */
+    int   filter;                /* vv_resample_filter */
+    int   out_type;              /* VV_VOXEL_U8 or VV_VOXEL_F32, whatever the loaded volume's type */
+    float m[12];                 /* row-major 3 x 4: output coordinates q -> texture coordinates p of the loaded volume */
+    float fill;                  /* r of a sample outside the volume, storage units of the source */
+} vv_resample;                   /* 96 bytes; offsets 0, 12, 24, 36, 40, 44, 92 */
+int  vv_resample_volume(vv_context *ctx, const vv_resample *r, void *out, size_t capacity,
+                        int out_on_device, void *stream);
+int  vv_resample_matrix(const float euler[3], float zoom, const float centre[3], const float scale[3] /* or NULL */,
+                        float m[12]);   /* host only, no context */
+
 /* The first pass on its own (firstpass.vert:6, firstpass.frag:4, glwidget.cpp:198-228): the
  * RGBA8 images the reference's two FBOs would hold for this camera -- cube-space entry (front
  * faces) and exit (back faces) positions, UNORM8-rounded, alpha 255 where a face is visible and

@@ -30,6 +30,7 @@ struct vv_knobs {
     int hist_blocks = -1;                   // VV_HIST_BLOCKS: cap on hist_kernel's grid (tests drive its grid-stride loop with it)
     int derive_blocks = -1;                 // VV_DERIVE_BLOCKS: the same for derive_kernel
     int stencil_blocks = -1;                // VV_STENCIL_BLOCKS: the same for the stencil kernels (their loop over (tile, z segment) items)
+    int resample_blocks = -1;               // VV_RESAMPLE_BLOCKS: the same for resample_kernel (its loop over tiles)
     // finalize_layout: VV_PITCH_PAD = bytes of row padding (0 or anything that is no number: rows stay dense; not a multiple of 16 in 16..4096: the default),
     // VV_PITCH_FORCE (set: any row length is padded), VV_PITCH_ROWS = extra rows per slice (0..64, anything else: the default)
     int pitch_pad = 32, pitch_rows = -1; bool pitch_force = false;
@@ -43,7 +44,7 @@ struct vv_knobs {
         zfast = geti("VV_ZFAST", -1); force_big = getenv("VV_FORCE_BIG") != nullptr;
         rect = geti("VV_RECT", -1); lpt = geti("VV_LPT", -1); lpt_run = geti("VV_LPT_RUN", -1); phong_bricks = geti("VV_PHONG_BRICKS", -1);
         hist_blocks = geti("VV_HIST_BLOCKS", -1); derive_blocks = geti("VV_DERIVE_BLOCKS", -1);
-        stencil_blocks = geti("VV_STENCIL_BLOCKS", -1);
+        stencil_blocks = geti("VV_STENCIL_BLOCKS", -1); resample_blocks = geti("VV_RESAMPLE_BLOCKS", -1);
         const int pad = geti("VV_PITCH_PAD", 32);
         pitch_pad = pad <= 0 ? 0 : ((pad >= 16 && pad <= 4096 && pad % 16 == 0) ? pad : 32);
         pitch_force = getenv("VV_PITCH_FORCE") != nullptr; pitch_rows = geti("VV_PITCH_ROWS", -1);
@@ -1925,6 +1926,75 @@ int vv_stencil_volume(vv_context *c, const vv_stencil *d, void *out, size_t capa
             rc = fail(c, VV_ERR_DEVICE, "vv_stencil_volume: volume allocation is not what the kernel expects");
         else {
             launch_stencil(A, c->n_cu, c->knobs.stencil_blocks, st);
+            rc = finish_call(c, stream, st, &b, 1);
+        }
+    }
+    if (tmp) (void)hipFree(tmp);
+    return rc;
+}
+
+// ---- resampled volumes (include/volviz.h: vv_resample_volume) -------------------------------
+// The header's rule 9 behind the NULL checks, in its order; fills the box (lo, hi) and the output's bytes.
+static int resample_check(vv_context *c, const vv_resample *r, const void *out, size_t capacity, int out_on_device, int lo[3], int hi[3], size_t *bytes)
+{
+    if (!c->d_vol) return fail(c, VV_ERR_NO_VOLUME, "vv_resample_volume: no volume loaded");
+    for (int a = 0; a < 3; ++a)
+        if (r->dims[a] < 1 || r->dims[a] > VV_RESAMPLE_MAX_DIM) return fail(c, VV_ERR_INVALID, "vv_resample_volume: dims must lie in 1..16384");
+    bool whole = true;
+    for (int a = 0; a < 3; ++a) whole = whole && r->box_lo[a] == 0 && r->box_hi[a] == 0;
+    for (int a = 0; a < 3; ++a) {
+        lo[a] = whole ? 0 : r->box_lo[a]; hi[a] = whole ? r->dims[a] : r->box_hi[a];
+        if (!(0 <= lo[a] && lo[a] < hi[a] && hi[a] <= r->dims[a])) return fail(c, VV_ERR_INVALID, "vv_resample_volume: the box must satisfy 0 <= lo < hi <= dims on every axis (or be all zeros)");
+    }
+    if (r->filter != VV_RESAMPLE_TEX8 && r->filter != VV_RESAMPLE_EXACT && r->filter != VV_RESAMPLE_NEAREST)
+        return fail(c, VV_ERR_INVALID, "vv_resample_volume: filter must be VV_RESAMPLE_TEX8, VV_RESAMPLE_EXACT or VV_RESAMPLE_NEAREST");
+    if (r->out_type != VV_VOXEL_U8 && r->out_type != VV_VOXEL_F32) return fail(c, VV_ERR_INVALID, "vv_resample_volume: out_type must be VV_VOXEL_U8 or VV_VOXEL_F32");
+    for (int k = 0; k < 12; ++k)
+        if (!std::isfinite(r->m[k])) return fail(c, VV_ERR_INVALID, "vv_resample_volume: the matrix must be finite");
+    if (!std::isfinite(r->fill)) return fail(c, VV_ERR_INVALID, "vv_resample_volume: fill must be finite");
+    *bytes = (size_t)(hi[0] - lo[0]) * (size_t)(hi[1] - lo[1]) * (size_t)(hi[2] - lo[2]) * (r->out_type == VV_VOXEL_F32 ? 4 : 1);
+    if (capacity < *bytes) return fail(c, VV_ERR_INVALID, "vv_resample_volume: capacity is below the output's bytes");
+    if (out_on_device && r->out_type == VV_VOXEL_F32 && ((uintptr_t)out & 3) != 0) return fail(c, VV_ERR_INVALID, "vv_resample_volume: a device f32 out must be 4-byte aligned");
+    if (out_on_device && (uintptr_t)out < (uintptr_t)c->d_vol + c->alloc_bytes && (uintptr_t)c->d_vol < (uintptr_t)out + *bytes)
+        return fail(c, VV_ERR_INVALID, "vv_resample_volume: out overlaps the loaded volume (the pass is not in place)");
+    return VV_OK;
+}
+
+int vv_resample_volume(vv_context *c, const vv_resample *r, void *out, size_t capacity, int out_on_device, void *stream)
+{
+    if (!c) return fail(nullptr, VV_ERR_INVALID, "vv_resample_volume: NULL context");
+    if (!r || !out) return fail(c, VV_ERR_INVALID, "vv_resample_volume: NULL argument");
+    int lo[3], hi[3];
+    size_t bytes = 0;
+    int rc = resample_check(c, r, out, capacity, out_on_device, lo, hi, &bytes);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    // a host volume goes through a device buffer of this call's own, as vv_stencil_volume's; a device out allocates nothing
+    void *tmp = nullptr;
+    if (!out_on_device && hipMalloc(&tmp, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, VV_ERR_NOMEM, "vv_resample_volume: no device memory for the staging buffer of a host out");
+    }
+    hipStream_t st;
+    CallBuf b = {out, bytes, !out_on_device, false, true, 0, tmp, nullptr};
+    if ((rc = stage_call(c, stream, &st, &b, 1)) == VV_OK) {
+        ResampleArgs A;
+        memset(&A, 0, sizeof A);
+        A.V = view_of(c, MB_LINEAR); A.out = b.dev;
+        A.src_type = c->vtype; A.out_type = r->out_type; A.filter = r->filter;
+        for (int a = 0; a < 3; ++a) {
+            A.lo[a] = lo[a]; A.b[a] = (uint32_t)(hi[a] - lo[a]);
+            const volatile float inv = 1.0f / (float)r->dims[a];        // one IEEE binary32 division
+            A.inv[a] = inv;
+        }
+        memcpy(A.m, r->m, sizeof A.m); A.fill = r->fill;
+        // what launch_resample is promised: the weight-0 corners of the last voxel's sample (one slice and one row on, two dwords) lie inside the allocation
+        const size_t size = c->vtype == VV_VOXEL_F32 ? 4 : 1;
+        const size_t reach = ((size_t)c->nz + 1) * c->slice_pitch + (size_t)c->nx * size + 8;
+        if (reach > c->alloc_bytes || (size == 4 && (((uintptr_t)c->d_vol | c->row_pitch | c->slice_pitch) & 3) != 0))
+            rc = fail(c, VV_ERR_DEVICE, "vv_resample_volume: volume allocation is not what the kernel expects");
+        else {
+            launch_resample(A, c->n_cu, c->knobs.resample_blocks, st);
             rc = finish_call(c, stream, st, &b, 1);
         }
     }

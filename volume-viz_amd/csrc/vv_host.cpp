@@ -76,6 +76,37 @@ int vv_stencil_taps(int shape, int radius, float sigma, float taps[5])
     return VV_OK;
 }
 
+// include/volviz.h: the matrix of vv_resample for a rotation, a zoom about a centre and the scales of an anisotropic volume (binary64)
+int vv_resample_matrix(const float euler[3], float zoom, const float centre[3], const float scale[3], float m[12])
+{
+    if (!euler || !centre || !m) return VV_ERR_INVALID;
+    double s[3] = {1.0, 1.0, 1.0};
+    if (!(std::isfinite(zoom) && zoom > 0.f)) return VV_ERR_INVALID;
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(euler[a]) || !std::isfinite(centre[a]) || (scale && !std::isfinite(scale[a]))) return VV_ERR_INVALID;
+    if (scale && !(scale[0] == 0.f && scale[1] == 0.f && scale[2] == 0.f))
+        for (int a = 0; a < 3; ++a) {
+            if (!(scale[a] > 0.f)) return VV_ERR_INVALID;
+            s[a] = (double)scale[a];
+        }
+    const double cx = std::cos((double)euler[0]), sx = std::sin((double)euler[0]), cy = std::cos((double)euler[1]), sy = std::sin((double)euler[1]);
+    const double cz = std::cos((double)euler[2]), sz = std::sin((double)euler[2]);
+    // R = Rz Ry Rx
+    const double R[3][3] = {{cz * cy, cz * sy * sx - sz * cx, cz * sy * cx + sz * sx},
+                            {sz * cy, sz * sy * sx + cz * cx, sz * sy * cx - cz * sx},
+                            {0.0 - sy, cy * sx,               cy * cx}};      // (0 - sy: no -0.0 in the identity)
+    float out[12];
+    for (int r = 0; r < 3; ++r) {
+        double A[3];
+        for (int k = 0; k < 3; ++k) A[k] = R[r][k] * (s[k] / s[r]) / (double)zoom;
+        const double t = (double)centre[r] - ((A[0] * 0.5 + A[1] * 0.5) + A[2] * 0.5);
+        for (int k = 0; k < 3; ++k) out[4 * r + k] = (float)A[k];
+        out[4 * r + 3] = (float)t;
+    }
+    memcpy(m, out, sizeof out);
+    return VV_OK;
+}
+
 // glwidget.cpp:678-689: table and scale by the file name's ending (QString::endsWith, case-sensitive)
 int vv_dataset_preset(const char *path, int *tf_preset, float scale[3])
 {

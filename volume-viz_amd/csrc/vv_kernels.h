@@ -160,6 +160,18 @@ struct StencilArgs {
     float gscale[3];
 };
 void launch_stencil(const StencilArgs &a, int n_cu, int max_blocks /* <= 0: one block per (tile, z segment) */, hipStream_t s);
+// resampled volumes (vv_resample.hip): the box lo / b (voxels, x, y, z) of an output grid sampled from the linear volume V into a dense volume of
+// the box's extents at `out` (vv_resample of include/volviz.h, checked by the caller).  inv[a] = 1.0f / (float)dims[a] of the grid; m, fill,
+// filter: the descriptor's.  The caller vouches that V is the linear layout as slice_kernel takes it (its padding behind the last slice
+// included) and that `out` holds b[0] * b[1] * b[2] voxels of out_type outside it.
+struct ResampleArgs {
+    VolumeView V; void *out;
+    int src_type, out_type, filter;         // vv_voxel_type (2 x), vv_resample_filter
+    int32_t lo[3];
+    uint32_t b[3];
+    float inv[3], m[12], fill;
+};
+void launch_resample(const ResampleArgs &a, int n_cu, int max_blocks /* <= 0: one block per tile */, hipStream_t s);
 void launch_first_pass(const FrameParams &P, uint32_t *front, uint32_t *back, hipStream_t s);
 
 size_t generate_scratch_floats(int nx, int ny, int nz, int n);

@@ -35,6 +35,8 @@ REDUCE_MEAN, REDUCE_MAX, REDUCE_MIN = 0, 1, 2    # vv_reduce_mode
 STENCIL_SEPARABLE, STENCIL_MEDIAN, STENCIL_GRADMAG = 0, 1, 2     # vv_stencil_kind
 STENCIL_MAX_RADIUS = 4
 TAPS_BOX, TAPS_BINOMIAL, TAPS_GAUSS = 0, 1, 2    # vv_taps_shape
+RESAMPLE_TEX8, RESAMPLE_EXACT, RESAMPLE_NEAREST = 0, 1, 2        # vv_resample_filter
+RESAMPLE_MAX_DIM = 16384
 RAYS_IMAGES, RAYS_ANALYTIC = 0, 1
 TF_ENGINE, TF_HEAD, TF_MRI = 0, 1, 2
 # `stream` arguments: 0/None = the context's own stream, synchronous; STREAM_DEFAULT_ASYNC = the device's default (null)
@@ -97,6 +99,11 @@ class vv_stencil(C.Structure):            # 116 bytes
                 ("taps", (C.c_float * 5) * 3), ("gscale", C.c_float * 3)]
 
 
+class vv_resample(C.Structure):           # 96 bytes
+    _fields_ = [("dims", C.c_int * 3), ("box_lo", C.c_int * 3), ("box_hi", C.c_int * 3), ("filter", C.c_int), ("out_type", C.c_int),
+                ("m", C.c_float * 12), ("fill", C.c_float)]
+
+
 @dataclass
 class Histogram:
     """vv_histogram as numpy values: counts uint64[256], voxels, nan_voxels, vmin / vmax as np.float32 (bit for bit what the library wrote)."""
@@ -129,12 +136,12 @@ EXPORTS = [
     "vv_load_volume_stream_slices_async", "vv_load_volume_stream_wait_source", "vv_dataset_preset", "vv_debug_last_launch", "vv_set_frame_timing", "vv_debug_screen_rect",
     "vv_render_mip", "vv_classify_indices", "vv_render_iso", "vv_slice_slab", "vv_slice_advanced_slab",
     "vv_volume_histogram", "vv_histogram_indices", "vv_render_projection", "vv_debug_read_layout",
-    "vv_derive_dims", "vv_derive_volume", "vv_stencil_volume", "vv_stencil_taps",
+    "vv_derive_dims", "vv_derive_volume", "vv_stencil_volume", "vv_stencil_taps", "vv_resample_volume", "vv_resample_matrix",
 ]
 # entry points a variant library built from an earlier tree (A/B tools, load_library(path)) may lack
 _NEWER_EXPORTS = ("vv_render_mip", "vv_classify_indices", "vv_render_iso", "vv_slice_slab", "vv_slice_advanced_slab",
                   "vv_volume_histogram", "vv_histogram_indices", "vv_render_projection", "vv_debug_read_layout",
-                  "vv_derive_dims", "vv_derive_volume", "vv_stencil_volume", "vv_stencil_taps")
+                  "vv_derive_dims", "vv_derive_volume", "vv_stencil_volume", "vv_stencil_taps", "vv_resample_volume", "vv_resample_matrix")
 
 _lib = None
 _libs = {}
@@ -193,6 +200,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     if hasattr(lib, "vv_stencil_volume"):
         lib.vv_stencil_volume.argtypes = [vp, C.POINTER(vv_stencil), vp, sz, i, vp]
         lib.vv_stencil_taps.argtypes = [i, i, f, C.POINTER(f * 5)]
+    if hasattr(lib, "vv_resample_volume"):
+        lib.vv_resample_volume.argtypes = [vp, C.POINTER(vv_resample), vp, sz, i, vp]
+        lib.vv_resample_matrix.argtypes = [C.POINTER(f * 3), f, C.POINTER(f * 3), C.POINTER(f * 3), C.POINTER(f * 12)]
     lib.vv_generate_ellipsoids.argtypes = [vp, vp, i, i, i, i, i, vp, vp, vp, vp]
     lib.vv_generate_default_brain.argtypes = [vp, vp, i, i, i, i, vp]
     lib.vv_draw_ellipsoid.argtypes = [vp, vp, i, i, i, i, vp, vp, C.c_uint8, vp]
@@ -811,6 +821,45 @@ class Context:
         """The magnitude of the central-difference gradient, each axis multiplied by gscale[a] first."""
         return self.stencil(STENCIL_GRADMAG, box, out_type, gscale=gscale)
 
+    # vv_resample_volume (no reference counterpart)
+    def _resample(self, dims, matrix, filter, fill, out_type, box) -> vv_resample:
+        """dims = (mx, my, mz) of the output grid; matrix: 12 floats (row-major 3 x 4) or None = the identity; box = ((x0, y0, z0), (x1, y1, z1))
+        of the output grid or None = the whole grid; out_type None = the volume's type."""
+        d = vv_resample()
+        d.dims[:] = [int(v) for v in dims]
+        if box is not None:
+            d.box_lo[:] = [int(v) for v in box[0]]
+            d.box_hi[:] = [int(v) for v in box[1]]
+        d.filter = int(filter)
+        d.out_type = self.volume_type() if out_type is None else int(out_type)
+        m = (1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0) if matrix is None else np.asarray(matrix, np.float32).reshape(12)
+        d.m[:] = [float(v) for v in m]
+        d.fill = float(fill)
+        return d
+
+    @staticmethod
+    def _resample_dims(d: vv_resample):
+        if not any(d.box_lo) and not any(d.box_hi):
+            return int(d.dims[0]), int(d.dims[1]), int(d.dims[2])
+        return tuple(max(int(h) - int(l), 0) for l, h in zip(d.box_lo, d.box_hi))
+
+    def resample(self, dims, matrix=None, filter=RESAMPLE_TEX8, fill=0.0, out_type=None, box=None, prefill=None) -> np.ndarray:
+        """vv_resample_volume into a host array [bz, by, bx] of uint8 or float32 (the box's extents).  `prefill`: the byte the buffer holds before
+        the call (the result does not depend on it)."""
+        d = self._resample(dims, matrix, filter, fill, out_type, box)
+        bx, by, bz = self._resample_dims(d)
+        out = np.empty((bz, by, bx), np.float32 if d.out_type == VOXEL_F32 else np.uint8)
+        if prefill is not None:
+            out.view(np.uint8)[...] = prefill
+        self._chk(self.lib.vv_resample_volume(self.h, C.byref(d), out.ctypes.data if out.size else None, out.nbytes, 0, None))
+        return out
+
+    def resample_device(self, out_ptr: int, capacity: int, dims, matrix=None, filter=RESAMPLE_TEX8, fill=0.0, out_type=None, box=None, stream: int = 0):
+        """vv_resample_volume into a device buffer of `capacity` bytes, enqueued on `stream`; returns the output's (bx, by, bz)."""
+        d = self._resample(dims, matrix, filter, fill, out_type, box)
+        self._chk(self.lib.vv_resample_volume(self.h, C.byref(d), out_ptr or None, int(capacity), 1, stream or None))
+        return self._resample_dims(d)
+
     # VolumeGenerator::drawEllipsoid x n / drawDefaultBrain (volumegenerator.cpp:31-119)
     def generate_ellipsoids(self, nx: int, ny: int, nz: int, centers, axes, colors) -> np.ndarray:
         centers = np.ascontiguousarray(centers, np.float32).reshape(-1, 3)
@@ -852,6 +901,18 @@ def stencil_taps(shape: int, radius: int, sigma: float = 0.0) -> np.ndarray:
     if rc != 0:
         raise VolvizError(rc, "vv_stencil_taps: bad shape, radius or sigma")
     return np.array(t[:], np.float32)
+
+
+def resample_matrix(euler=(0.0, 0.0, 0.0), zoom: float = 1.0, centre=(0.5, 0.5, 0.5), scale=None) -> np.ndarray:
+    """vv_resample_matrix: float32[12], the row-major 3 x 4 matrix of Context.resample for a rotation Rz Ry Rx (radians), a zoom about `centre`
+    (texture coordinates) and the voxel scales of an anisotropic volume."""
+    f3 = C.c_float * 3
+    m = (C.c_float * 12)()
+    s = None if scale is None else C.byref(f3(*[float(v) for v in scale]))
+    rc = load_library().vv_resample_matrix(C.byref(f3(*[float(v) for v in euler])), float(zoom), C.byref(f3(*[float(v) for v in centre])), s, C.byref(m))
+    if rc != 0:
+        raise VolvizError(rc, "vv_resample_matrix: bad angle, zoom, centre or scale")
+    return np.array(m[:], np.float32)
 
 
 def cut_plane_canonical(orientation: int, displace: float):
