@@ -159,6 +159,27 @@ def test_draw_in_place_host_and_device_buffers_agree(loaded, torch_side):
     assert 200 in vol and FILL in vol
 
 
+def test_draw_in_place_uploads_the_host_volume(loaded):
+    """vv_draw_ellipsoid on a host volume of 20 x 6 x 3 that holds a byte pattern (rows of 20: a 16-voxel chunk and a tail): the call's staging buffer
+    starts as the caller's bytes, so the result is that of the same call on a device copy of the volume, and the voxels outside the ellipsoid keep
+    their bytes in both."""
+    import torch
+    ctx = loaded["fresh"]
+    nx, ny, nz = 20, 6, 3
+    color = 200
+    pattern = (1 + np.arange(nx * ny * nz) * 37 % 199).astype(np.uint8)                    # 1..199: never the colour
+    assert len(np.unique(pattern)) > 100 and color not in pattern
+    center = np.array([0.45, 0.5, 0.5], np.float32); axes = np.array([0.3, 0.35, 0.4], np.float32)
+    host = pattern.copy()
+    dev = torch.from_numpy(pattern.copy()).to(torch.device("cuda", 0))
+    torch.cuda.synchronize()
+    for ptr, on_device in ((host.ctypes.data, 0), (dev.data_ptr(), 1)):
+        assert ctx.lib.vv_draw_ellipsoid(ctx.h, ptr, on_device, nx, ny, nz, center.ctypes.data, axes.ctypes.data, color, None) == 0
+    assert np.array_equal(host, dev.cpu().numpy()), "the host volume differs from the device volume"
+    inside = host == color
+    assert 0 < inside.sum() < host.size and np.array_equal(host[~inside], pattern[~inside]), "voxels outside the ellipsoid lost their bytes"
+
+
 # ---- error precedence ------------------------------------------------------------------------------------------------------------------------
 
 _SC = (C.c_float * 3)(1.0, 1.0, 1.0)

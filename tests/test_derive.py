@@ -2,8 +2,8 @@
 
 CPU part: the model is tied to independent statements (identity, the binary64 mean, composition of maxima, the histogram model) and the library and
 the binding export the calls.  GPU part: the kernel equals the model on every volume, mode, output type, factor, box and window of the issue -- u8 as
-bytes, f32 as uint32 patterns (NaN results of MEAN: NaN on both sides) --, into a device buffer prefilled with 0xA5 whose bytes behind the output must
-survive, and through the host path; on every layout, launch geometry and load path; and the calls leave the context alone."""
+bytes, f32 as uint32 patterns (NaN results of MEAN: NaN on both sides) --, into a device buffer prefilled with 0xA5 whose bytes before and behind the
+output must survive, and through the host path; on every layout, launch geometry and load path; and the calls leave the context alone."""
 import ctypes as C
 import functools
 import itertools
@@ -15,12 +15,12 @@ import pytest
 import derive_model as DM
 import hist_model as HM
 import test_hist as TH
+import volume_out as VO
 import volviz_amd as vv
+from volume_out import GARBAGE, GUARD
 
 f32 = np.float32
 ERR_INVALID, ERR_NO_VOLUME = -1, -2
-GARBAGE = 0xA5
-GUARD = 64                                                 # bytes behind the output that must keep GARBAGE
 TF = TH.TF
 MODES = (DM.MEAN, DM.MAX, DM.MIN)
 MODE_IDS = ("mean", "max", "min")
@@ -55,13 +55,7 @@ def _reduced(volname, box, factor, mode):
 
 
 def _check(got, want, what, mean_f32):
-    bad = DM.same(got, want, nan_free_for_all=mean_f32)
-    if len(bad):
-        i = tuple(bad[0])
-        g, w = got[i], want[i]
-        if got.dtype == np.float32:
-            g, w = f"{g!r} ({int(np.asarray(g).view(np.uint32)):#x})", f"{w!r} ({int(np.asarray(w).view(np.uint32)):#x})"
-        raise AssertionError(f"{what}: {len(bad)} of {got.size} voxels differ, first at (z, y, x) = {i}: {g} vs {w}")
+    VO.report(got, want, DM.same(got, want, nan_free_for_all=mean_f32), what)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -155,43 +149,22 @@ def test_derive_dims_is_the_ceiling_formula():
 # GPU
 # ---------------------------------------------------------------------------------------------------------------------
 def _clear_env(monkeypatch):
-    for k in LAYOUT_KNOBS:
-        monkeypatch.delenv(k, raising=False)
+    VO.clear_env(monkeypatch, LAYOUT_KNOBS)
 
 
 def _load(ctx, monkeypatch, volname):
-    _clear_env(monkeypatch)
-    ctx.load_volume(_volume(volname), TF)                       # (the knobs are read at volume load)
+    VO.load(ctx, monkeypatch, LAYOUT_KNOBS, _volume(volname), TF)
 
 
-class _DeviceOut:
-    """A device buffer the derive calls write into: GARBAGE everywhere before each call, the output at an offset that changes from call to call
-    (0, 4, 8, 12 bytes; u8 outputs 0, 1, 2, 3), GUARD bytes behind it that must survive."""
-
-    def __init__(self, nbytes):
-        import torch
-        self.torch = torch
-        self.buf = torch.empty(nbytes + GUARD + 16, dtype=torch.uint8, device=torch.device("cuda", 0))
-        self.calls = 0
-
-    def run(self, ctx, dtype, **kw):
-        self.calls += 1
-        off = (self.calls % 4) * (4 if dtype == np.float32 else 1)
-        m = ctx.derive_dims(kw.get("box"), kw.get("factor", 1))
-        nbytes = m[0] * m[1] * m[2] * np.dtype(dtype).itemsize
-        assert off + nbytes + GUARD <= self.buf.numel()
-        self.buf.fill_(GARBAGE)
-        self.torch.cuda.synchronize()
-        got_m = ctx.derive_device(self.buf.data_ptr() + off, nbytes, **kw)          # no stream: complete on return
-        assert got_m == m
-        raw = self.buf.cpu().numpy()
-        assert (raw[:off] == GARBAGE).all() and (raw[off + nbytes:] == GARBAGE).all(), f"bytes outside the output were written ({kw})"
-        return raw[off:off + nbytes].copy().view(dtype).reshape(m[2], m[1], m[0])
+def _device_run(dev, ctx, dtype, **kw):
+    """vv_derive_volume into the guarded device buffer: of the extents vv_derive_dims gives, which the call must return too."""
+    m = ctx.derive_dims(kw.get("box"), kw.get("factor", 1))
+    return dev.run(lambda ptr, capacity: ctx.derive_device(ptr, capacity, **kw), m[::-1], dtype, kw)          # no stream: complete on return
 
 
 def _sweep(ctx, volname, vol, modes, factors, boxes, windows, reduced, what, host_too=True):
     """Every (mode, factor, box, output type, window) against the model: device output with guard; the host path without a window."""
-    dev = _DeviceOut(vol.size * 4)
+    dev = VO.DeviceOut(vol.size * 4)
     for mode, factor, box in itertools.product(modes, factors, boxes):
         r = reduced(box, factor, mode)
         mean_f32 = mode == DM.MEAN and vol.dtype == np.float32
@@ -205,7 +178,7 @@ def _sweep(ctx, volname, vol, modes, factors, boxes, windows, reduced, what, hos
                 continue
             want = DM.finish(r, out_type, window)
             dtype = np.float32 if out_type == DM.F32 else np.uint8
-            _check(dev.run(ctx, dtype, **kw), want, tag + " (device)", mean_f32)
+            _check(_device_run(dev, ctx, dtype, **kw), want, tag + " (device)", mean_f32)
             if host_too and window is None:
                 _check(ctx.derive(prefill=GARBAGE, **kw), want, tag + " (host)", mean_f32)
 

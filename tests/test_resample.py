@@ -21,12 +21,12 @@ import derive_model as DM
 import hist_model as HM
 import resample_model as RM
 import test_hist as TH
+import volume_out as VO
 import volviz_amd as vv
+from volume_out import GARBAGE, GUARD, bits as _bits
 
 f32 = np.float32
 ERR_INVALID, ERR_NO_VOLUME = -1, -2
-GARBAGE = 0xA5
-GUARD = 64                                                 # bytes before and behind the output that must keep GARBAGE
 TF = TH.TF
 FILTERS = (RM.TEX8, RM.EXACT, RM.NEAREST)
 TILES = ((32, 8, 4), (32, 4, 4))                           # resample_kernel's tiles in (x, y, z): kRsTX, resample_tile_y(4) / resample_tile_y(2), kRsTZ of csrc/vv_resample.hip
@@ -112,17 +112,7 @@ def _whole(volname, dims, matname, filt, fill):
 
 def _check(got, want, what):
     assert got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, want.shape, got.dtype, want.dtype)
-    bad = RM.same(got, want)
-    if len(bad):
-        i = tuple(bad[0])
-        g, w = got[i], want[i]
-        if got.dtype == np.float32:
-            g, w = f"{g!r} ({int(np.asarray(g).view(np.uint32)):#x})", f"{w!r} ({int(np.asarray(w).view(np.uint32)):#x})"
-        raise AssertionError(f"{what}: {len(bad)} of {got.size} voxels differ, first at (z, y, x) = {i}: {g} vs {w}")
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, f32).view(np.uint32)
+    VO.report(got, want, RM.same(got, want), what)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -336,38 +326,11 @@ def test_model_exact_filter_against_grid_sample():
 # GPU
 # ---------------------------------------------------------------------------------------------------------------------
 def _clear_env(monkeypatch):
-    for k in LAYOUT_KNOBS:
-        monkeypatch.delenv(k, raising=False)
+    VO.clear_env(monkeypatch, LAYOUT_KNOBS)
 
 
 def _load(ctx, monkeypatch, volname):
-    _clear_env(monkeypatch)
-    ctx.reread_env()
-    ctx.load_volume(_volume(volname), TF)
-
-
-class _DeviceOut:
-    """A device buffer the calls write into: GARBAGE everywhere before each call, the output GUARD bytes in plus an offset that changes from
-    call to call (0, 4, 8, 12 bytes; u8 outputs 0, 1, 2, 3); the bytes before and behind it must survive."""
-
-    def __init__(self, nbytes):
-        import torch
-        self.torch = torch
-        self.buf = torch.empty(nbytes + 2 * GUARD + 16, dtype=torch.uint8, device=torch.device("cuda", 0))
-        self.calls = 0
-
-    def run(self, ctx, shape, dtype, dims, **kw):
-        self.calls += 1
-        off = GUARD + (self.calls % 4) * (4 if dtype == np.float32 else 1)
-        nbytes = int(np.prod(shape)) * np.dtype(dtype).itemsize
-        assert off + nbytes + GUARD <= self.buf.numel()
-        self.buf.fill_(GARBAGE)
-        self.torch.cuda.synchronize()
-        m = ctx.resample_device(self.buf.data_ptr() + off, nbytes, dims, **kw)         # no stream: complete on return
-        assert tuple(m) == tuple(shape[::-1])
-        raw = self.buf.cpu().numpy()
-        assert (raw[:off] == GARBAGE).all() and (raw[off + nbytes:] == GARBAGE).all(), f"bytes outside the output were written ({dims}, {kw})"
-        return raw[off:off + nbytes].copy().view(dtype).reshape(shape)
+    VO.load(ctx, monkeypatch, LAYOUT_KNOBS, _volume(volname), TF)
 
 
 def _run_case(ctx, dev, volname, dims, matname, filt, fill, boxes, host_boxes, vol=None, wants=None):
@@ -379,7 +342,8 @@ def _run_case(ctx, dev, volname, dims, matname, filt, fill, boxes, host_boxes, v
             want = np.ascontiguousarray(HM.crop(wants[out_type], box))
             tag = f"{volname} grid {dims} matrix {matname} filter {filt} fill {fill} box {box} out {out_type}"
             kw = dict(matrix=MATS[matname], filter=filt, fill=fill, out_type=out_type, box=box)
-            _check(dev.run(ctx, want.shape, want.dtype, dims, **kw), want, tag + " (device)")
+            got = dev.run(lambda ptr, capacity: ctx.resample_device(ptr, capacity, dims, **kw), want.shape, want.dtype, tag)          # no stream: complete on return
+            _check(got, want, tag + " (device)")
             if box in host_boxes:
                 _check(ctx.resample(dims, prefill=GARBAGE, **kw), want, tag + " (host)")
 
@@ -387,7 +351,7 @@ def _run_case(ctx, dev, volname, dims, matname, filt, fill, boxes, host_boxes, v
 def _sweep(ctx, volname, filters):
     vol = _volume(volname)
     grids = _grids(vol.shape)
-    dev = _DeviceOut(max(int(np.prod(g)) for g in grids) * 4)
+    dev = VO.DeviceOut(max(int(np.prod(g)) for g in grids) * 4)
     k = 0
     for dims in grids:
         for matname in (FEW if int(np.prod(dims)) > BIG_GRID else MATS):
@@ -477,7 +441,7 @@ def test_resample_layouts(kind, nx, knobs, monkeypatch):
             row = nx * vol.itemsize + 32
             rows = ny + 1 if "VV_PITCH_ROWS" in knobs else ny
             assert c.device_bytes()[0] == nz * rows * row + rows * row + 2 * row + 4096             # the volume is re-pitched
-        dev = _DeviceOut(33 * 17 * 9 * 4)
+        dev = VO.DeviceOut(33 * 17 * 9 * 4)
         for dims, matname, filt in LAYOUT_CASES:
             wants = tuple(RM.resample(vol, dims, MATS[matname], filt, fill, t) for t in (RM.U8, RM.F32))
             _run_case(c, dev, f"layout {kind} {knobs}", dims, matname, filt, fill, [None, ((1, 0, 1), (dims[0] - 1, dims[1], dims[2] - 1))], (None,), wants=wants)
@@ -528,7 +492,7 @@ def test_resample_load_paths(ctx, monkeypatch):
     dims = (33, 17, 9)
 
     def check(vol, what, filters):
-        out = _DeviceOut(33 * 17 * 9 * 4)
+        out = VO.DeviceOut(33 * 17 * 9 * 4)
         for matname, filt in (("rot_c", RM.TEX8), ("shear", RM.EXACT), ("identity", RM.NEAREST)):
             if filt in filters:
                 fill = _fill(vol, 1)

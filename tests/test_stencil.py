@@ -19,12 +19,12 @@ import derive_model as DM
 import hist_model as HM
 import stencil_model as SM
 import test_hist as TH
+import volume_out as VO
 import volviz_amd as vv
+from volume_out import GARBAGE, GUARD, bits as _bits
 
 f32 = np.float32
 ERR_INVALID, ERR_NO_VOLUME = -1, -2
-GARBAGE = 0xA5
-GUARD = 64                                                 # bytes before and behind the output that must keep GARBAGE
 TF = TH.TF
 KINDS = (SM.SEPARABLE, SM.MEDIAN, SM.GRADMAG)
 KIND_IDS = ("separable", "median", "gradmag")
@@ -83,13 +83,7 @@ def _arith(kind, radius):
 
 
 def _check(got, want, what, nan_free_for_all):
-    bad = SM.same(got, want, nan_free_for_all)
-    if len(bad):
-        i = tuple(bad[0])
-        g, w = got[i], want[i]
-        if got.dtype == np.float32:
-            g, w = f"{g!r} ({int(np.asarray(g).view(np.uint32)):#x})", f"{w!r} ({int(np.asarray(w).view(np.uint32)):#x})"
-        raise AssertionError(f"{what}: {len(bad)} of {got.size} voxels differ, first at (z, y, x) = {i}: {g} vs {w}")
+    VO.report(got, want, SM.same(got, want, nan_free_for_all), what)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -107,10 +101,6 @@ def test_library_and_binding_export_the_stencil_calls():
     s = vv.vv_stencil
     assert C.sizeof(s) == 116
     assert (s.box_lo.offset, s.box_hi.offset, s.kind.offset, s.out_type.offset, s.radius.offset, s.taps.offset, s.gscale.offset) == (0, 12, 24, 28, 32, 44, 104)
-
-
-def _bits(a):
-    return np.asarray(a, f32).view(np.uint32)
 
 
 def test_stencil_taps_closed_forms_and_errors():
@@ -266,37 +256,11 @@ def test_model_radius_zero_is_the_derive_model_at_factor_one(volname):
 # GPU
 # ---------------------------------------------------------------------------------------------------------------------
 def _clear_env(monkeypatch):
-    for k in LAYOUT_KNOBS:
-        monkeypatch.delenv(k, raising=False)
+    VO.clear_env(monkeypatch, LAYOUT_KNOBS)
 
 
 def _load(ctx, monkeypatch, volname):
-    _clear_env(monkeypatch)
-    ctx.load_volume(_volume(volname), TF)                       # (the knobs are read at volume load)
-
-
-class _DeviceOut:
-    """A device buffer the stencil calls write into: GARBAGE everywhere before each call, the output GUARD bytes in plus an offset that changes
-    from call to call (0, 4, 8, 12 bytes; u8 outputs 0, 1, 2, 3); the bytes before and behind it must survive."""
-
-    def __init__(self, nbytes):
-        import torch
-        self.torch = torch
-        self.buf = torch.empty(nbytes + 2 * GUARD + 16, dtype=torch.uint8, device=torch.device("cuda", 0))
-        self.calls = 0
-
-    def run(self, ctx, shape, dtype, kind, **kw):
-        self.calls += 1
-        off = GUARD + (self.calls % 4) * (4 if dtype == np.float32 else 1)
-        nbytes = int(np.prod(shape)) * np.dtype(dtype).itemsize
-        assert off + nbytes + GUARD <= self.buf.numel()
-        self.buf.fill_(GARBAGE)
-        self.torch.cuda.synchronize()
-        m = ctx.stencil_device(self.buf.data_ptr() + off, nbytes, kind, **kw)          # no stream: complete on return
-        assert tuple(m) == tuple(shape[::-1])
-        raw = self.buf.cpu().numpy()
-        assert (raw[:off] == GARBAGE).all() and (raw[off + nbytes:] == GARBAGE).all(), f"bytes outside the output were written ({kind}, {kw})"
-        return raw[off:off + nbytes].copy().view(dtype).reshape(shape)
+    VO.load(ctx, monkeypatch, LAYOUT_KNOBS, _volume(volname), TF)
 
 
 def _box_shape(vol, box):
@@ -311,7 +275,8 @@ def _run_case(ctx, dev, vol, r_whole, kind, boxes, host_boxes, what, **kw):
             want = _want(vol, r_whole, kind, box, out_type)
             dtype = np.float32 if out_type == SM.F32 else np.uint8
             tag = f"{what} kind {kind} box {box} out {out_type} {({k: v for k, v in kw.items() if k != 'taps'})}"
-            _check(dev.run(ctx, want.shape, dtype, kind, box=box, out_type=out_type, **kw), want, tag + " (device)", nan_ok)
+            got = dev.run(lambda ptr, capacity: ctx.stencil_device(ptr, capacity, kind, box=box, out_type=out_type, **kw), want.shape, dtype, tag)    # no stream: complete on return
+            _check(got, want, tag + " (device)", nan_ok)
             if box in host_boxes:
                 _check(ctx.stencil(kind, box, out_type, prefill=GARBAGE, **kw), want, tag + " (host)", nan_ok)
 
@@ -327,7 +292,7 @@ def _sep_cases():
 def _sweep(ctx, volname, kind):
     vol = _volume(volname)
     boxes = TH._boxes(vol.shape, 71)
-    dev = _DeviceOut(vol.size * 4)
+    dev = VO.DeviceOut(vol.size * 4)
     host_boxes = (None, boxes[-1])
     if kind == SM.SEPARABLE:
         for radius, tapset in _sep_cases():
@@ -409,7 +374,7 @@ def test_stencil_layouts(kind, nx, knobs, monkeypatch):
             row = nx * vol.itemsize + 32
             rows = ny + 1 if "VV_PITCH_ROWS" in knobs else ny
             assert c.device_bytes()[0] == nz * rows * row + rows * row + 2 * row + 4096             # the volume is re-pitched
-        dev = _DeviceOut(vol.size * 4)
+        dev = VO.DeviceOut(vol.size * 4)
         boxes = TH._boxes(vol.shape, 43)
         for kd, kw in _all_kind_cases():
             _run_case(c, dev, vol, SM.result(vol, kd, None, **kw), kd, boxes, (None,), f"layout {knobs}", **kw)
@@ -460,7 +425,7 @@ def test_stencil_load_paths(ctx, monkeypatch):
     boxes = (None, ((2, 1, 3), (11, 9, 10)))
 
     def check(vol, what):
-        out = _DeviceOut(vol.size * 4)
+        out = VO.DeviceOut(vol.size * 4)
         for kd, kw in _all_kind_cases():
             _run_case(ctx, out, vol, SM.result(vol, kd, None, **kw), kd, boxes, (), what, **kw)
 

@@ -153,6 +153,8 @@ static void drop_copies(vv_context *c)
     c->view_key_valid = false;             // (a new volume: the launch-policy estimate taken from first-pass images is re-taken)
 }
 
+static size_t voxel_bytes(int vtype) { return vtype == VV_VOXEL_F32 ? 4 : 1; }
+
 // ---- the linear volume: checked, given up and allocated in one place each (the loaders, the streamed upload, vv_shutdown) -------------------
 // `who`: the caller's message prefix; bad_dims / bad_type: its texts for those two findings
 static int check_volume(vv_context *c, const char *who, const char *bad_dims, const char *bad_type, int vtype, int nx, int ny, int nz)
@@ -160,7 +162,7 @@ static int check_volume(vv_context *c, const char *who, const char *bad_dims, co
     const std::string w(who);
     if (nx < 1 || ny < 1 || nz < 1) return fail(c, VV_ERR_INVALID, w + bad_dims);
     if (vtype != VV_VOXEL_U8 && vtype != VV_VOXEL_F32) return fail(c, VV_ERR_INVALID, w + bad_type);
-    const size_t vsz = vtype == VV_VOXEL_F32 ? 4 : 1;
+    const size_t vsz = voxel_bytes(vtype);
     if ((size_t)nx * ny * vsz > 0xFFFFFFF0ull) return fail(c, VV_ERR_INVALID, w + "one slice must stay below 4 GiB");
     if ((size_t)nx * vsz >= (1u << 24) || ny >= (1 << 24) || nz >= (1 << 24))
         return fail(c, VV_ERR_INVALID, w + "a volume row must be below 16 MiB and each dimension below 2^24");
@@ -181,7 +183,7 @@ static int release_volume(vv_context *c)
 // corner fetches of edge samples land there instead of needing index clamps (see vv_device.h VolumeView).
 static int alloc_volume(vv_context *c, int vtype, int nx, int ny, int nz, hipStream_t st)
 {
-    const size_t vsz = vtype == VV_VOXEL_F32 ? 4 : 1;
+    const size_t vsz = voxel_bytes(vtype);
     const size_t bytes = (size_t)nx * ny * nz * vsz, pad = (size_t)nx * ny * vsz + 2 * (size_t)nx * vsz + 4096;
     HIPCHK(c, hipMalloc(&c->d_vol, bytes + pad));
     HIPCHK(c, hipMemsetAsync((char *)c->d_vol + bytes, 0, pad, st));
@@ -250,6 +252,70 @@ static int finish_call(vv_context *c, void *stream, hipStream_t st, const CallBu
     }
     if (host_out || !stream) HIPCHK(c, hipStreamSynchronize(st));
     return VV_OK;
+}
+
+// ---- what the calls that read the loaded volume's boxes and write a dense volume share -----------------------------------
+// Source addressing: the byte offset of voxel (x, y, z) in the linear volume, and the end of the last voxel of the box below `hi`.
+static size_t voxel_offset(const vv_context *c, int x, int y, int z)
+{
+    return (size_t)z * c->slice_pitch + (size_t)y * c->row_pitch + (size_t)x * voxel_bytes(c->vtype);
+}
+static size_t box_end(const vv_context *c, const int hi[3]) { return voxel_offset(c, hi[0], hi[1] - 1, hi[2] - 1); }
+
+static bool box_in_range(const int lo[3], const int hi[3], const int ext[3])
+{
+    for (int a = 0; a < 3; ++a)
+        if (!(0 <= lo[a] && lo[a] < hi[a] && hi[a] <= ext[a])) return false;
+    return true;
+}
+// The box of a descriptor, measured against `ext`: six zeros mean all of it.  (err_to: vv_derive_dims has a const context.)
+static int check_box(vv_context *err_to, const char *who, const int box_lo[3], const int box_hi[3], const int ext[3], int lo[3], int hi[3])
+{
+    bool whole = true;
+    for (int a = 0; a < 3; ++a) whole = whole && box_lo[a] == 0 && box_hi[a] == 0;
+    for (int a = 0; a < 3; ++a) { lo[a] = whole ? 0 : box_lo[a]; hi[a] = whole ? ext[a] : box_hi[a]; }
+    if (!box_in_range(lo, hi, ext)) return fail(err_to, VV_ERR_INVALID, std::string(who) + ": the box must satisfy 0 <= lo < hi <= dims on every axis (or be all zeros)");
+    return VV_OK;
+}
+static int check_out_type(vv_context *err_to, const char *who, int out_type)
+{
+    if (out_type != VV_VOXEL_U8 && out_type != VV_VOXEL_F32) return fail(err_to, VV_ERR_INVALID, std::string(who) + ": out_type must be VV_VOXEL_U8 or VV_VOXEL_F32");
+    return VV_OK;
+}
+// The caller's buffer for a dense volume of m[0] x m[1] x m[2] voxels of `out_type`: its bytes (*bytes), its capacity (`whence`: the message's
+// word on where the extents come from, or ""), a device f32 buffer's alignment and, for the calls that promise it, no overlap with the loaded volume.
+static int check_out_volume(vv_context *c, const char *who, const char *whence, const void *out, size_t capacity, int out_on_device, int out_type,
+                            const int m[3], bool refuse_overlap, size_t *bytes)
+{
+    const std::string w(who);
+    *bytes = (size_t)m[0] * (size_t)m[1] * (size_t)m[2] * voxel_bytes(out_type);
+    if (capacity < *bytes) return fail(c, VV_ERR_INVALID, w + ": capacity is below the output's bytes" + whence);
+    if (out_on_device && out_type == VV_VOXEL_F32 && ((uintptr_t)out & 3) != 0) return fail(c, VV_ERR_INVALID, w + ": a device f32 out must be 4-byte aligned");
+    if (refuse_overlap && out_on_device && (uintptr_t)out < (uintptr_t)c->d_vol + c->alloc_bytes && (uintptr_t)c->d_vol < (uintptr_t)out + *bytes)
+        return fail(c, VV_ERR_INVALID, w + ": out overlaps the loaded volume (the pass is not in place)");
+    return VV_OK;
+}
+
+// Runs a call that fills a volume of `bytes` at `out`, behind its checks.  A host volume goes through a device buffer of the call's own, not through
+// the scratch table: a volume-sized buffer must not stay resident in the context.  stage_call finds it as the buffer's fixed home (and uploads the
+// caller's bytes into it where the call works `in_place`); it is freed on every path.  `body(dev, st)` launches on the device volume and returns
+// VV_OK, or fails before it launches; the download and the wait are finish_call's.
+template <class Body>
+static int run_out_volume(vv_context *c, const char *who, void *out, size_t bytes, int out_on_device, bool in_place, void *stream, Body body)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    void *tmp = nullptr;
+    if (!out_on_device && hipMalloc(&tmp, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, VV_ERR_NOMEM, std::string(who) + ": no device memory for the staging buffer of a host out");
+    }
+    hipStream_t st;
+    CallBuf b = {out, bytes, !out_on_device, in_place, true, 0, tmp, nullptr};
+    int rc = stage_call(c, stream, &st, &b, 1);
+    if (rc == VV_OK) rc = body(b.dev, st);
+    if (rc == VV_OK) rc = finish_call(c, stream, st, &b, 1);
+    if (tmp) (void)hipFree(tmp);
+    return rc;
 }
 
 static int finalize_layout(vv_context *c, hipStream_t st);
@@ -410,7 +476,7 @@ static bool ensure_zfast(vv_context *c, hipStream_t st)
 {
     layout_copy &cp = c->copies[CP_ZFAST];
     if (cp.valid || cp.failed) return cp.valid;
-    const size_t vsz = c->vtype == VV_VOXEL_F32 ? 4 : 1;
+    const size_t vsz = voxel_bytes(c->vtype);
     size_t row = (size_t)c->nz * vsz;
     if (row % 1024 == 0) row += 32;
     else if (vsz == 1) row = (row + 3) & ~(size_t)3;                       // (u8 rows are read as aligned dwords)
@@ -666,7 +732,7 @@ int vv_load_volume_stream_slices_async(vv_context *c, const void *src, int src_t
     if (src_type != c->vtype && !(src_type == VV_VOXEL_U8 && c->vtype == VV_VOXEL_F32))
         return fail(c, VV_ERR_INVALID, "stream_slices: source type must match the volume (or be u8 for an f32 volume)");
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t ssz = src_type == VV_VOXEL_F32 ? 4 : 1, dsz = c->vtype == VV_VOXEL_F32 ? 4 : 1;
+    const size_t ssz = voxel_bytes(src_type), dsz = voxel_bytes(c->vtype);
     const size_t slice_vox = (size_t)c->nx * c->ny;
     const bool promote = src_type != c->vtype;
     hipPointerAttribute_t attr;
@@ -1728,31 +1794,29 @@ int vv_volume_histogram(vv_context *c, const int box_lo[3], const int box_hi[3],
     if (!c->d_vol) return fail(c, VV_ERR_NO_VOLUME, "vv_volume_histogram: no volume loaded");
     const int dims[3] = {c->nx, c->ny, c->nz};
     int lo[3] = {0, 0, 0}, hi[3] = {c->nx, c->ny, c->nz};
-    if (box_lo)
-        for (int a = 0; a < 3; ++a) {
-            lo[a] = box_lo[a]; hi[a] = box_hi[a];
-            if (!(0 <= lo[a] && lo[a] < hi[a] && hi[a] <= dims[a])) return fail(c, VV_ERR_INVALID, "vv_volume_histogram: the box must satisfy 0 <= lo < hi <= dims on every axis");
-        }
+    if (box_lo) {
+        for (int a = 0; a < 3; ++a) { lo[a] = box_lo[a]; hi[a] = box_hi[a]; }
+        if (!box_in_range(lo, hi, dims)) return fail(c, VV_ERR_INVALID, "vv_volume_histogram: the box must satisfy 0 <= lo < hi <= dims on every axis");
+    }
     hipStream_t st;
     CallBuf b = {out, sizeof(vv_histogram), !out_on_device, false, true, 0, (char *)c->d_hist + kHistResultOffset, nullptr};
     int rc = stage_call(c, stream, &st, &b, 1);
     if (rc) return rc;
     // the box as runs of the linear layout: its rows; whole slices of it where the rows are dense and taken whole; the whole box where the slices are too
-    const size_t size = c->vtype == VV_VOXEL_F32 ? 4 : 1;
+    const size_t size = voxel_bytes(c->vtype);
     const size_t bx = (size_t)(hi[0] - lo[0]), by = (size_t)(hi[1] - lo[1]), bz = (size_t)(hi[2] - lo[2]);
     const bool rows_dense = bx == (size_t)c->nx && c->row_pitch == (size_t)c->nx * size;
     const bool slices_dense = rows_dense && by == (size_t)c->ny && c->slice_pitch == (size_t)c->ny * c->row_pitch;
     HistRuns R;
     memset(&R, 0, sizeof R);
     R.vtype = c->vtype; R.tight = 0;
-    R.data0 = (const char *)c->d_vol + (size_t)lo[2] * c->slice_pitch + (size_t)lo[1] * c->row_pitch + (size_t)lo[0] * size;
+    R.data0 = (const char *)c->d_vol + voxel_offset(c, lo[0], lo[1], lo[2]);
     R.row_step = c->row_pitch; R.slice_step = c->slice_pitch;
     if (slices_dense)    { R.run_voxels = bx * by * bz; R.rps = 1; R.n_slices = 1; }
     else if (rows_dense) { R.run_voxels = bx * by; R.rps = 1; R.n_slices = (uint32_t)bz; }
     else                 { R.run_voxels = bx; R.rps = (uint32_t)by; R.n_slices = (uint32_t)bz; }
     // what launch_hist is promised: the last voxel of the box lies inside the volume, which ends more than 16 bytes before its allocation does
-    const size_t last = (size_t)(hi[2] - 1) * c->slice_pitch + (size_t)(hi[1] - 1) * c->row_pitch + (size_t)hi[0] * size;
-    if (((uintptr_t)c->d_vol & 15) != 0 || last + 16 > c->alloc_bytes) return fail(c, VV_ERR_DEVICE, "vv_volume_histogram: volume allocation is not what the kernel expects");
+    if (((uintptr_t)c->d_vol & 15) != 0 || box_end(c, hi) + 16 > c->alloc_bytes) return fail(c, VV_ERR_DEVICE, "vv_volume_histogram: volume allocation is not what the kernel expects");
     if ((rc = run_hist(c, &R, c->vtype, (unsigned long long)(bx * by * bz), (vv_histogram *)b.dev, nullptr, st)) != VV_OK) return rc;
     return finish_call(c, stream, st, &b, 1);
 }
@@ -1785,12 +1849,8 @@ static int derive_check(const vv_context *c, vv_context *err_to, const char *who
     const std::string w(who);
     if (!c->d_vol) return fail(err_to, VV_ERR_NO_VOLUME, w + ": no volume loaded");
     const int dims[3] = {c->nx, c->ny, c->nz};
-    bool whole = true;
-    for (int a = 0; a < 3; ++a) whole = whole && d->box_lo[a] == 0 && d->box_hi[a] == 0;
-    for (int a = 0; a < 3; ++a) {
-        lo[a] = whole ? 0 : d->box_lo[a]; hi[a] = whole ? dims[a] : d->box_hi[a];
-        if (!(0 <= lo[a] && lo[a] < hi[a] && hi[a] <= dims[a])) return fail(err_to, VV_ERR_INVALID, w + ": the box must satisfy 0 <= lo < hi <= dims on every axis (or be all zeros)");
-    }
+    int rc = check_box(err_to, who, d->box_lo, d->box_hi, dims, lo, hi);
+    if (rc) return rc;
     for (int a = 0; a < 3; ++a) {
         if (d->factor[a] < 0 || d->factor[a] > 8) return fail(err_to, VV_ERR_INVALID, w + ": factors must lie in 1..8 (0 is read as 1)");
         f[a] = d->factor[a] ? d->factor[a] : 1;
@@ -1798,7 +1858,7 @@ static int derive_check(const vv_context *c, vv_context *err_to, const char *who
     }
     if (d->mode != VV_REDUCE_MEAN && d->mode != VV_REDUCE_MAX && d->mode != VV_REDUCE_MIN)
         return fail(err_to, VV_ERR_INVALID, w + ": mode must be VV_REDUCE_MEAN, VV_REDUCE_MAX or VV_REDUCE_MIN");
-    if (d->out_type != VV_VOXEL_U8 && d->out_type != VV_VOXEL_F32) return fail(err_to, VV_ERR_INVALID, w + ": out_type must be VV_VOXEL_U8 or VV_VOXEL_F32");
+    if ((rc = check_out_type(err_to, who, d->out_type)) != VV_OK) return rc;
     if (d->window != 0 && d->window != 1) return fail(err_to, VV_ERR_INVALID, w + ": window must be 0 or 1");
     if (d->window) {
         const volatile float span = d->win_hi - d->win_lo;            // binary32, as the kernel takes it
@@ -1822,65 +1882,47 @@ int vv_derive_dims(const vv_context *c, const vv_derive *d, int out_dims[3])
 
 int vv_derive_volume(vv_context *c, const vv_derive *d, void *out, size_t capacity, int out_on_device, void *stream)
 {
+    static const char who[] = "vv_derive_volume";
     if (!c) return fail(nullptr, VV_ERR_INVALID, "vv_derive_volume: NULL context");
     if (!d || !out) return fail(c, VV_ERR_INVALID, "vv_derive_volume: NULL argument");
     int lo[3], hi[3], f[3], m[3];
-    int rc = derive_check(c, c, "vv_derive_volume", d, lo, hi, f, m);
+    size_t bytes;
+    int rc = derive_check(c, c, who, d, lo, hi, f, m);
+    if (!rc) rc = check_out_volume(c, who, " (vv_derive_dims)", out, capacity, out_on_device, d->out_type, m, false, &bytes);
     if (rc) return rc;
-    const size_t osize = d->out_type == VV_VOXEL_F32 ? 4 : 1, bytes = (size_t)m[0] * m[1] * m[2] * osize;
-    if (capacity < bytes) return fail(c, VV_ERR_INVALID, "vv_derive_volume: capacity is below the output's bytes (vv_derive_dims)");
-    if (out_on_device && d->out_type == VV_VOXEL_F32 && ((uintptr_t)out & 3) != 0) return fail(c, VV_ERR_INVALID, "vv_derive_volume: a device f32 out must be 4-byte aligned");
-    HIPCHK(c, hipSetDevice(c->device));
-    // A host volume goes through a device buffer of this call's own, as the generator's: a volume-sized buffer must not stay resident in the context.
-    // stage_call finds it as the buffer's fixed home; it is freed on every path below.
-    void *tmp = nullptr;
-    if (!out_on_device && hipMalloc(&tmp, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(c, VV_ERR_NOMEM, "vv_derive_volume: no device memory for the staging buffer of a host out");
-    }
-    hipStream_t st;
-    CallBuf b = {out, bytes, !out_on_device, false, true, 0, tmp, nullptr};
-    if ((rc = stage_call(c, stream, &st, &b, 1)) == VV_OK) {
-        const size_t size = c->vtype == VV_VOXEL_F32 ? 4 : 1;
-        DeriveArgs A;
-        memset(&A, 0, sizeof A);
-        A.src0 = (const char *)c->d_vol + (size_t)lo[2] * c->slice_pitch + (size_t)lo[1] * c->row_pitch + (size_t)lo[0] * size;
-        A.out = b.dev;
-        A.row_pitch = c->row_pitch; A.slice_pitch = c->slice_pitch;
-        for (int a = 0; a < 3; ++a) { A.b[a] = (uint32_t)(hi[a] - lo[a]); A.f[a] = (uint32_t)f[a]; A.m[a] = (uint32_t)m[a]; }
-        A.src_type = c->vtype; A.out_type = d->out_type; A.mode = d->mode; A.window = d->window;
-        A.win_lo = d->win_lo; A.win_hi = d->win_hi;
-        // what launch_derive is promised: the allocation starts 16-byte aligned and holds the box's last voxel; what lies behind that voxel is its to read
-        const size_t last = (size_t)(hi[2] - 1) * c->slice_pitch + (size_t)(hi[1] - 1) * c->row_pitch + (size_t)hi[0] * size;
-        if (((uintptr_t)c->d_vol & 15) != 0 || last > c->alloc_bytes) rc = fail(c, VV_ERR_DEVICE, "vv_derive_volume: volume allocation is not what the kernel expects");
-        else {
-            A.slack = c->alloc_bytes - last;
-            launch_derive(A, c->n_cu, c->knobs.derive_blocks, st);
-            rc = finish_call(c, stream, st, &b, 1);
-        }
-    }
-    if (tmp) (void)hipFree(tmp);
-    return rc;
+    DeriveArgs A;
+    memset(&A, 0, sizeof A);
+    A.src0 = (const char *)c->d_vol + voxel_offset(c, lo[0], lo[1], lo[2]);
+    A.row_pitch = c->row_pitch; A.slice_pitch = c->slice_pitch;
+    for (int a = 0; a < 3; ++a) { A.b[a] = (uint32_t)(hi[a] - lo[a]); A.f[a] = (uint32_t)f[a]; A.m[a] = (uint32_t)m[a]; }
+    A.src_type = c->vtype; A.out_type = d->out_type; A.mode = d->mode; A.window = d->window;
+    A.win_lo = d->win_lo; A.win_hi = d->win_hi;
+    // what launch_derive is promised: the allocation starts 16-byte aligned and holds the box's last voxel; what lies behind that voxel is its to read
+    const size_t last = box_end(c, hi);
+    if (((uintptr_t)c->d_vol & 15) != 0 || last > c->alloc_bytes) return fail(c, VV_ERR_DEVICE, "vv_derive_volume: volume allocation is not what the kernel expects");
+    A.slack = c->alloc_bytes - last;
+    return run_out_volume(c, who, out, bytes, out_on_device, false, stream, [&](void *dev, hipStream_t st) {
+        A.out = dev;
+        launch_derive(A, c->n_cu, c->knobs.derive_blocks, st);
+        return VV_OK;
+    });
 }
 
 // ---- neighbourhood filters (include/volviz.h: vv_stencil_volume) ---------------------------
 int vv_stencil_volume(vv_context *c, const vv_stencil *d, void *out, size_t capacity, int out_on_device, void *stream)
 {
+    static const char who[] = "vv_stencil_volume";
     if (!c) return fail(nullptr, VV_ERR_INVALID, "vv_stencil_volume: NULL context");
     if (!d || !out) return fail(c, VV_ERR_INVALID, "vv_stencil_volume: NULL argument");
     if (!c->d_vol) return fail(c, VV_ERR_NO_VOLUME, "vv_stencil_volume: no volume loaded");
     // the header's rule 9, in its order
     const int dims[3] = {c->nx, c->ny, c->nz};
     int lo[3], hi[3];
-    bool whole = true;
-    for (int a = 0; a < 3; ++a) whole = whole && d->box_lo[a] == 0 && d->box_hi[a] == 0;
-    for (int a = 0; a < 3; ++a) {
-        lo[a] = whole ? 0 : d->box_lo[a]; hi[a] = whole ? dims[a] : d->box_hi[a];
-        if (!(0 <= lo[a] && lo[a] < hi[a] && hi[a] <= dims[a])) return fail(c, VV_ERR_INVALID, "vv_stencil_volume: the box must satisfy 0 <= lo < hi <= dims on every axis (or be all zeros)");
-    }
+    int rc = check_box(c, who, d->box_lo, d->box_hi, dims, lo, hi);
+    if (rc) return rc;
     if (d->kind != VV_STENCIL_SEPARABLE && d->kind != VV_STENCIL_MEDIAN && d->kind != VV_STENCIL_GRADMAG)
         return fail(c, VV_ERR_INVALID, "vv_stencil_volume: kind must be VV_STENCIL_SEPARABLE, VV_STENCIL_MEDIAN or VV_STENCIL_GRADMAG");
-    if (d->out_type != VV_VOXEL_U8 && d->out_type != VV_VOXEL_F32) return fail(c, VV_ERR_INVALID, "vv_stencil_volume: out_type must be VV_VOXEL_U8 or VV_VOXEL_F32");
+    if ((rc = check_out_type(c, who, d->out_type)) != VV_OK) return rc;
     StencilArgs A;
     memset(&A, 0, sizeof A);
     if (d->kind == VV_STENCIL_SEPARABLE)
@@ -1899,107 +1941,70 @@ int vv_stencil_volume(vv_context *c, const vv_stencil *d, void *out, size_t capa
             A.gscale[a] = unset ? 1.f : d->gscale[a];
         }
     }
-    const size_t osize = d->out_type == VV_VOXEL_F32 ? 4 : 1, bytes = (size_t)(hi[0] - lo[0]) * (size_t)(hi[1] - lo[1]) * (size_t)(hi[2] - lo[2]) * osize;
-    if (capacity < bytes) return fail(c, VV_ERR_INVALID, "vv_stencil_volume: capacity is below the output's bytes");
-    if (out_on_device && d->out_type == VV_VOXEL_F32 && ((uintptr_t)out & 3) != 0) return fail(c, VV_ERR_INVALID, "vv_stencil_volume: a device f32 out must be 4-byte aligned");
-    if (out_on_device && (uintptr_t)out < (uintptr_t)c->d_vol + c->alloc_bytes && (uintptr_t)c->d_vol < (uintptr_t)out + bytes)
-        return fail(c, VV_ERR_INVALID, "vv_stencil_volume: out overlaps the loaded volume (the pass is not in place)");
-    HIPCHK(c, hipSetDevice(c->device));
-    // a host volume goes through a device buffer of this call's own, as vv_derive_volume's; a device out allocates nothing
-    void *tmp = nullptr;
-    if (!out_on_device && hipMalloc(&tmp, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(c, VV_ERR_NOMEM, "vv_stencil_volume: no device memory for the staging buffer of a host out");
-    }
-    hipStream_t st;
-    CallBuf b = {out, bytes, !out_on_device, false, true, 0, tmp, nullptr};
-    int rc = stage_call(c, stream, &st, &b, 1);
-    if (rc == VV_OK) {
-        const size_t size = c->vtype == VV_VOXEL_F32 ? 4 : 1;
-        A.vol = c->d_vol; A.out = b.dev;
-        A.row_pitch = c->row_pitch; A.slice_pitch = c->slice_pitch;
-        for (int a = 0; a < 3; ++a) { A.n[a] = dims[a]; A.lo[a] = lo[a]; A.b[a] = (uint32_t)(hi[a] - lo[a]); }
-        A.src_type = c->vtype; A.out_type = d->out_type; A.kind = d->kind;
-        // what launch_stencil is promised: the volume's last voxel lies inside the allocation
-        const size_t last = (size_t)(c->nz - 1) * c->slice_pitch + (size_t)(c->ny - 1) * c->row_pitch + (size_t)c->nx * size;
-        if (last > c->alloc_bytes || (size == 4 && (((uintptr_t)c->d_vol | c->row_pitch | c->slice_pitch) & 3) != 0))
-            rc = fail(c, VV_ERR_DEVICE, "vv_stencil_volume: volume allocation is not what the kernel expects");
-        else {
-            launch_stencil(A, c->n_cu, c->knobs.stencil_blocks, st);
-            rc = finish_call(c, stream, st, &b, 1);
-        }
-    }
-    if (tmp) (void)hipFree(tmp);
-    return rc;
+    const int b[3] = {hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]};
+    size_t bytes;
+    if ((rc = check_out_volume(c, who, "", out, capacity, out_on_device, d->out_type, b, true, &bytes)) != VV_OK) return rc;
+    A.vol = c->d_vol;
+    A.row_pitch = c->row_pitch; A.slice_pitch = c->slice_pitch;
+    for (int a = 0; a < 3; ++a) { A.n[a] = dims[a]; A.lo[a] = lo[a]; A.b[a] = (uint32_t)b[a]; }
+    A.src_type = c->vtype; A.out_type = d->out_type; A.kind = d->kind;
+    // what launch_stencil is promised: the volume's last voxel lies inside the allocation
+    if (box_end(c, dims) > c->alloc_bytes || (c->vtype == VV_VOXEL_F32 && (((uintptr_t)c->d_vol | c->row_pitch | c->slice_pitch) & 3) != 0))
+        return fail(c, VV_ERR_DEVICE, "vv_stencil_volume: volume allocation is not what the kernel expects");
+    return run_out_volume(c, who, out, bytes, out_on_device, false, stream, [&](void *dev, hipStream_t st) {
+        A.out = dev;
+        launch_stencil(A, c->n_cu, c->knobs.stencil_blocks, st);
+        return VV_OK;
+    });
 }
 
 // ---- resampled volumes (include/volviz.h: vv_resample_volume) -------------------------------
 // The header's rule 9 behind the NULL checks, in its order; fills the box (lo, hi) and the output's bytes.
-static int resample_check(vv_context *c, const vv_resample *r, const void *out, size_t capacity, int out_on_device, int lo[3], int hi[3], size_t *bytes)
+static int resample_check(vv_context *c, const char *who, const vv_resample *r, const void *out, size_t capacity, int out_on_device, int lo[3], int hi[3], size_t *bytes)
 {
     if (!c->d_vol) return fail(c, VV_ERR_NO_VOLUME, "vv_resample_volume: no volume loaded");
     for (int a = 0; a < 3; ++a)
         if (r->dims[a] < 1 || r->dims[a] > VV_RESAMPLE_MAX_DIM) return fail(c, VV_ERR_INVALID, "vv_resample_volume: dims must lie in 1..16384");
-    bool whole = true;
-    for (int a = 0; a < 3; ++a) whole = whole && r->box_lo[a] == 0 && r->box_hi[a] == 0;
-    for (int a = 0; a < 3; ++a) {
-        lo[a] = whole ? 0 : r->box_lo[a]; hi[a] = whole ? r->dims[a] : r->box_hi[a];
-        if (!(0 <= lo[a] && lo[a] < hi[a] && hi[a] <= r->dims[a])) return fail(c, VV_ERR_INVALID, "vv_resample_volume: the box must satisfy 0 <= lo < hi <= dims on every axis (or be all zeros)");
-    }
+    int rc = check_box(c, who, r->box_lo, r->box_hi, r->dims, lo, hi);
+    if (rc) return rc;
     if (r->filter != VV_RESAMPLE_TEX8 && r->filter != VV_RESAMPLE_EXACT && r->filter != VV_RESAMPLE_NEAREST)
         return fail(c, VV_ERR_INVALID, "vv_resample_volume: filter must be VV_RESAMPLE_TEX8, VV_RESAMPLE_EXACT or VV_RESAMPLE_NEAREST");
-    if (r->out_type != VV_VOXEL_U8 && r->out_type != VV_VOXEL_F32) return fail(c, VV_ERR_INVALID, "vv_resample_volume: out_type must be VV_VOXEL_U8 or VV_VOXEL_F32");
+    if ((rc = check_out_type(c, who, r->out_type)) != VV_OK) return rc;
     for (int k = 0; k < 12; ++k)
         if (!std::isfinite(r->m[k])) return fail(c, VV_ERR_INVALID, "vv_resample_volume: the matrix must be finite");
     if (!std::isfinite(r->fill)) return fail(c, VV_ERR_INVALID, "vv_resample_volume: fill must be finite");
-    *bytes = (size_t)(hi[0] - lo[0]) * (size_t)(hi[1] - lo[1]) * (size_t)(hi[2] - lo[2]) * (r->out_type == VV_VOXEL_F32 ? 4 : 1);
-    if (capacity < *bytes) return fail(c, VV_ERR_INVALID, "vv_resample_volume: capacity is below the output's bytes");
-    if (out_on_device && r->out_type == VV_VOXEL_F32 && ((uintptr_t)out & 3) != 0) return fail(c, VV_ERR_INVALID, "vv_resample_volume: a device f32 out must be 4-byte aligned");
-    if (out_on_device && (uintptr_t)out < (uintptr_t)c->d_vol + c->alloc_bytes && (uintptr_t)c->d_vol < (uintptr_t)out + *bytes)
-        return fail(c, VV_ERR_INVALID, "vv_resample_volume: out overlaps the loaded volume (the pass is not in place)");
-    return VV_OK;
+    const int b[3] = {hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]};
+    return check_out_volume(c, who, "", out, capacity, out_on_device, r->out_type, b, true, bytes);
 }
 
 int vv_resample_volume(vv_context *c, const vv_resample *r, void *out, size_t capacity, int out_on_device, void *stream)
 {
+    static const char who[] = "vv_resample_volume";
     if (!c) return fail(nullptr, VV_ERR_INVALID, "vv_resample_volume: NULL context");
     if (!r || !out) return fail(c, VV_ERR_INVALID, "vv_resample_volume: NULL argument");
     int lo[3], hi[3];
     size_t bytes = 0;
-    int rc = resample_check(c, r, out, capacity, out_on_device, lo, hi, &bytes);
+    const int rc = resample_check(c, who, r, out, capacity, out_on_device, lo, hi, &bytes);
     if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    // a host volume goes through a device buffer of this call's own, as vv_stencil_volume's; a device out allocates nothing
-    void *tmp = nullptr;
-    if (!out_on_device && hipMalloc(&tmp, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(c, VV_ERR_NOMEM, "vv_resample_volume: no device memory for the staging buffer of a host out");
+    ResampleArgs A;
+    memset(&A, 0, sizeof A);
+    A.V = view_of(c, MB_LINEAR);
+    A.src_type = c->vtype; A.out_type = r->out_type; A.filter = r->filter;
+    for (int a = 0; a < 3; ++a) {
+        A.lo[a] = lo[a]; A.b[a] = (uint32_t)(hi[a] - lo[a]);
+        const volatile float inv = 1.0f / (float)r->dims[a];        // one IEEE binary32 division
+        A.inv[a] = inv;
     }
-    hipStream_t st;
-    CallBuf b = {out, bytes, !out_on_device, false, true, 0, tmp, nullptr};
-    if ((rc = stage_call(c, stream, &st, &b, 1)) == VV_OK) {
-        ResampleArgs A;
-        memset(&A, 0, sizeof A);
-        A.V = view_of(c, MB_LINEAR); A.out = b.dev;
-        A.src_type = c->vtype; A.out_type = r->out_type; A.filter = r->filter;
-        for (int a = 0; a < 3; ++a) {
-            A.lo[a] = lo[a]; A.b[a] = (uint32_t)(hi[a] - lo[a]);
-            const volatile float inv = 1.0f / (float)r->dims[a];        // one IEEE binary32 division
-            A.inv[a] = inv;
-        }
-        memcpy(A.m, r->m, sizeof A.m); A.fill = r->fill;
-        // what launch_resample is promised: the weight-0 corners of the last voxel's sample (one slice and one row on, two dwords) lie inside the allocation
-        const size_t size = c->vtype == VV_VOXEL_F32 ? 4 : 1;
-        const size_t reach = ((size_t)c->nz + 1) * c->slice_pitch + (size_t)c->nx * size + 8;
-        if (reach > c->alloc_bytes || (size == 4 && (((uintptr_t)c->d_vol | c->row_pitch | c->slice_pitch) & 3) != 0))
-            rc = fail(c, VV_ERR_DEVICE, "vv_resample_volume: volume allocation is not what the kernel expects");
-        else {
-            launch_resample(A, c->n_cu, c->knobs.resample_blocks, st);
-            rc = finish_call(c, stream, st, &b, 1);
-        }
-    }
-    if (tmp) (void)hipFree(tmp);
-    return rc;
+    memcpy(A.m, r->m, sizeof A.m); A.fill = r->fill;
+    // what launch_resample is promised: the weight-0 corners of the last voxel's sample (one slice and one row on, two dwords) lie inside the allocation
+    const size_t reach = voxel_offset(c, c->nx, 0, c->nz + 1) + 8;
+    if (reach > c->alloc_bytes || (c->vtype == VV_VOXEL_F32 && (((uintptr_t)c->d_vol | c->row_pitch | c->slice_pitch) & 3) != 0))
+        return fail(c, VV_ERR_DEVICE, "vv_resample_volume: volume allocation is not what the kernel expects");
+    return run_out_volume(c, who, out, bytes, out_on_device, false, stream, [&](void *dev, hipStream_t st) {
+        A.out = dev;
+        launch_resample(A, c->n_cu, c->knobs.resample_blocks, st);
+        return VV_OK;
+    });
 }
 
 // ---- generator: VolumeGenerator::drawEllipsoid / drawDefaultBrain ------------------------
@@ -2011,24 +2016,13 @@ static int generate_impl(vv_context *c, uint8_t *out, int out_on_device, int nx,
         return fail(c, VV_ERR_INVALID, "vv_generate_ellipsoids: bad argument (n <= 64)");
     if ((((unsigned long long)nx + 15ull) / 16ull) * (unsigned long long)ny >= (1ull << 31))
         return fail(c, VV_ERR_INVALID, "vv_generate_ellipsoids: a slice must have fewer than 2^31 16-voxel chunks");
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = pick_stream(c, stream);
-    // A host volume goes through a device buffer of this call's own, not through the scratch table: a volume-sized buffer must not stay resident in the
-    // context.  Freed on every path below; the download and the wait are finish_call's.
-    CallBuf b = {out, (size_t)nx * ny * nz, !out_on_device, in_place != 0, true, 0, nullptr, out};
-    void *tmp = nullptr;
-    if (b.host) {
-        HIPCHK(c, hipMalloc(&tmp, b.bytes)); b.dev = tmp;
-        if (b.in && hipMemcpyAsync(b.dev, out, b.bytes, hipMemcpyHostToDevice, st) != hipSuccess) { hipFree(tmp); return fail(c, VV_ERR_DEVICE, "vv_draw_ellipsoid: upload failed"); }
-    }
-    int rc = ((uintptr_t)b.dev & 15) != 0 ? fail(c, VV_ERR_INVALID, "vv_generate_ellipsoids: device buffer must be 16-byte aligned") : VV_OK;
-    if (!rc) rc = ensure(c, SC_GEN, generate_scratch_floats(nx, ny, nz, n) * sizeof(float));
-    if (!rc) {
-        launch_generate_ellipsoids((uint8_t *)b.dev, nx, ny, nz, n, centers, axes, colors, in_place, (float *)c->scratch[SC_GEN].p, st);
-        rc = finish_call(c, stream, st, &b, 1);
-    }
-    if (tmp) hipFree(tmp);
-    return rc;
+    if (out_on_device && ((uintptr_t)out & 15) != 0) return fail(c, VV_ERR_INVALID, "vv_generate_ellipsoids: device buffer must be 16-byte aligned");     // (a staging buffer is)
+    return run_out_volume(c, "vv_generate_ellipsoids", out, (size_t)nx * ny * nz, out_on_device, in_place != 0, stream, [&](void *dev, hipStream_t st) {
+        const int rc = ensure(c, SC_GEN, generate_scratch_floats(nx, ny, nz, n) * sizeof(float));
+        if (rc) return rc;
+        launch_generate_ellipsoids((uint8_t *)dev, nx, ny, nz, n, centers, axes, colors, in_place, (float *)c->scratch[SC_GEN].p, st);
+        return (int)VV_OK;
+    });
 }
 
 int vv_generate_ellipsoids(vv_context *c, uint8_t *out, int out_on_device, int nx, int ny, int nz, int n,

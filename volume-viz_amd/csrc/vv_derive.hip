@@ -88,8 +88,7 @@ __device__ __forceinline__ uint32_t derive_finish(const DeriveCell<F32> &c, uint
         const float w = (u - win_lo) / (win_hi - win_lo);
         return OF32 ? __float_as_uint(w) : index_of<VV_VOXEL_F32>(w);
     }
-    if constexpr (F32) return OF32 ? rbits : index_of<VV_VOXEL_F32>(u);
-    else               return OF32 ? __float_as_uint(byte_over_255(u)) : rbits;
+    return voxel_out_copy<F32, OF32>(rbits);
 }
 
 template <int SRC, int OUT, int FX>
@@ -168,7 +167,7 @@ __global__ __launch_bounds__(64 * kDeriveWaves) void derive_kernel(DeriveKernelA
             } else {
 #pragma unroll
                 for (int o = 0; o < OPL; ++o)
-                    if ((uint32_t)o < n_out) { if (OF32) ((uint32_t *)dst)[o] = r[o]; else ((uint8_t *)dst)[o] = (uint8_t)r[o]; }
+                    if ((uint32_t)o < n_out) voxel_store<OF32>(dst + o * OSIZE, r[o]);
             }
         }
         k += A.dk;

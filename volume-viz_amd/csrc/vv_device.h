@@ -586,6 +586,26 @@ __device__ __forceinline__ float byte_over_255(float b)
     const float r = __builtin_fmaf(-q0, 255.0f, b);
     return __builtin_fmaf(r, c, q0);
 }
+// The output stage of the volume-to-volume kernels (vv_derive.hip, vv_stencil.hip, vv_resample.hip; F32: the source's voxels, OF32: the output's).
+// Of an arithmetic result r in the source's storage units: the voxel's byte or binary32 pattern.
+template <bool F32, bool OF32> __device__ __forceinline__ uint32_t voxel_out(float r)
+{
+#pragma clang fp contract(off)
+    if constexpr (F32) return OF32 ? __float_as_uint(r) : index_of<VV_VOXEL_F32>(r);
+    else if constexpr (OF32) return __float_as_uint(r / 255.0f);
+    else return !(r >= 0.5f) ? 0u : r >= 254.5f ? 255u : (uint32_t)(int)(r + 0.5f);
+}
+// ... of a voxel that is copied, not computed: raw = the f32 pattern or the byte
+template <bool F32, bool OF32> __device__ __forceinline__ uint32_t voxel_out_copy(uint32_t raw)
+{
+    if constexpr (F32) return OF32 ? raw : index_of<VV_VOXEL_F32>(__uint_as_float(raw));
+    else return OF32 ? __float_as_uint(byte_over_255((float)raw)) : raw;
+}
+// ... and its store
+template <bool OF32> __device__ __forceinline__ void voxel_store(char *at, uint32_t v)
+{
+    if constexpr (OF32) *(uint32_t *)at = v; else *(uint8_t *)at = (uint8_t)v;
+}
 // ... without the bounds test (the caller applies it)
 template <int VOXEL, class CT>
 __device__ __forceinline__ uint32_t classify_raw(const CT &C)

@@ -54,20 +54,6 @@ struct ResampleKernelArgs {
     uint64_t tiles, chunk, items;   // tiles of the box; tiles per XCD; items = kRsXcds * chunk
 };
 
-// the output stage of r (rule 4): the voxel's byte or binary32 pattern
-template <bool F32, bool OF32> __device__ __forceinline__ uint32_t resample_finish(float r)
-{
-#pragma clang fp contract(off)
-    if constexpr (F32) return OF32 ? __float_as_uint(r) : index_of<VV_VOXEL_F32>(r);
-    else if constexpr (OF32) return __float_as_uint(r / 255.0f);
-    else return !(r >= 0.5f) ? 0u : r >= 254.5f ? 255u : (uint32_t)(int)(r + 0.5f);
-}
-// ... of a voxel copied by NEAREST: raw = the f32 pattern or the byte
-template <bool F32, bool OF32> __device__ __forceinline__ uint32_t resample_copy(uint32_t raw)
-{
-    if constexpr (F32) return OF32 ? raw : index_of<VV_VOXEL_F32>(__uint_as_float(raw));
-    else return OF32 ? __float_as_uint(byte_over_255((float)raw)) : raw;
-}
 __device__ __forceinline__ bool resample_inside(float x, float y, float z)      // slice_kernel's test (vv_aux.hip): false for a NaN, true for -0
 {
     return x < 1.0f && x >= 0.0f && y < 1.0f && y >= 0.0f && z < 1.0f && z >= 0.0f;
@@ -90,7 +76,7 @@ __global__ __launch_bounds__(kRsThreads) void resample_kernel(ResampleKernelArgs
     const VolumeView &V = R.V;
     const uint32_t lane = threadIdx.x & 63u, wz = threadIdx.x >> 6;
     const uint32_t lx = lane % LANES_X, ly = lane / LANES_X;
-    const uint32_t fill_out = resample_finish<F32, OF32>(R.fill);
+    const uint32_t fill_out = voxel_out<F32, OF32>(R.fill);
 
     for (uint64_t i = blockIdx.x; i < A.items; i += gridDim.x) {
 #if VV_RESAMPLE_XCD
@@ -141,8 +127,8 @@ __global__ __launch_bounds__(kRsThreads) void resample_kernel(ResampleKernelArgs
         for (int k = 0; k < VPL; ++k) {
             v[k] = fill_out;
             if (in[k]) {
-                if constexpr (NEAREST) v[k] = resample_copy<F32, OF32>(raw[k]);
-                else v[k] = resample_finish<F32, OF32>(finish_corners<SRC>(Cn[k]));
+                if constexpr (NEAREST) v[k] = voxel_out_copy<F32, OF32>(raw[k]);
+                else v[k] = voxel_out<F32, OF32>(finish_corners<SRC>(Cn[k]));
             }
         }
         char *at = (char *)R.out + (((uint64_t)oz * R.b[1] + oy) * R.b[0] + ox) * OSIZE;

@@ -63,20 +63,6 @@ __device__ __forceinline__ float stencil_pass(const float *centre, int stride, i
     return acc;
 }
 
-// the output stage of an arithmetic result r (SEPARABLE, GRADMAG): the voxel's byte or binary32 pattern
-template <bool F32, bool OF32> __device__ __forceinline__ uint32_t stencil_finish(float r)
-{
-#pragma clang fp contract(off)
-    if constexpr (F32) return OF32 ? __float_as_uint(r) : index_of<VV_VOXEL_F32>(r);
-    else if constexpr (OF32) return __float_as_uint(r / 255.0f);
-    else return !(r >= 0.5f) ? 0u : r >= 254.5f ? 255u : (uint32_t)(int)(r + 0.5f);
-}
-
-template <bool OF32> __device__ __forceinline__ void stencil_store(char *at, uint32_t v)
-{
-    if constexpr (OF32) *(uint32_t *)at = v; else *(uint8_t *)at = (uint8_t)v;
-}
-
 // what the kernels share: the item's tile and z range
 struct StencilItem { int x0, y0, zb, ze; uint32_t ox, oy; bool owns; uint64_t first, plane; };   // first / plane: the column's first output voxel, voxels per output plane
 template <int TILE_Y> __device__ __forceinline__ StencilItem stencil_item(const StencilKernelArgs &A, uint64_t item, uint32_t lx, uint32_t ly)
@@ -189,7 +175,7 @@ __global__ __launch_bounds__(kStThreads) void stencil_sep_kernel(StencilKernelAr
             if (j - Rz >= I.zb) {                                         // output plane j - R_z
 #pragma unroll
                 for (int q = 0; q < kSepRows; ++q)
-                    if (owns[q]) stencil_store<OF32>(op + q * qstep, stencil_finish<F32, OF32>(r[q]));
+                    if (owns[q]) voxel_store<OF32>(op + q * qstep, voxel_out<F32, OF32>(r[q]));
                 op += I.plane * OSIZE;
             }
         }
@@ -272,16 +258,15 @@ __global__ __launch_bounds__(kStThreads) void stencil_nb_kernel(StencilKernelArg
                         w[dy * 3 + dx] = pa[q]; w[9 + dy * 3 + dx] = pb[q]; w[18 + dy * 3 + dx] = pc[q];
                     }
                 const uint32_t m = stencil_select<15>(w, w + 15);
-                if constexpr (F32) { const uint32_t bits = hist_key_inverse(m); v = OF32 ? bits : index_of<VV_VOXEL_F32>(__uint_as_float(bits)); }
-                else v = OF32 ? __float_as_uint(byte_over_255((float)m)) : m;
+                v = voxel_out_copy<F32, OF32>(F32 ? hist_key_inverse(m) : m);
             } else {
                 const float gx = stencil_value<F32>(pb[ci + 1]) - stencil_value<F32>(pb[ci - 1]);
                 const float gy = stencil_value<F32>(pb[ci + kNbSW]) - stencil_value<F32>(pb[ci - kNbSW]);
                 const float gz = stencil_value<F32>(pc[ci]) - stencil_value<F32>(pa[ci]);
                 const float Gx = gx * D.gscale[0], Gy = gy * D.gscale[1], Gz = gz * D.gscale[2];
-                v = stencil_finish<F32, OF32>(sqrtf((Gx * Gx + Gy * Gy) + Gz * Gz));
+                v = voxel_out<F32, OF32>(sqrtf((Gx * Gx + Gy * Gy) + Gz * Gz));
             }
-            if (I.owns) stencil_store<OF32>(op, v);
+            if (I.owns) voxel_store<OF32>(op, v);
             op += I.plane * OSIZE;
         }
         __syncthreads();                                                 // the next item starts over at plane 0 of S

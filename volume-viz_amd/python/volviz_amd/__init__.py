@@ -722,23 +722,49 @@ class Context:
         self._chk(self.lib.vv_volume_dims(self.h, C.byref(dims), C.byref(vt)))
         return int(vt.value)
 
-    def _derive(self, box, factor, mode, out_type, window) -> vv_derive:
-        """box = ((x0, y0, z0), (x1, y1, z1)) or None = the whole volume; factor: an int or (fx, fy, fz); out_type None = the volume's type;
-        window = (win_lo, win_hi) or None."""
-        d = vv_derive()
+    # what the volume-to-volume calls share: the descriptor's box and output type, the output's extents, the host and the device call
+    def _box_and_type(self, d, box, out_type):
+        """box = ((x0, y0, z0), (x1, y1, z1)) or None = all of it (six zeros); out_type None = the volume's type."""
         if box is not None:
             d.box_lo[:] = [int(v) for v in box[0]]
             d.box_hi[:] = [int(v) for v in box[1]]
+        d.out_type = self.volume_type() if out_type is None else int(out_type)
+        return d
+
+    def _out_dims(self, d, whole=None):
+        """(bx, by, bz) of the descriptor's box; `whole`: what six zeros stand for (None: the loaded volume's extents)."""
+        if any(d.box_lo) or any(d.box_hi):
+            return tuple(max(int(h) - int(l), 0) for l, h in zip(d.box_lo, d.box_hi))
+        if whole is None:
+            whole = (C.c_int * 3)()
+            self._chk(self.lib.vv_volume_dims(self.h, C.byref(whole), None))
+        return int(whole[0]), int(whole[1]), int(whole[2])
+
+    def _volume_to_host(self, call, d, dims, prefill) -> np.ndarray:
+        """`call` (a vv_*_volume) into a new host array [bz, by, bx] of the descriptor's out_type, prefilled with the byte `prefill` unless None."""
+        out = np.empty(tuple(dims)[::-1], np.float32 if d.out_type == VOXEL_F32 else np.uint8)
+        if prefill is not None:
+            out.view(np.uint8)[...] = prefill
+        self._chk(call(self.h, C.byref(d), out.ctypes.data if out.size else None, out.nbytes, 0, None))
+        return out
+
+    def _volume_to_device(self, call, d, out_ptr, capacity, stream):
+        self._chk(call(self.h, C.byref(d), out_ptr or None, int(capacity), 1, stream or None))
+
+    def _derive(self, box, factor, mode, out_type, window) -> vv_derive:
+        """box and out_type as _box_and_type; factor: an int or (fx, fy, fz); window = (win_lo, win_hi) or None."""
+        d = self._box_and_type(vv_derive(), box, out_type)
         d.factor[:] = [int(factor)] * 3 if np.isscalar(factor) else [int(v) for v in factor]
         d.mode = int(mode)
-        d.out_type = self.volume_type() if out_type is None else int(out_type)
         if window is not None:
             d.window, d.win_lo, d.win_hi = 1, float(window[0]), float(window[1])
         return d
 
     def derive_dims(self, box=None, factor=1):
         """vv_derive_dims: (mx, my, mz) of the volume derive() makes of this box and factor."""
-        d = self._derive(box, factor, REDUCE_MEAN, VOXEL_U8, None)
+        return self._derive_dims(self._derive(box, factor, REDUCE_MEAN, VOXEL_U8, None))
+
+    def _derive_dims(self, d: vv_derive):
         m = (C.c_int * 3)()
         self._chk(self.lib.vv_derive_dims(self.h, C.byref(d), C.byref(m)))
         return int(m[0]), int(m[1]), int(m[2])
@@ -747,32 +773,21 @@ class Context:
         """vv_derive_volume into a host array [mz, my, mx] of uint8 or float32.  `prefill`: the byte the buffer holds before the call (the
         result does not depend on it)."""
         d = self._derive(box, factor, mode, out_type, window)
-        m = (C.c_int * 3)()
-        self._chk(self.lib.vv_derive_dims(self.h, C.byref(d), C.byref(m)))
-        out = np.empty((m[2], m[1], m[0]), np.float32 if d.out_type == VOXEL_F32 else np.uint8)
-        if prefill is not None:
-            out.view(np.uint8)[...] = prefill
-        self._chk(self.lib.vv_derive_volume(self.h, C.byref(d), out.ctypes.data, out.nbytes, 0, None))
-        return out
+        return self._volume_to_host(self.lib.vv_derive_volume, d, self._derive_dims(d), prefill)
 
     def derive_device(self, out_ptr: int, capacity: int, box=None, factor=1, mode=REDUCE_MEAN, out_type=None, window=None, stream: int = 0):
         """vv_derive_volume into a device buffer of `capacity` bytes, enqueued on `stream`; returns (mx, my, mz)."""
         d = self._derive(box, factor, mode, out_type, window)
-        m = (C.c_int * 3)()
-        self._chk(self.lib.vv_derive_dims(self.h, C.byref(d), C.byref(m)))
-        self._chk(self.lib.vv_derive_volume(self.h, C.byref(d), out_ptr or None, int(capacity), 1, stream or None))
-        return int(m[0]), int(m[1]), int(m[2])
+        m = self._derive_dims(d)
+        self._volume_to_device(self.lib.vv_derive_volume, d, out_ptr, capacity, stream)
+        return m
 
     # vv_stencil_volume (no reference counterpart)
     def _stencil(self, kind, box, out_type, radius, taps, gscale) -> vv_stencil:
-        """box and out_type as _derive; radius: an int or (rx, ry, rz); taps: None, one row of up to 5 taps for all three axes, or three rows
+        """box and out_type as _box_and_type; radius: an int or (rx, ry, rz); taps: None, one row of up to 5 taps for all three axes, or three rows
         (x, y, z), taps[a][0] the centre; gscale: None (= (1, 1, 1)) or three multipliers."""
-        d = vv_stencil()
-        if box is not None:
-            d.box_lo[:] = [int(v) for v in box[0]]
-            d.box_hi[:] = [int(v) for v in box[1]]
+        d = self._box_and_type(vv_stencil(), box, out_type)
         d.kind = int(kind)
-        d.out_type = self.volume_type() if out_type is None else int(out_type)
         d.radius[:] = [int(radius)] * 3 if np.isscalar(radius) else [int(v) for v in radius]
         if taps is not None:
             t = np.asarray(taps, np.float32)
@@ -784,29 +799,17 @@ class Context:
             d.gscale[:] = [float(v) for v in gscale]
         return d
 
-    def _stencil_dims(self, d: vv_stencil):
-        if not any(d.box_lo) and not any(d.box_hi):
-            dims = (C.c_int * 3)()
-            self._chk(self.lib.vv_volume_dims(self.h, C.byref(dims), None))
-            return int(dims[0]), int(dims[1]), int(dims[2])
-        return tuple(max(int(h) - int(l), 0) for l, h in zip(d.box_lo, d.box_hi))
-
     def stencil(self, kind, box=None, out_type=None, radius=(0, 0, 0), taps=None, gscale=None, prefill=None) -> np.ndarray:
         """vv_stencil_volume into a host array [bz, by, bx] of uint8 or float32 (the box's extents).  `prefill`: the byte the buffer holds before
         the call (the result does not depend on it)."""
         d = self._stencil(kind, box, out_type, radius, taps, gscale)
-        bx, by, bz = self._stencil_dims(d)
-        out = np.empty((bz, by, bx), np.float32 if d.out_type == VOXEL_F32 else np.uint8)
-        if prefill is not None:
-            out.view(np.uint8)[...] = prefill
-        self._chk(self.lib.vv_stencil_volume(self.h, C.byref(d), out.ctypes.data if out.size else None, out.nbytes, 0, None))
-        return out
+        return self._volume_to_host(self.lib.vv_stencil_volume, d, self._out_dims(d), prefill)
 
     def stencil_device(self, out_ptr: int, capacity: int, kind, box=None, out_type=None, radius=(0, 0, 0), taps=None, gscale=None, stream: int = 0):
         """vv_stencil_volume into a device buffer of `capacity` bytes, enqueued on `stream`; returns the output's (bx, by, bz)."""
         d = self._stencil(kind, box, out_type, radius, taps, gscale)
-        self._chk(self.lib.vv_stencil_volume(self.h, C.byref(d), out_ptr or None, int(capacity), 1, stream or None))
-        return self._stencil_dims(d)
+        self._volume_to_device(self.lib.vv_stencil_volume, d, out_ptr, capacity, stream)
+        return self._out_dims(d)
 
     def smooth(self, radius=1, shape=TAPS_BINOMIAL, sigma=0.0, box=None, out_type=None) -> np.ndarray:
         """The volume (or a box of it) smoothed with stencil_taps(shape, r, sigma) on every axis; radius: an int or (rx, ry, rz)."""
@@ -827,38 +830,24 @@ class Context:
         of the output grid or None = the whole grid; out_type None = the volume's type."""
         d = vv_resample()
         d.dims[:] = [int(v) for v in dims]
-        if box is not None:
-            d.box_lo[:] = [int(v) for v in box[0]]
-            d.box_hi[:] = [int(v) for v in box[1]]
+        self._box_and_type(d, box, out_type)
         d.filter = int(filter)
-        d.out_type = self.volume_type() if out_type is None else int(out_type)
         m = (1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0) if matrix is None else np.asarray(matrix, np.float32).reshape(12)
         d.m[:] = [float(v) for v in m]
         d.fill = float(fill)
         return d
 
-    @staticmethod
-    def _resample_dims(d: vv_resample):
-        if not any(d.box_lo) and not any(d.box_hi):
-            return int(d.dims[0]), int(d.dims[1]), int(d.dims[2])
-        return tuple(max(int(h) - int(l), 0) for l, h in zip(d.box_lo, d.box_hi))
-
     def resample(self, dims, matrix=None, filter=RESAMPLE_TEX8, fill=0.0, out_type=None, box=None, prefill=None) -> np.ndarray:
         """vv_resample_volume into a host array [bz, by, bx] of uint8 or float32 (the box's extents).  `prefill`: the byte the buffer holds before
         the call (the result does not depend on it)."""
         d = self._resample(dims, matrix, filter, fill, out_type, box)
-        bx, by, bz = self._resample_dims(d)
-        out = np.empty((bz, by, bx), np.float32 if d.out_type == VOXEL_F32 else np.uint8)
-        if prefill is not None:
-            out.view(np.uint8)[...] = prefill
-        self._chk(self.lib.vv_resample_volume(self.h, C.byref(d), out.ctypes.data if out.size else None, out.nbytes, 0, None))
-        return out
+        return self._volume_to_host(self.lib.vv_resample_volume, d, self._out_dims(d, d.dims), prefill)
 
     def resample_device(self, out_ptr: int, capacity: int, dims, matrix=None, filter=RESAMPLE_TEX8, fill=0.0, out_type=None, box=None, stream: int = 0):
         """vv_resample_volume into a device buffer of `capacity` bytes, enqueued on `stream`; returns the output's (bx, by, bz)."""
         d = self._resample(dims, matrix, filter, fill, out_type, box)
-        self._chk(self.lib.vv_resample_volume(self.h, C.byref(d), out_ptr or None, int(capacity), 1, stream or None))
-        return self._resample_dims(d)
+        self._volume_to_device(self.lib.vv_resample_volume, d, out_ptr, capacity, stream)
+        return self._out_dims(d, d.dims)
 
     # VolumeGenerator::drawEllipsoid x n / drawDefaultBrain (volumegenerator.cpp:31-119)
     def generate_ellipsoids(self, nx: int, ny: int, nz: int, centers, axes, colors) -> np.ndarray:
