@@ -566,6 +566,86 @@ int  vv_resample_volume(vv_context *ctx, const vv_resample *r, void *out, size_t
 int  vv_resample_matrix(const float euler[3], float zoom, const float centre[3], const float scale[3] /* or NULL */,
                         float m[12]);   /* host only, no context */
 
+/* ---- segmentation: connected-component labels of a box of the loaded volume, and the volume masked by them (no reference counterpart) ----
+ * vv_label_volume labels the loaded volume where it lies, in HBM: the voxels of a box whose classification index lies in a range are the
+ * foreground, and every foreground voxel receives the label of its connected component.  vv_mask_volume then writes the volume where a test
+ * on the labels holds and `fill` elsewhere: thresholding by the table entries that colour a structure, keeping the region under a seed (or the
+ * largest region, or everything above a size), and rendering only that, without the volume leaving the device.
+ *  1. FOREGROUND: a voxel of the box is foreground iff bin_lo <= bin <= bin_hi, bin the classification index of vv_volume_histogram's rule 1 (the
+ *     byte of a u8 voxel).  A NaN has bin 0, +Inf has bin 255.
+ *  2. NEIGHBOURS: two voxels of the box are neighbours iff their coordinates differ by at most 1 on every axis and differ on exactly one axis
+ *     (connectivity 6), on at most two (18) or on up to three (26).  Voxels outside the box do not exist: a structure that the box cuts in two
+ *     becomes two components.  Unlike vv_derive_volume, vv_stencil_volume and vv_resample_volume, the result for a box is therefore NOT the crop
+ *     of the whole volume's result.
+ *  3. COMPONENT: the classes of the transitive closure of "neighbours and both foreground".
+ *  4. LABEL: a background voxel gets 0; a foreground voxel gets 1 + i_min, where i = ((z - lo_z) b_y + (y - lo_y)) b_x + (x - lo_x) numbers the
+ *     box's voxels (b = hi - lo) and i_min is the least i of the voxel's component.  The label is a property of the input alone: every output is
+ *     exact and the same from run to run.  The box may hold at most 2^32 - 2 voxels (0xFFFFFFFF is never a label).  `labels` is dense, x fastest,
+ *     with the box's extents: labels[i] is the label of voxel i.
+ *  5. SIZES (optional): sizes[i] = the number of voxels of the component whose least voxel is i, and 0 at every other i: sizes[label - 1] is the
+ *     size of a labelled voxel's component.
+ *  6. STATS (optional): foreground = the box's foreground voxels, components = their components; with `sizes`, largest_size = the largest
+ *     component's voxels and largest_label = the smallest label among the components of that size; without `sizes` (or without foreground) both
+ *     are 0.  reserved is written as 0.
+ *  7. What follows: (a) bin_lo = 0, bin_hi = 255: every voxel has label 1.  (b) The components under 6 refine those under 18, which refine those
+ *     under 26.  (c) Nothing depends on the pitch of the source, on the 64-bit addressing build, on the launch geometry, on how the volume was
+ *     loaded or on what the outputs held.  (d) No byte outside the box is read as data; no byte beyond 4 b_x b_y b_z of labels / sizes and
+ *     sizeof(vv_label_stats) of stats is written.
+ *  8. STREAM AND MEMORY: labels, sizes and stats are all host pointers or all device pointers (out_on_device).  Device labels and sizes must be
+ *     4-byte aligned, device stats 8-byte aligned.  A device-output call allocates no device memory: `labels` is its only volume-sized working
+ *     array, the counters live in scratch the context holds from vv_init on (keep enqueue-only calls of one context on one stream).  The call is
+ *     a fixed number of kernel launches for given arguments, with no host read-back between them: `stream` NULL = the context's stream, the call
+ *     returns when the work is complete; any other handle with device outputs only enqueues (as vv_stencil_volume).  Host outputs are staged
+ *     through device buffers of the call's own, released before it returns.  The context's volume, table, layout copies and residency state are
+ *     not touched; vv_last_frame_ms keeps its value.
+ *  9. Errors, in this order.  VV_ERR_INVALID: NULL ctx / d / labels.  VV_ERR_NO_VOLUME: no volume loaded.  VV_ERR_INVALID, each in turn: a box
+ *     outside vv_derive's rule 5; more than 2^32 - 2 voxels in the box; bins outside 0 <= bin_lo <= bin_hi <= 255; a connectivity other than 6, 18
+ *     or 26; capacity (bytes, of labels and of sizes each) below 4 b_x b_y b_z; a misaligned device pointer; a device labels or sizes whose byte
+ *     range overlaps the context's linear volume allocation or the other buffer.  VV_ERR_NOMEM: a staging buffer of a host output could not be
+ *     allocated.  A refused call writes nothing and leaves the context usable.
+ * vv_mask_volume: `out` receives a dense volume, x fastest, of the box's extents in out_type, ready for vv_load_volume_device / vv_load_volume_*.
+ *  M1. Output voxel i is KEPT iff test(i) != invert.  VV_KEEP_LABEL: labels[i] == label.  VV_KEEP_FOREGROUND: labels[i] != 0.  VV_KEEP_MIN_SIZE:
+ *      labels[i] != 0 && labels[i] - 1 < voxels && sizes[labels[i] - 1] >= min_size (voxels = b_x b_y b_z; the bound is part of the rule:
+ *      `labels` is caller data and never makes an address unchecked).
+ *  M2. A kept voxel is the source voxel through the copy stage: vv_derive_volume at factor 1 without a window (rule 3 there).  Any other voxel
+ *      is `fill` (storage units of the source) through the arithmetic output stage: vv_resample_volume's rule 4.
+ *  M3. What follows: with the labels of bins 0..255 and VV_KEEP_FOREGROUND, `out` equals vv_derive_volume at factor 1, same box and out_type,
+ *      byte for byte.  Rule 7 (c), (d) hold here too.
+ *  M4. labels, sizes and out are all host or all device pointers (on_device); device labels / sizes must be 4-byte aligned, a device f32 out
+ *      too.  Host buffers are staged through device buffers of the call's own; a device call allocates nothing.  `stream` as in rule 8.
+ *  M5. Errors, in this order.  VV_ERR_INVALID: NULL ctx / m / labels / out.  VV_ERR_NO_VOLUME: no volume loaded.  VV_ERR_INVALID, each in turn:
+ *      a box outside vv_derive's rule 5 or above 2^32 - 2 voxels; an out_type or keep outside its enum; invert not 0 or 1; a fill that is not
+ *      finite; VV_KEEP_MIN_SIZE with sizes == NULL; capacity (bytes) below the output's bytes; a misaligned device pointer; a device out whose
+ *      byte range overlaps the context's linear volume allocation, labels or sizes.  VV_ERR_NOMEM: a staging buffer could not be allocated.  A
+ *      refused call writes nothing and leaves the context usable.                                                                            */
+typedef struct vv_label {
+    int box_lo[3], box_hi[3];   /* as vv_derive: lo inclusive, hi exclusive, all six 0 = the whole volume */
+    int bin_lo, bin_hi;         /* foreground: bin_lo <= bin <= bin_hi, both in 0..255, bin_lo <= bin_hi */
+    int connectivity;           /* 6, 18 or 26 */
+} vv_label;                     /* 36 bytes */
+typedef struct vv_label_stats {
+    unsigned long long foreground;    /* foreground voxels of the box */
+    unsigned long long components;
+    unsigned long long largest_size;  /* 0 when `sizes` is NULL */
+    uint32_t largest_label;           /* smallest label among the components of that size; 0 when `sizes` is NULL or there is no foreground */
+    uint32_t reserved;                /* written as 0 */
+} vv_label_stats;                     /* 32 bytes */
+int  vv_label_volume(vv_context *ctx, const vv_label *d, uint32_t *labels, size_t capacity,
+                     uint32_t *sizes /* or NULL; same extents and capacity */, vv_label_stats *stats /* or NULL */,
+                     int out_on_device, void *stream);
+typedef enum { VV_KEEP_LABEL = 0, VV_KEEP_FOREGROUND = 1, VV_KEEP_MIN_SIZE = 2 } vv_keep;
+typedef struct vv_mask {
+    int      box_lo[3], box_hi[3];  /* the box the labels were made for */
+    int      out_type;              /* VV_VOXEL_U8 or VV_VOXEL_F32 */
+    int      keep;                  /* vv_keep */
+    int      invert;                /* 0 / 1 */
+    uint32_t label;                 /* VV_KEEP_LABEL */
+    uint32_t min_size;              /* VV_KEEP_MIN_SIZE (needs sizes) */
+    float    fill;                  /* storage units of the source, finite */
+} vv_mask;                          /* 48 bytes */
+int  vv_mask_volume(vv_context *ctx, const vv_mask *m, const uint32_t *labels, const uint32_t *sizes /* or NULL */,
+                    void *out, size_t capacity, int on_device, void *stream);
+
 /* The first pass on its own (firstpass.vert:6, firstpass.frag:4, glwidget.cpp:198-228): the
  * RGBA8 images the reference's two FBOs would hold for this camera -- cube-space entry (front
  * faces) and exit (back faces) positions, UNORM8-rounded, alpha 255 where a face is visible and

@@ -31,6 +31,9 @@ struct vv_knobs {
     int derive_blocks = -1;                 // VV_DERIVE_BLOCKS: the same for derive_kernel
     int stencil_blocks = -1;                // VV_STENCIL_BLOCKS: the same for the stencil kernels (their loop over (tile, z segment) items)
     int resample_blocks = -1;               // VV_RESAMPLE_BLOCKS: the same for resample_kernel (its loop over tiles)
+    int label_blocks = -1;                  // VV_LABEL_BLOCKS: the same for the label kernels and mask_kernel (tests vary the block order with it)
+    int label_phases = -1;                  // VV_LABEL_PHASES = 1 / 2 / 3: vv_label_volume stops behind its local / merge / flatten launch (tools/time_label.py times the
+                                            // launches by difference; the outputs are then unfinished)
     // finalize_layout: VV_PITCH_PAD = bytes of row padding (0 or anything that is no number: rows stay dense; not a multiple of 16 in 16..4096: the default),
     // VV_PITCH_FORCE (set: any row length is padded), VV_PITCH_ROWS = extra rows per slice (0..64, anything else: the default)
     int pitch_pad = 32, pitch_rows = -1; bool pitch_force = false;
@@ -45,6 +48,7 @@ struct vv_knobs {
         rect = geti("VV_RECT", -1); lpt = geti("VV_LPT", -1); lpt_run = geti("VV_LPT_RUN", -1); phong_bricks = geti("VV_PHONG_BRICKS", -1);
         hist_blocks = geti("VV_HIST_BLOCKS", -1); derive_blocks = geti("VV_DERIVE_BLOCKS", -1);
         stencil_blocks = geti("VV_STENCIL_BLOCKS", -1); resample_blocks = geti("VV_RESAMPLE_BLOCKS", -1);
+        label_blocks = geti("VV_LABEL_BLOCKS", -1); label_phases = geti("VV_LABEL_PHASES", -1);
         const int pad = geti("VV_PITCH_PAD", 32);
         pitch_pad = pad <= 0 ? 0 : ((pad >= 16 && pad <= 4096 && pad % 16 == 0) ? pad : 32);
         pitch_force = getenv("VV_PITCH_FORCE") != nullptr; pitch_rows = geti("VV_PITCH_ROWS", -1);
@@ -75,6 +79,7 @@ enum {
     SC_SLICE,       // the image of a host-buffer slice, both images of a slab slice
     SC_GEN,         // per-axis tables of the ellipsoid generator
     SC_TF_ARG,      // vv_classify_indices: the caller's table
+    SC_LABEL,       // vv_label_volume: the kernels' counters, then the vv_label_stats of a host-output call (kLabelScratchBytes, held from vv_init on)
     SC_N
 };
 struct scratch_buf { void *p = nullptr; size_t cap = 0; };
@@ -124,6 +129,10 @@ static std::string g_err;
 static const size_t kHistResultOffset = kHistAccWords * sizeof(unsigned long long);
 static const size_t kHistScratchBytes = kHistResultOffset + sizeof(vv_histogram);
 static_assert(sizeof(vv_histogram) == 2072 && sizeof(unsigned long long) == 8, "vv_histogram layout (include/volviz.h)");
+// scratch entry SC_LABEL: the counters of the label kernels, then (8-byte aligned) the vv_label_stats a host-output call copies back
+static const size_t kLabelStatsOffset = kLabelCounters * sizeof(unsigned long long);
+static const size_t kLabelScratchBytes = kLabelStatsOffset + sizeof(vv_label_stats);
+static_assert(sizeof(vv_label) == 36 && sizeof(vv_label_stats) == 32 && sizeof(vv_mask) == 48, "vv_label / vv_label_stats / vv_mask layout (include/volviz.h)");
 static const size_t kStageBytes = 64u << 20;      // streamed upload: pinned / device staging buffers (vv_context::pin, d_stage)
 
 static int fail(vv_context *c, int code, const std::string &msg)
@@ -300,22 +309,36 @@ static int check_out_volume(vv_context *c, const char *who, const char *whence, 
 // the scratch table: a volume-sized buffer must not stay resident in the context.  stage_call finds it as the buffer's fixed home (and uploads the
 // caller's bytes into it where the call works `in_place`); it is freed on every path.  `body(dev, st)` launches on the device volume and returns
 // VV_OK, or fails before it launches; the download and the wait are finish_call's.
+// run_out_volumes is the same for a short list of buffers (a call with several volume-sized arguments, inputs among them): every host buffer of the
+// list that has no home gets a device buffer of the call's own; `body(b, st)` finds the device addresses in b[i].dev.
+template <class Body>
+static int run_out_volumes(vv_context *c, const char *who, CallBuf *b, int n, void *stream, Body body)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    void *tmp[8] = {};
+    assert(n <= 8);
+    int rc = VV_OK;
+    for (int i = 0; i < n && rc == VV_OK; ++i) {
+        if (!b[i].host || !b[i].bytes || b[i].home) continue;
+        if (hipMalloc(&tmp[i], b[i].bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            tmp[i] = nullptr;
+            rc = fail(c, VV_ERR_NOMEM, std::string(who) + ": no device memory for the staging buffer of a host out");
+        } else b[i].home = tmp[i];
+    }
+    hipStream_t st;
+    if (rc == VV_OK) rc = stage_call(c, stream, &st, b, n);
+    if (rc == VV_OK) rc = body(b, st);
+    if (rc == VV_OK) rc = finish_call(c, stream, st, b, n);
+    for (void *t : tmp)
+        if (t) (void)hipFree(t);
+    return rc;
+}
 template <class Body>
 static int run_out_volume(vv_context *c, const char *who, void *out, size_t bytes, int out_on_device, bool in_place, void *stream, Body body)
 {
-    HIPCHK(c, hipSetDevice(c->device));
-    void *tmp = nullptr;
-    if (!out_on_device && hipMalloc(&tmp, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(c, VV_ERR_NOMEM, std::string(who) + ": no device memory for the staging buffer of a host out");
-    }
-    hipStream_t st;
-    CallBuf b = {out, bytes, !out_on_device, in_place, true, 0, tmp, nullptr};
-    int rc = stage_call(c, stream, &st, &b, 1);
-    if (rc == VV_OK) rc = body(b.dev, st);
-    if (rc == VV_OK) rc = finish_call(c, stream, st, &b, 1);
-    if (tmp) (void)hipFree(tmp);
-    return rc;
+    CallBuf b = {out, bytes, !out_on_device, in_place, true, 0, nullptr, nullptr};
+    return run_out_volumes(c, who, &b, 1, stream, [&](CallBuf *bb, hipStream_t st) { return body(bb[0].dev, st); });
 }
 
 static int finalize_layout(vv_context *c, hipStream_t st);
@@ -538,7 +561,8 @@ int vv_init(int device, vv_context **out)
         hipMalloc((void **)&c->d_counter, 16 * sizeof(unsigned long long)) != hipSuccess ||
         hipMalloc((void **)&c->d_hist, kHistScratchBytes) != hipSuccess ||
         hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess ||
-        hipMalloc((void **)&c->d_tf, 256 * sizeof(float4)) != hipSuccess) {
+        hipMalloc((void **)&c->d_tf, 256 * sizeof(float4)) != hipSuccess ||
+        ensure(c, SC_LABEL, kLabelScratchBytes) != VV_OK) {               // (held from here on: a label call allocates nothing)
         vv_shutdown(c);                           // (gives back whatever was created before the failure)
         return fail(nullptr, VV_ERR_DEVICE, "vv_init: device set-up failed");
     }
@@ -2004,6 +2028,119 @@ int vv_resample_volume(vv_context *c, const vv_resample *r, void *out, size_t ca
         A.out = dev;
         launch_resample(A, c->n_cu, c->knobs.resample_blocks, st);
         return VV_OK;
+    });
+}
+
+// ---- segmentation (include/volviz.h: vv_label_volume, vv_mask_volume) ------------------------
+static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+    return a && b && (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na;
+}
+// the box of a label / mask descriptor (lo, hi, extents b) and its voxel count, at most 2^32 - 2
+static int label_box(vv_context *c, const char *who, const int box_lo[3], const int box_hi[3], int lo[3], int hi[3], uint32_t b[3], unsigned long long *voxels)
+{
+    const int dims[3] = {c->nx, c->ny, c->nz};
+    const int rc = check_box(c, who, box_lo, box_hi, dims, lo, hi);
+    if (rc) return rc;
+    for (int a = 0; a < 3; ++a) b[a] = (uint32_t)(hi[a] - lo[a]);
+    *voxels = (unsigned long long)b[0] * b[1] * b[2];                // (each below 2^24: the product fits)
+    if (*voxels > 0xFFFFFFFEull) return fail(c, VV_ERR_INVALID, std::string(who) + ": the box may hold at most 2^32 - 2 voxels");
+    return VV_OK;
+}
+// what both kernels' source addressing is promised: the box's last voxel lies inside the allocation, f32 voxels are aligned
+static bool label_source_ok(const vv_context *c, const int hi[3])
+{
+    return box_end(c, hi) <= c->alloc_bytes && !(c->vtype == VV_VOXEL_F32 && (((uintptr_t)c->d_vol | c->row_pitch | c->slice_pitch) & 3) != 0);
+}
+
+int vv_label_volume(vv_context *c, const vv_label *d, uint32_t *labels, size_t capacity, uint32_t *sizes, vv_label_stats *stats, int out_on_device, void *stream)
+{
+    static const char who[] = "vv_label_volume";
+    if (!c) return fail(nullptr, VV_ERR_INVALID, "vv_label_volume: NULL context");
+    if (!d || !labels) return fail(c, VV_ERR_INVALID, "vv_label_volume: NULL argument");
+    if (!c->d_vol) return fail(c, VV_ERR_NO_VOLUME, "vv_label_volume: no volume loaded");
+    // the header's rule 9, in its order
+    int lo[3], hi[3];
+    LabelArgs A;
+    memset(&A, 0, sizeof A);
+    unsigned long long voxels;
+    int rc = label_box(c, who, d->box_lo, d->box_hi, lo, hi, A.b, &voxels);
+    if (rc) return rc;
+    if (!(0 <= d->bin_lo && d->bin_lo <= d->bin_hi && d->bin_hi <= 255)) return fail(c, VV_ERR_INVALID, "vv_label_volume: bins must satisfy 0 <= bin_lo <= bin_hi <= 255");
+    if (d->connectivity != 6 && d->connectivity != 18 && d->connectivity != 26) return fail(c, VV_ERR_INVALID, "vv_label_volume: connectivity must be 6, 18 or 26");
+    const size_t bytes = (size_t)voxels * sizeof(uint32_t);
+    if (capacity < bytes) return fail(c, VV_ERR_INVALID, "vv_label_volume: capacity is below 4 bytes per voxel of the box");
+    if (out_on_device) {
+        if ((((uintptr_t)labels | (uintptr_t)sizes) & 3) != 0) return fail(c, VV_ERR_INVALID, "vv_label_volume: device labels and sizes must be 4-byte aligned");
+        if (((uintptr_t)stats & 7) != 0) return fail(c, VV_ERR_INVALID, "vv_label_volume: a device stats must be 8-byte aligned");
+        if (ranges_overlap(labels, bytes, c->d_vol, c->alloc_bytes) || ranges_overlap(sizes, bytes, c->d_vol, c->alloc_bytes))
+            return fail(c, VV_ERR_INVALID, "vv_label_volume: labels / sizes overlap the loaded volume");
+        if (ranges_overlap(labels, bytes, sizes, bytes)) return fail(c, VV_ERR_INVALID, "vv_label_volume: labels and sizes overlap");
+    }
+    if (((uintptr_t)c->d_vol & 15) != 0 || !label_source_ok(c, hi) || !c->scratch[SC_LABEL].p)
+        return fail(c, VV_ERR_DEVICE, "vv_label_volume: volume allocation is not what the kernel expects");
+    A.src0 = (const char *)c->d_vol + voxel_offset(c, lo[0], lo[1], lo[2]);
+    A.row_pitch = c->row_pitch; A.slice_pitch = c->slice_pitch;
+    A.bin_lo = (uint32_t)d->bin_lo; A.bin_hi = (uint32_t)d->bin_hi;
+    A.src_type = c->vtype; A.connectivity = d->connectivity;
+    A.counters = (unsigned long long *)c->scratch[SC_LABEL].p;
+    const bool host = !out_on_device;
+    CallBuf b[3] = {
+        {labels, bytes, host, false, true, 0, nullptr, nullptr},
+        {sizes, sizes ? bytes : 0, host, false, true, 0, nullptr, nullptr},
+        {stats, stats ? sizeof(vv_label_stats) : 0, host, false, true, 0, (char *)c->scratch[SC_LABEL].p + kLabelStatsOffset, nullptr},
+    };
+    return run_out_volumes(c, who, b, 3, stream, [&](CallBuf *bb, hipStream_t st) {
+        A.labels = (uint32_t *)bb[0].dev; A.sizes = (uint32_t *)bb[1].dev; A.stats = (vv_label_stats *)bb[2].dev;
+        HIPCHK(c, hipMemsetAsync(A.counters, 0, kLabelCounters * sizeof(unsigned long long), st));
+        launch_label(A, c->n_cu, c->knobs.label_blocks, c->knobs.label_phases, st);
+        return (int)VV_OK;
+    });
+}
+
+int vv_mask_volume(vv_context *c, const vv_mask *m, const uint32_t *labels, const uint32_t *sizes, void *out, size_t capacity, int on_device, void *stream)
+{
+    static const char who[] = "vv_mask_volume";
+    if (!c) return fail(nullptr, VV_ERR_INVALID, "vv_mask_volume: NULL context");
+    if (!m || !labels || !out) return fail(c, VV_ERR_INVALID, "vv_mask_volume: NULL argument");
+    if (!c->d_vol) return fail(c, VV_ERR_NO_VOLUME, "vv_mask_volume: no volume loaded");
+    // the header's rule M5, in its order
+    int lo[3], hi[3];
+    MaskArgs A;
+    memset(&A, 0, sizeof A);
+    unsigned long long voxels;
+    int rc = label_box(c, who, m->box_lo, m->box_hi, lo, hi, A.b, &voxels);
+    if (rc) return rc;
+    if ((rc = check_out_type(c, who, m->out_type)) != VV_OK) return rc;
+    if (m->keep != VV_KEEP_LABEL && m->keep != VV_KEEP_FOREGROUND && m->keep != VV_KEEP_MIN_SIZE)
+        return fail(c, VV_ERR_INVALID, "vv_mask_volume: keep must be VV_KEEP_LABEL, VV_KEEP_FOREGROUND or VV_KEEP_MIN_SIZE");
+    if (m->invert != 0 && m->invert != 1) return fail(c, VV_ERR_INVALID, "vv_mask_volume: invert must be 0 or 1");
+    if (!std::isfinite(m->fill)) return fail(c, VV_ERR_INVALID, "vv_mask_volume: fill must be finite");
+    if (m->keep == VV_KEEP_MIN_SIZE && !sizes) return fail(c, VV_ERR_INVALID, "vv_mask_volume: VV_KEEP_MIN_SIZE needs sizes");
+    const int ext[3] = {(int)A.b[0], (int)A.b[1], (int)A.b[2]};
+    size_t bytes;
+    if ((rc = check_out_volume(c, who, "", out, capacity, on_device, m->out_type, ext, true, &bytes)) != VV_OK) return rc;
+    const size_t lbytes = (size_t)voxels * sizeof(uint32_t);
+    if (on_device) {
+        if ((((uintptr_t)labels | (uintptr_t)sizes) & 3) != 0) return fail(c, VV_ERR_INVALID, "vv_mask_volume: device labels and sizes must be 4-byte aligned");
+        if (ranges_overlap(out, bytes, labels, lbytes) || ranges_overlap(out, bytes, sizes, lbytes))
+            return fail(c, VV_ERR_INVALID, "vv_mask_volume: out overlaps labels or sizes (the pass is not in place)");
+    }
+    if (!label_source_ok(c, hi)) return fail(c, VV_ERR_DEVICE, "vv_mask_volume: volume allocation is not what the kernel expects");
+    A.src0 = (const char *)c->d_vol + voxel_offset(c, lo[0], lo[1], lo[2]);
+    A.row_pitch = c->row_pitch; A.slice_pitch = c->slice_pitch;
+    A.src_type = c->vtype; A.out_type = m->out_type; A.keep = m->keep; A.invert = m->invert;
+    A.label = m->label; A.min_size = m->min_size; A.fill = m->fill;
+    const bool host = !on_device;
+    CallBuf b[3] = {
+        {(void *)labels, lbytes, host, true, false, 0, nullptr, nullptr},
+        {(void *)sizes, sizes && m->keep == VV_KEEP_MIN_SIZE ? lbytes : 0, host, true, false, 0, nullptr, nullptr},    // (read under VV_KEEP_MIN_SIZE only)
+        {out, bytes, host, false, true, 0, nullptr, nullptr},
+    };
+    return run_out_volumes(c, who, b, 3, stream, [&](CallBuf *bb, hipStream_t st) {
+        A.labels = (const uint32_t *)bb[0].dev; A.sizes = (const uint32_t *)bb[1].dev; A.out = bb[2].dev;
+        launch_mask(A, c->n_cu, c->knobs.label_blocks, st);
+        return (int)VV_OK;
     });
 }
 

@@ -172,6 +172,34 @@ struct ResampleArgs {
     float inv[3], m[12], fill;
 };
 void launch_resample(const ResampleArgs &a, int n_cu, int max_blocks /* <= 0: one block per tile */, hipStream_t s);
+// segmentation (vv_label.hip).  launch_label: the connected components of the box of b[0] x b[1] x b[2] voxels whose first voxel is src0 (vv_label of
+// include/volviz.h, checked by the caller) as labels, x fastest, at `labels`; with `sizes` the components' voxel counts at their least voxels; with
+// `stats` a vv_label_stats.  counters: kLabelCounters words, all zero before the launch (the kernels' accumulators).  The caller vouches that the box
+// lies inside one allocation (f32: src0 and both pitches 4-byte aligned), that it holds at most 2^32 - 2 voxels and that labels / sizes hold as many
+// words outside it and outside each other.  Three launches, and one or two more with `stats`.
+constexpr int kLabelForeground = 0, kLabelComponents = 1, kLabelLargest = 2, kLabelCounters = 4;
+struct LabelArgs {
+    const void *src0; uint32_t *labels, *sizes; vv_label_stats *stats;
+    unsigned long long *counters;
+    uint64_t row_pitch, slice_pitch;        // of the source, bytes
+    uint32_t b[3];
+    uint32_t bin_lo, bin_hi;
+    int src_type, connectivity;             // vv_voxel_type; 6, 18 or 26
+};
+void launch_label(const LabelArgs &a, int n_cu, int max_blocks /* <= 0: one block per tile, a CU's complement of waves for the elementwise kernels */,
+                  int phases /* 1..3: stop behind that launch (timing aid); anything else: all */, hipStream_t s);
+// launch_mask: out[i] = the box's voxel i through the copy stage where the test on labels[i] holds (vv_mask of include/volviz.h, checked by the
+// caller), `fill` through the arithmetic output stage elsewhere.  labels / sizes: b[0] * b[1] * b[2] words each (sizes may be null unless keep is
+// VV_KEEP_MIN_SIZE), whatever they hold.
+struct MaskArgs {
+    const void *src0; const uint32_t *labels, *sizes; void *out;
+    uint64_t row_pitch, slice_pitch;        // of the source, bytes
+    uint32_t b[3];
+    int src_type, out_type, keep, invert;   // vv_voxel_type (2 x), vv_keep, 0 / 1
+    uint32_t label, min_size;
+    float fill;
+};
+void launch_mask(const MaskArgs &a, int n_cu, int max_blocks, hipStream_t s);
 void launch_first_pass(const FrameParams &P, uint32_t *front, uint32_t *back, hipStream_t s);
 
 size_t generate_scratch_floats(int nx, int ny, int nz, int n);

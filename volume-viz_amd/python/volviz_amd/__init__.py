@@ -37,6 +37,7 @@ STENCIL_MAX_RADIUS = 4
 TAPS_BOX, TAPS_BINOMIAL, TAPS_GAUSS = 0, 1, 2    # vv_taps_shape
 RESAMPLE_TEX8, RESAMPLE_EXACT, RESAMPLE_NEAREST = 0, 1, 2        # vv_resample_filter
 RESAMPLE_MAX_DIM = 16384
+KEEP_LABEL, KEEP_FOREGROUND, KEEP_MIN_SIZE = 0, 1, 2             # vv_keep
 RAYS_IMAGES, RAYS_ANALYTIC = 0, 1
 TF_ENGINE, TF_HEAD, TF_MRI = 0, 1, 2
 # `stream` arguments: 0/None = the context's own stream, synchronous; STREAM_DEFAULT_ASYNC = the device's default (null)
@@ -104,6 +105,37 @@ class vv_resample(C.Structure):           # 96 bytes
                 ("m", C.c_float * 12), ("fill", C.c_float)]
 
 
+class vv_label(C.Structure):              # 36 bytes
+    _fields_ = [("box_lo", C.c_int * 3), ("box_hi", C.c_int * 3), ("bin_lo", C.c_int), ("bin_hi", C.c_int), ("connectivity", C.c_int)]
+
+
+class vv_label_stats(C.Structure):        # 32 bytes
+    _fields_ = [("foreground", C.c_ulonglong), ("components", C.c_ulonglong), ("largest_size", C.c_ulonglong),
+                ("largest_label", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class vv_mask(C.Structure):               # 48 bytes
+    _fields_ = [("box_lo", C.c_int * 3), ("box_hi", C.c_int * 3), ("out_type", C.c_int), ("keep", C.c_int), ("invert", C.c_int),
+                ("label", C.c_uint32), ("min_size", C.c_uint32), ("fill", C.c_float)]
+
+
+@dataclass
+class LabelStats:
+    """vv_label_stats as Python ints."""
+    foreground: int
+    components: int
+    largest_size: int
+    largest_label: int
+    reserved: int = 0
+
+    @staticmethod
+    def from_bytes(raw) -> "LabelStats":
+        """From the 32 bytes of a vv_label_stats (e.g. read back from a device buffer)."""
+        raw = np.frombuffer(bytes(raw), np.uint8, C.sizeof(vv_label_stats))
+        q, w = raw[:24].view(np.uint64), raw[24:].view(np.uint32)
+        return LabelStats(int(q[0]), int(q[1]), int(q[2]), int(w[0]), int(w[1]))
+
+
 @dataclass
 class Histogram:
     """vv_histogram as numpy values: counts uint64[256], voxels, nan_voxels, vmin / vmax as np.float32 (bit for bit what the library wrote)."""
@@ -137,11 +169,13 @@ EXPORTS = [
     "vv_render_mip", "vv_classify_indices", "vv_render_iso", "vv_slice_slab", "vv_slice_advanced_slab",
     "vv_volume_histogram", "vv_histogram_indices", "vv_render_projection", "vv_debug_read_layout",
     "vv_derive_dims", "vv_derive_volume", "vv_stencil_volume", "vv_stencil_taps", "vv_resample_volume", "vv_resample_matrix",
+    "vv_label_volume", "vv_mask_volume",
 ]
 # entry points a variant library built from an earlier tree (A/B tools, load_library(path)) may lack
 _NEWER_EXPORTS = ("vv_render_mip", "vv_classify_indices", "vv_render_iso", "vv_slice_slab", "vv_slice_advanced_slab",
                   "vv_volume_histogram", "vv_histogram_indices", "vv_render_projection", "vv_debug_read_layout",
-                  "vv_derive_dims", "vv_derive_volume", "vv_stencil_volume", "vv_stencil_taps", "vv_resample_volume", "vv_resample_matrix")
+                  "vv_derive_dims", "vv_derive_volume", "vv_stencil_volume", "vv_stencil_taps", "vv_resample_volume", "vv_resample_matrix",
+                  "vv_label_volume", "vv_mask_volume")
 
 _lib = None
 _libs = {}
@@ -203,6 +237,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     if hasattr(lib, "vv_resample_volume"):
         lib.vv_resample_volume.argtypes = [vp, C.POINTER(vv_resample), vp, sz, i, vp]
         lib.vv_resample_matrix.argtypes = [C.POINTER(f * 3), f, C.POINTER(f * 3), C.POINTER(f * 3), C.POINTER(f * 12)]
+    if hasattr(lib, "vv_label_volume"):
+        lib.vv_label_volume.argtypes = [vp, C.POINTER(vv_label), vp, sz, vp, vp, i, vp]
+        lib.vv_mask_volume.argtypes = [vp, C.POINTER(vv_mask), vp, vp, vp, sz, i, vp]
     lib.vv_generate_ellipsoids.argtypes = [vp, vp, i, i, i, i, i, vp, vp, vp, vp]
     lib.vv_generate_default_brain.argtypes = [vp, vp, i, i, i, i, vp]
     lib.vv_draw_ellipsoid.argtypes = [vp, vp, i, i, i, i, vp, vp, C.c_uint8, vp]
@@ -848,6 +885,93 @@ class Context:
         d = self._resample(dims, matrix, filter, fill, out_type, box)
         self._volume_to_device(self.lib.vv_resample_volume, d, out_ptr, capacity, stream)
         return self._out_dims(d, d.dims)
+
+    # vv_label_volume / vv_mask_volume (no reference counterpart)
+    def _label(self, bins, connectivity, box) -> vv_label:
+        """bins = (bin_lo, bin_hi), both inclusive, or one bin; box = ((x0, y0, z0), (x1, y1, z1)) or None = the whole volume."""
+        d = vv_label()
+        if box is not None:
+            d.box_lo[:] = [int(v) for v in box[0]]
+            d.box_hi[:] = [int(v) for v in box[1]]
+        d.bin_lo, d.bin_hi = (int(bins), int(bins)) if np.isscalar(bins) else (int(bins[0]), int(bins[1]))
+        d.connectivity = int(connectivity)
+        return d
+
+    def label(self, bins, connectivity=6, box=None, sizes=False, stats=False, prefill=None):
+        """vv_label_volume into host arrays: labels [bz, by, bx] uint32; with `sizes` also the sizes array of the same shape; with `stats` also
+        a LabelStats (in that order, as a tuple).  `prefill`: the byte the outputs hold before the call (the result does not depend on it)."""
+        d = self._label(bins, connectivity, box)
+        shape = self._out_dims(d)[::-1]
+        labels = np.empty(shape, np.uint32)
+        size_arr = np.empty(shape, np.uint32) if sizes else None
+        st = vv_label_stats() if stats else None
+        if prefill is not None:
+            labels.view(np.uint8)[...] = prefill
+            if sizes:
+                size_arr.view(np.uint8)[...] = prefill
+            if stats:
+                C.memset(C.byref(st), prefill, C.sizeof(st))
+        self._chk(self.lib.vv_label_volume(self.h, C.byref(d), labels.ctypes.data if labels.size else None, labels.nbytes,
+                                           size_arr.ctypes.data if sizes else None, C.addressof(st) if stats else None, 0, None))
+        out = [labels]
+        if sizes:
+            out.append(size_arr)
+        if stats:
+            out.append(LabelStats.from_bytes(st))
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def label_device(self, labels_ptr: int, capacity: int, bins, connectivity=6, box=None, sizes_ptr: int = 0, stats_ptr: int = 0, stream: int = 0):
+        """vv_label_volume into device buffers (labels and sizes: `capacity` bytes each, 4-byte aligned; stats: 32 bytes, 8-byte aligned),
+        enqueued on `stream`; returns the box's (bx, by, bz)."""
+        d = self._label(bins, connectivity, box)
+        self._chk(self.lib.vv_label_volume(self.h, C.byref(d), labels_ptr or None, int(capacity), sizes_ptr or None, stats_ptr or None, 1, stream or None))
+        return self._out_dims(d)
+
+    def _mask(self, keep, label, min_size, invert, fill, box, out_type) -> vv_mask:
+        d = self._box_and_type(vv_mask(), box, out_type)
+        d.keep, d.invert, d.label, d.min_size, d.fill = int(keep), int(bool(invert)), int(label), int(min_size), float(fill)
+        return d
+
+    def mask(self, labels: np.ndarray, keep=KEEP_FOREGROUND, label=0, min_size=0, sizes=None, invert=False, fill=0.0, box=None, out_type=None,
+             prefill=None) -> np.ndarray:
+        """vv_mask_volume with host labels (and sizes) [bz, by, bx] uint32 into a host array of the same shape, uint8 or float32: the volume's
+        voxels where the test on the labels holds, `fill` elsewhere."""
+        d = self._mask(keep, label, min_size, invert, fill, box, out_type)
+        dims = self._out_dims(d)
+        labels = np.ascontiguousarray(labels, np.uint32)
+        if labels.shape != tuple(dims)[::-1]:
+            raise ValueError(f"labels have shape {labels.shape}, the box has {tuple(dims)[::-1]}")
+        if sizes is not None:
+            sizes = np.ascontiguousarray(sizes, np.uint32)
+            if sizes.shape != labels.shape:
+                raise ValueError(f"sizes have shape {sizes.shape}, the box has {labels.shape}")
+        out = np.empty(labels.shape, np.float32 if d.out_type == VOXEL_F32 else np.uint8)
+        if prefill is not None:
+            out.view(np.uint8)[...] = prefill
+        self._chk(self.lib.vv_mask_volume(self.h, C.byref(d), labels.ctypes.data, sizes.ctypes.data if sizes is not None else None,
+                                          out.ctypes.data, out.nbytes, 0, None))
+        return out
+
+    def mask_device(self, out_ptr: int, capacity: int, labels_ptr: int, keep=KEEP_FOREGROUND, label=0, min_size=0, sizes_ptr: int = 0, invert=False,
+                    fill=0.0, box=None, out_type=None, stream: int = 0):
+        """vv_mask_volume on device buffers, enqueued on `stream`; returns the box's (bx, by, bz)."""
+        d = self._mask(keep, label, min_size, invert, fill, box, out_type)
+        self._chk(self.lib.vv_mask_volume(self.h, C.byref(d), labels_ptr or None, sizes_ptr or None, out_ptr or None, int(capacity), 1, stream or None))
+        return self._out_dims(d)
+
+    def keep_component(self, seed, bins, connectivity=6, invert=False, fill=0.0, box=None, out_type=None) -> np.ndarray:
+        """The seeded region grow, composed of the two calls: label(bins, connectivity, box), then mask(KEEP_LABEL) with the label under
+        seed = (x, y, z) in volume coordinates.  ValueError if the seed lies outside the box or on background."""
+        labels = self.label(bins, connectivity, box)
+        lo = (0, 0, 0) if box is None else tuple(int(v) for v in box[0])
+        x, y, z = (int(s) - l for s, l in zip(seed, lo))
+        bz, by, bx = labels.shape
+        if not (0 <= x < bx and 0 <= y < by and 0 <= z < bz):
+            raise ValueError(f"seed {tuple(seed)} lies outside the box")
+        lab = int(labels[z, y, x])
+        if lab == 0:
+            raise ValueError(f"seed {tuple(seed)} is background for bins {bins}")
+        return self.mask(labels, KEEP_LABEL, label=lab, invert=invert, fill=fill, box=box, out_type=out_type)
 
     # VolumeGenerator::drawEllipsoid x n / drawDefaultBrain (volumegenerator.cpp:31-119)
     def generate_ellipsoids(self, nx: int, ny: int, nz: int, centers, axes, colors) -> np.ndarray:
