@@ -20,8 +20,27 @@ and they hold at least 20 distinct values.  Mean projections and composited fram
 limit.  The shares are taken over the images a family compares on one build (two cameras: one enters the volume at high z and x, the other at low
 addresses).  Offsets: exact in the linear layout; in a copy, whose order follows z (bricked, z-pair) or x (z-fastest, x-pair), proportional along that axis.
 
+The volume-to-volume families (derive, stencil, resample, label and mask; helpers in addressing_volumes.py) read the linear layout only and are held three ways:
+
+  test                                         what it runs                                                              what a bug would be
+  test_derive / _stencil / _resample /         the histogram's four boxes on every volume but u8_pair_top: below the     a source address formed in 32 bits, sign-extended,
+    _label_and_mask                            limit, across it inside a row, across it over a slice boundary, ending   or with a 24-bit multiply of the slice index
+                                               at the last voxel; device output with guard bytes, host path once
+  test_volume_outputs_beyond_4_gib             f32_above, u8_above: the whole volume derived, filtered, resampled into   an output offset (`dst`, `first` / `plane`, `at`)
+                                               8.4 / 7.4 GB; three slabs against the models, the copying calls against   or a grid-stride item counter in 32 bits
+                                               the regenerated source byte for byte; grid caps of 4096 blocks
+  test_label_box_of_more_than_2_to_31_voxels   2047 x 2049 x 1023 u8, sparse foreground, against a sparse model that     a signed compare, atomicMin or division of a
+                                               the CPU half ties to label_model; then a mask into 17 GB of f32           voxel index; `i0 * 4` in 32 bits
+
+The voxel that decides an output voxel of a straddling box is the source voxel (label and mask), the cell's first voxel (derive), the centre voxel
+(stencil), the lower corner of the sample position (resample); the same thresholds hold over the two straddling boxes together, with 20 distinct labels
+under connectivity 6 (under 26 a foreground share of 0.3 ... 0.6 is one component almost surely: there the records compared, label, size and masked
+voxel, are what is distinct).  The rotation of the resampled boxes leaves the box's centre where it is: vv_resample_matrix's `centre` is where the grid's
+centre lands, so it is handed c + A (1/2 - c).  The mask's `fill` is in storage units (rule M2): 0.25 on a u8 volume is 0.25 / 255 in an f32 output.
+
 The CPU half holds the same conditions for the thin volumes and shows once that the models notice the bugs this module is for (a slice pitch multiplied
-in 24 bits; an offset taken modulo 2^32; one sign-extended from 32 bits): profiles/addressing_sensitivity.txt."""
+in 24 bits; an offset taken modulo 2^32; one sign-extended from 32 bits): profiles/addressing_sensitivity.txt.  For every volume it asserts the boxes'
+properties and the shares from the layout alone, and it ties the sparse label model to label_model on the wide box's structures at 63 x 41 x 39."""
 import functools
 import os
 import re
@@ -31,12 +50,15 @@ from types import SimpleNamespace
 import numpy as np
 import pytest
 
+import addressing_volumes as AV
 import hist_model as HM
 import iso_model as IM
+import label_model as LM
 import mip_oracle as MO
 import oracle_lib as O
 import proj_model as PM
 import slab_model as SM
+import volume_out as VO
 import volviz_amd as vv
 import witness as Wt
 
@@ -50,6 +72,7 @@ CAM_HI = vv.Camera.orbit(3.0, 1.0, 0.6)                         # (2.08, 1.62, 1
 CAM_LO = vv.Camera.orbit(3.0, np.pi - 1.0, 0.6 + np.pi)         # the opposite corner: rays enter at low addresses
 CAMS = (("hi", CAM_HI), ("lo", CAM_LO))
 LEVEL_NEAR = 128                                                # the noise's median: hits among a ray's first samples
+WIDE_FG = 200                                                   # the wide label box: foreground byte on a background of 0 (test_label.py's FG)
 
 # build -> (knobs, vv_prepare_layouts bit, the copies it samples (vv_layout_state), the axis its offsets follow: 2 = z, 0 = x)
 BUILDS = {
@@ -359,17 +382,21 @@ def test_thin_volume_preconditions(name):
             _slice_condition(M.host, [(v, pair[0]) for v, pair in _slab_images(M.host, filt, mode)], first, f"{name} slabs mode {mode} filter {filt}")
 
 
-def _misread(host, pitch_of, offset_of):
+def _misread(host, pitch_of, offset_of, pitches=None):
     """The volume a kernel would see whose byte offset of voxel (z, y, x) is offset_of(z * pitch_of(slice pitch) + y * row + x * size): offsets that
-    fall outside the volume read 0."""
+    fall outside the volume read 0.  pitches: (row, slice) pitch in bytes of a re-pitched layout (its padding holds zeros); None: the dense one."""
     nz, ny, nx = host.shape
     size = host.itemsize
+    row, slice_bytes = pitches or (nx * size, ny * nx * size)
     flat, out = host.ravel(), np.empty(host.shape, host.dtype)
-    in_slice = np.arange(ny * nx, dtype=np.int64) * size
+    in_slice = (np.arange(ny, dtype=np.int64)[:, None] * row + np.arange(nx, dtype=np.int64)[None, :] * size).ravel()
     for z in range(nz):                                         # (a slice at a time: the volumes of several GB too)
-        off = offset_of(z * pitch_of(ny * nx * size) + in_slice)
-        ok = (off >= 0) & (off < host.nbytes)
-        out[z] = np.where(ok, flat[np.where(ok, off // size, 0)], host.dtype.type(0)).reshape(ny, nx)
+        off = offset_of(z * pitch_of(slice_bytes) + in_slice)
+        sz, rem = np.divmod(off, slice_bytes)
+        sy, sx = np.divmod(rem, row)
+        sx //= size
+        ok = (off >= 0) & (sz < nz) & (sy < ny) & (sx < nx)
+        out[z] = np.where(ok, flat[np.where(ok, (sz * ny + sy) * nx + sx, 0)], host.dtype.type(0)).reshape(ny, nx)
     return out
 
 
@@ -401,15 +428,32 @@ def _sensitivity(name, bug, good, bad):
         rows.append((f"slab mean {view[0]}",) + _differing(a[0].view(np.uint32), b[0].view(np.uint32), _slice_coords(view)[1].ravel()))
     ha, hb = (sum(HM.histogram(m.host[z:z + 64]).counts for z in range(0, m.host.shape[0], 64)) for m in (good, bad))      # (64 slices at a time)
     rows.append(("histogram bins",) + (int((ha != hb).sum()), 256))
-    return [(name, bug) + r for r in rows]
+    return [(name, bug) + r for r in rows] + _volume_call_sensitivity(name, bug, good.host, bad.host)
+
+
+def _volume_call_sensitivity(name, bug, good_host, bad_host):
+    """One row per volume-to-volume family: on how many output voxels of its calls on the two straddling boxes the models of the two volumes differ."""
+    V = _layout_only(name)
+    rows = []
+    for family in AV.FAMILIES:
+        boxes = _family_boxes(V, family)
+        differ = of = 0
+        for bname in AV.STRADDLING:
+            for case in AV.cases(family, bname, int(good_host.dtype == np.float32)):
+                a, b = (AV.records(family, AV.want(family, case, h, boxes[bname]), h, boxes[bname]) for h in (good_host, bad_host))
+                d = _differing(a[:, None, :], b[:, None, :])    # (per output voxel)
+                differ, of = differ + d[0], of + d[1]
+        rows.append((name, bug, f"{family}, straddling boxes", differ, of))
+    return rows
 
 
 def _write_sensitivity(rows, path):
-    lines = ["On how many of the compared pixels (bins) the host models of a misread volume differ from the models of the volume itself: what the",
+    lines = ["On how many of the compared pixels (bins, output voxels) the host models of a misread volume differ from the models of the volume itself: what the",
              "comparisons of tests/test_addressing.py would report if a kernel read its voxels through the offset named.  Written by",
              "tests/test_addressing.py::test_models_notice_a_misread_volume (thin volumes) and, for the volumes of several GB, by the same functions",
              "run once by hand (_sensitivity_of_big_volumes).  Offsets outside the volume read 0.  The low sagittal images of the large volumes lie",
-             "wholly below the limit and are read correctly: 0 by construction (they are the compared pixels decided below the limit).", "",
+             "wholly below the limit and are read correctly: 0 by construction (they are the compared pixels decided below the limit).  The rows of the",
+             "volume-to-volume families count the output voxels of all their calls on the two boxes that straddle the limit, in the library's pitches.", "",
              "volume".ljust(18) + "bug".ljust(38) + "image".ljust(46) + "differ".rjust(9) + "of".rjust(9)]
     lines += [r[0].ljust(18) + r[1].ljust(38) + r[2].ljust(46) + str(r[3]).rjust(9) + str(r[4]).rjust(9) for r in rows]
     with open(path, "w") as f:
@@ -448,16 +492,137 @@ def test_models_notice_a_misread_volume(name):
         pass                                                    # a read-only checkout: the assertions above are the test
 
 
-def _sensitivity_of_big_volumes(names=("f32_band", "u8_pair_refused", "f32_above", "u8_above")):
+def _sensitivity_of_big_volumes(names=("f32_band", "u8_pair_refused", "f32_above", "u8_above"), volume_calls_only=False):
     """The rows of the volumes of several GB (minutes of host time and 20 GB of host memory: run by hand, `python -c "import test_addressing as t;
-    t._sensitivity_of_big_volumes()"` from tests/): offsets modulo 2^32 on the volumes beyond 4 GiB, offsets sign-extended from 32 bits on the band volumes."""
+    t._sensitivity_of_big_volumes()"` from tests/): offsets modulo 2^32 on the volumes beyond 4 GiB, offsets sign-extended from 32 bits on the band volumes.
+    volume_calls_only: the rows of the volume-to-volume families alone, the others kept as the file has them."""
     keep = _read_sensitivity(SENSITIVITY_FILE)
     for name in names:
         good = Models(_host_noise(name), _table())
         bug = MOD32 if SPECS[name].limit == 1 << 32 else SIGN32
-        bad = Models(_misread(good.host, bug[1], bug[2]), good.tf)
-        keep = [k for k in keep if k[0] != name] + _sensitivity(name, bug[0], good, bad)
+        bad = None if volume_calls_only else Models(_misread(good.host, bug[1], bug[2]), good.tf)
+        if volume_calls_only:
+            V = _layout_only(name)                              # (these boxes lie where the library's layout passes the limit: its pitches)
+            bad = Models(_misread(good.host, bug[1], bug[2], (V.row_bytes, V.slice_bytes)), good.tf)
+            rows = _volume_call_sensitivity(name, bug[0], good.host, bad.host)
+            keep = [k for k in keep if k[0] != name or k[2] not in [r[2] for r in rows]] + rows
+        else:
+            keep = [k for k in keep if k[0] != name] + _sensitivity(name, bug[0], good, bad)
         _write_sensitivity(sorted(keep, key=lambda r: (NAMES.index(r[0]), r[1])), SENSITIVITY_FILE)
+
+
+# ---- the volume-to-volume families (derive, stencil, resample, label and mask): boxes, deciding voxels, conditions ----
+def _layout_only(name):
+    """What _hist_boxes and the conditions need of a Loaded, from the spec alone: the pitches by the re-pitch rule Loaded.__init__ states."""
+    s = SPECS[name]
+    dtype = np.float32 if s.dtype == "f32" else np.uint8
+    row, slice_bytes = AV.pitches(s.dims, np.dtype(dtype).itemsize)
+    return SimpleNamespace(name=name, spec=s, models=SimpleNamespace(host=np.empty((0, 0, 0), dtype)), row_bytes=row, slice_bytes=slice_bytes)
+
+
+def _layout(V):
+    return AV.Layout(V.spec.dims, V.models.host.itemsize, V.row_bytes, V.slice_bytes, V.spec.limit)
+
+
+def _family_boxes(V, family):
+    """_hist_boxes, grown where the family needs it; each keeps the property it is named for."""
+    L, out = _layout(V), {}
+    for bname, box in _hist_boxes(V).items():
+        out[bname] = AV.family_box(family, box, V.spec.dims)
+        assert AV.box_property(bname, out[bname], L, V.spec.dims), (V.name, family, bname, out[bname])
+    return out
+
+
+def _share_conditions(V, family):
+    """From the layout alone: of the output voxels of the two straddling boxes together, 10 % to 90 % are decided beyond the limit."""
+    L, out = _layout(V), {}
+    for what, off in AV.shares(family, _family_boxes(V, family), L):
+        share = float((off >= L.limit).mean())
+        assert len(off) >= 200 and 0.10 <= share <= 0.90, f"{V.name} {what}: {share:.3f} of {len(off)} output voxels are decided beyond the limit"
+        out[what] = round(share, 3)
+    return out
+
+
+def _volume_call_plan(V, family, host):
+    """Every call of one family on one volume with the model's output, and the module's conditions on the two straddling boxes asserted from the models
+    and the layout alone: [namespace(bname, box, k, case, want)]."""
+    L, boxes = _layout(V), _family_boxes(V, family)
+    src_type = int(host.dtype == np.float32)
+    plan = [SimpleNamespace(bname=bname, box=box, k=k, case=case, want=AV.want(family, case, host, box))
+            for bname, box in boxes.items() for k, case in enumerate(AV.cases(family, bname, src_type, other_type=bname == "inside a row"))]
+    labels = []
+    for k, case in enumerate(AV.cases(family, "across slices", src_type)):
+        items = [p for p in plan if p.bname in AV.STRADDLING and p.k == k]
+        assert [p.bname for p in items] == list(AV.STRADDLING)
+        off, rec = [], []
+        for p in items:
+            o, ok = AV.deciding(family, p.case, p.box, L)
+            assert o.shape == (p.want[0] if family == "label and mask" else p.want).shape
+            off.append(o[ok]); rec.append(AV.records(family, p.want, host, p.box)[ok.ravel()])
+        what = f"{V.name} {family} {({k_: v for k_, v in case.items() if k_ != 'taps'})}"
+        print(what, _decided(np.concatenate(off), L.limit, np.concatenate(rec), what))
+        if family == "label and mask":
+            labels.append(len(np.unique(np.concatenate([p.want[0][p.want[0] > 0] for p in items]))))
+    if family == "label and mask":
+        # 20 distinct labels across both sides.  Under 26 a foreground share of 0.3 ... 0.6 lies at three to six times the percolation threshold
+        # (0.097): nearly all of it is one component whatever the noise, so the count is asserted under 6 and the 26 run must have fewer components.
+        assert labels[0] >= 20 and 1 <= labels[1] < labels[0], (V.name, labels)
+        for p in plan:
+            share = p.want[2].foreground / p.want[0].size
+            assert 0.3 <= share <= 0.6, (V.name, p.bname, share)
+    return plan
+
+
+def test_volume_call_boxes_and_shares():
+    """Every volume whose linear layout passes its limit, without voxel data: the boxes have the properties they are named for and the deciding voxels
+    of the straddling boxes lie on both sides of the limit, for each of the four families."""
+    assert [n for n in NAMES if n not in LINEAR_NAMES] == ["u8_pair_top"]
+    s = SPECS["u8_pair_top"]
+    assert AV.pitches(s.dims, 1)[1] * s.dims[2] < s.limit           # nothing of its linear layout lies beyond the limit: no box can straddle it
+    for name in LINEAR_NAMES:
+        V = _layout_only(name)
+        assert (V.slice_bytes * V.spec.dims[2] > 1 << 32 or V.slice_bytes >= 1 << 24) == V.spec.big, name
+        for family in AV.FAMILIES:
+            print(name, family, _share_conditions(V, family))
+
+
+@pytest.mark.parametrize("family", AV.FAMILIES)
+@pytest.mark.parametrize("name", THIN)
+def test_thin_volume_call_preconditions(name, family):
+    """The full conditions of the four families' comparisons on the thin volumes, from the models alone."""
+    _volume_call_plan(_layout_only(name), family, _thin_models(name).host)
+
+
+@pytest.mark.parametrize("connectivity", LM.CONNECTIVITIES)
+def test_sparse_label_model_is_the_label_model(connectivity):
+    """The wide label box's structures in a 63 x 41 x 39 volume: the sparse model over the coordinate list equals label_model.label."""
+    dims = AV.SMALL["dims"]
+    idx, parts = AV.wide_foreground(**AV.SMALL)
+    vol = np.zeros(dims[::-1], np.uint8)
+    vol.ravel()[idx] = WIDE_FG
+    labels, sizes, stats = LM.label(vol, (WIDE_FG, WIDE_FG), connectivity)
+    got = AV.sparse_label(idx, dims, connectivity)
+    assert np.array_equal(got[0], labels.ravel()[idx]) and np.array_equal(got[1], sizes.ravel()[idx]), connectivity
+    assert got[2] == (stats.foreground, stats.components, stats.largest_size, stats.largest_label, stats.reserved)
+    assert int(labels.astype(bool).sum()) == len(idx) and int(sizes.astype(bool).sum()) == stats.components
+    _wide_conditions(idx, parts, got, AV.SMALL["half"], AV.SMALL["stairs"], connectivity)
+
+
+def _wide_conditions(idx, parts, model, half, stairs, connectivity):
+    """What the wide label box must show before a kernel runs: `stairs` expected labels above `half` (the staircase's voxels under 6; the loop's under
+    every connectivity), a component with members on both sides of `half` whose label is tiny, a unique largest component."""
+    labels, sizes, stats = model
+    high = labels[labels.astype(np.int64) - 1 >= half]           # (a label is an index + 1)
+    assert len(high) >= stairs and len(np.unique(high)) >= (stairs if connectivity == 6 else 2), (connectivity, len(high), len(np.unique(high)))
+    loop = labels[np.isin(idx, parts["loop"])]
+    assert len(np.unique(loop)) == 1 and int(loop[0]) == int(parts["loop"].min()) + 1 > half
+    wire = labels[np.isin(idx, parts["wire"])]
+    assert len(np.unique(wire)) == 1 and int(wire[0]) - 1 < idx[-1] >> 8
+    members = idx[labels == wire[0]]
+    assert members.min() < half <= members.max() and members.max() == idx[-1]
+    assert int((sizes == stats[2]).sum()) == 1 and stats[3] == int(wire[0])
+    st = labels[np.isin(idx, parts["stairs"])]
+    assert len(np.unique(st)) == {6: stairs, 18: stairs // 2, 26: 1}[connectivity]
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -758,5 +923,349 @@ def test_histogram_counts_more_than_2_to_32_voxels_of_one_value(ctx):
             assert int(h.counts[0]) == nx * ny * nz == h.voxels and int(h.counts[1:].sum()) == 0 and h.vmin == 0 and h.vmax == 0 and h.nan_voxels == 0
     finally:
         os.environ.pop("VV_HIST_BLOCKS", None)
+        with MO.knobs(ctx, {}):
+            ctx.load_volume(np.zeros((4, 4, 4), np.uint8), tf)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the volume-to-volume families: source addresses beyond the limits (boxes), outputs beyond 2^32 bytes, a label box of more than 2^31 voxels
+# ---------------------------------------------------------------------------------------------------------------------
+def _report(family, got, want, what):
+    VO.report(got, want, AV.same(family, got, want), what)
+
+
+def _device_and_host(ctx, family, p, dims):
+    """(device call(ptr, capacity) -> (bx, by, bz), host call() -> array) of one planned call of derive, stencil or resample."""
+    c = p.case
+    if family == "derive":
+        kw = dict(box=p.box, factor=c["factor"], mode=c["mode"], out_type=c["out_type"])
+        return (lambda ptr, cap: ctx.derive_device(ptr, cap, **kw)), (lambda: ctx.derive(prefill=VO.GARBAGE, **kw))
+    if family == "stencil":
+        kw = dict(box=p.box, out_type=c["out_type"], radius=c.get("radius", (0, 0, 0)), taps=c.get("taps"))
+        return (lambda ptr, cap: ctx.stencil_device(ptr, cap, c["kind"], **kw)), (lambda: ctx.stencil(c["kind"], prefill=VO.GARBAGE, **kw))
+    assert family == "resample"
+    matrix = None
+    if c["rotated"]:
+        matrix = vv.resample_matrix(AV.EULER, 1.0, AV.rotation_centre(p.box, dims))
+        assert matrix.tobytes() == AV.rotation(p.box, dims).tobytes(), "vv_resample_matrix is not the model's matrix"
+    kw = dict(matrix=matrix, filter=c["filter"], fill=0.0, box=p.box)
+    return (lambda ptr, cap: ctx.resample_device(ptr, cap, dims, **kw)), (lambda: ctx.resample(dims, prefill=VO.GARBAGE, **kw))
+
+
+def _volume_calls(V, family):
+    """derive, stencil or resample on the four boxes of one volume: every planned call into the guarded device buffer, and through the host path
+    once per call kind on the box that straddles the limit inside a row."""
+    ctx, host = V.ctx, V.models.host
+    with MO.knobs(ctx, {}):
+        V.prepare("linear")
+        plan = V.models.get(("volume calls", family), lambda: _volume_call_plan(V, family, host))
+        dev = VO.DeviceOut(max(p.want.nbytes for p in plan))
+        for p in plan:
+            what = f"{V.name} {family} box {p.bname} {p.box} {({k: v for k, v in p.case.items() if k != 'taps'})}"
+            device_call, host_call = _device_and_host(ctx, family, p, V.spec.dims)
+            _report(family, dev.run(device_call, p.want.shape, p.want.dtype.type, what), p.want, what + " (device)")
+            if p.bname == "inside a row" and (family != "derive" or p.case["mode"] == 0):
+                _report(family, host_call(), p.want, what + " (host)")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("vol", LINEAR_NAMES, indirect=True)
+def test_derive(vol):
+    """derive_kernel: vector loads (factor 1 from a 16-voxel boundary) and the generic path, source addresses on both sides of the limit."""
+    _volume_calls(vol, "derive")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("vol", LINEAR_NAMES, indirect=True)
+def test_stencil(vol):
+    """stencil_sep_kernel, the median and the gradient magnitude; the boxes `below` and `last voxel` clamp at the volume's first and last slice."""
+    _volume_calls(vol, "stencil")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("vol", LINEAR_NAMES, indirect=True)
+def test_resample(vol):
+    """resample_kernel on the volume's own grid, identity and a small rotation about the box's centre, TEX8 / EXACT / NEAREST: the 32-bit offsets
+    (with the 24-bit slice multiply) below the limits of VolumeView::big, the 64-bit slice bases beyond them."""
+    assert max(vol.spec.dims) <= 16384
+    _volume_calls(vol, "resample")
+
+
+def _guarded_words(torch, n):
+    """n uint32 words on the device between two guards of 16 words, everything 0xA5A5A5A5: (tensor, pointer of the words)."""
+    t = torch.full((n + 32,), 0xA5A5A5A5 - (1 << 32), dtype=torch.int32, device=torch.device("cuda", 0))
+    return t, t.data_ptr() + 64
+
+
+def _words(t, n, what):
+    raw = t.cpu().numpy().view(np.uint32)
+    assert (raw[:16] == 0xA5A5A5A5).all() and (raw[16 + n:] == 0xA5A5A5A5).all(), f"words outside the output were written ({what})"
+    return raw[16:16 + n].copy()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("vol", LINEAR_NAMES, indirect=True)
+def test_label_and_mask(vol):
+    """label_local_kernel and the merge phases read `src` on both sides of the limit; mask_kernel is fed the labels and sizes the call left on the device."""
+    import torch
+    V, ctx, host = vol, vol.ctx, vol.models.host
+    family = "label and mask"
+    with MO.knobs(ctx, {}):
+        V.prepare("linear")
+        plan = V.models.get(("volume calls", family), lambda: _volume_call_plan(V, family, host))
+        dev = VO.DeviceOut(max(p.want[0].size for p in plan) * 4)
+        for p in plan:
+            labels, sizes, stats = p.want
+            n, conn, bins = labels.size, p.case["connectivity"], AV.label_bins(host, p.box)
+            what = f"{V.name} label box {p.bname} {p.box} bins {bins} connectivity {conn}"
+            lab_t, lab_p = _guarded_words(torch, n)
+            siz_t, siz_p = _guarded_words(torch, n)
+            st_t = torch.full((6,), -1, dtype=torch.int64, device=torch.device("cuda", 0))
+            torch.cuda.synchronize()
+            assert ctx.label_device(lab_p, n * 4, bins, conn, p.box, sizes_ptr=siz_p, stats_ptr=st_t.data_ptr() + 8) == labels.shape[::-1]
+            _report(family, _words(lab_t, n, what).reshape(labels.shape), labels, what + ": labels")
+            _report(family, _words(siz_t, n, what).reshape(labels.shape), sizes, what + ": sizes")
+            st = st_t.cpu().numpy()
+            got = vv.LabelStats.from_bytes(st[1:5].tobytes())
+            assert st[0] == -1 and st[5] == -1 and (got.foreground, got.components, got.largest_size, got.largest_label, got.reserved) == \
+                (stats.foreground, stats.components, stats.largest_size, stats.largest_label, 0), (what, got, stats)
+            for mc in AV.mask_cases():
+                want = AV.want_mask(host, labels, sizes, p.box, mc)
+                mwhat = f"{what}: mask {mc}"
+                got = dev.run(lambda ptr, cap: ctx.mask_device(ptr, cap, lab_p, mc["keep"], min_size=mc["min_size"], sizes_ptr=siz_p, fill=mc["fill"], box=p.box,
+                                                               out_type=mc["out_type"]), want.shape, want.dtype.type, mwhat)
+                _report(family, got, want, mwhat)
+            if p.bname == "inside a row":
+                got = ctx.label(bins, conn, p.box, sizes=True, stats=True, prefill=VO.GARBAGE)
+                _report(family, got[0], labels, what + ": host labels")
+                _report(family, got[1], sizes, what + ": host sizes")
+                assert (got[2].foreground, got[2].components, got[2].largest_size, got[2].largest_label) == (stats.foreground, stats.components, stats.largest_size, stats.largest_label)
+                mc = AV.mask_cases()[3]
+                _report(family, ctx.mask(got[0], mc["keep"], min_size=mc["min_size"], sizes=got[1], fill=mc["fill"], box=p.box, out_type=mc["out_type"], prefill=VO.GARBAGE),
+                        AV.want_mask(host, labels, sizes, p.box, mc), what + ": host mask")
+
+
+OUT_GUARD = 64                                                  # the DeviceOut rule by hand: 0xA5 everywhere before a call, 64 bytes on either side of the output
+
+
+class _BigOut:
+    """A device buffer for outputs of several GB: nothing of its size ever goes to the host."""
+
+    def __init__(self, torch, nbytes):
+        self.torch, self.nbytes = torch, nbytes
+        self.buf = torch.empty(nbytes + 2 * OUT_GUARD, dtype=torch.uint8, device=torch.device("cuda", 0))
+        self.ptr = self.buf.data_ptr() + OUT_GUARD
+        assert self.ptr % 16 == 0
+
+    def run(self, call, nbytes, dims, what):
+        """call(ptr, capacity) -> the output's (mx, my, mz), complete on return; the bytes before and behind the output keep 0xA5."""
+        assert nbytes <= self.nbytes
+        self.buf.fill_(VO.GARBAGE)
+        self.torch.cuda.synchronize()
+        assert tuple(call(self.ptr, nbytes)) == tuple(dims), what
+        self.torch.cuda.synchronize()
+        tail = self.buf[OUT_GUARD + nbytes:]
+        assert bool((self.buf[:OUT_GUARD] == VO.GARBAGE).all()) and all(bool((tail[a:a + (1 << 30)] == VO.GARBAGE).all()) for a in range(0, tail.numel(), 1 << 30)), \
+            f"bytes outside the output were written ({what})"
+
+    def slices(self, z0, z1, dims, dtype):
+        """Output slices z0 .. z1 - 1 of an output of `dims` on the host."""
+        sb = dims[0] * dims[1] * np.dtype(dtype).itemsize
+        return self.buf[OUT_GUARD + z0 * sb:OUT_GUARD + z1 * sb].cpu().numpy().view(dtype).reshape(z1 - z0, dims[1], dims[0])
+
+    def tensor(self, nbytes, torch_dtype):
+        return self.buf[OUT_GUARD:OUT_GUARD + nbytes].view(torch_dtype)
+
+
+def _output_slabs(dims, itemsize):
+    """(z0, z1) of the three compared slabs of an output of `dims`: its first three slices, three slices around output byte 2^32, its last three; from
+    the arithmetic: the middle slab's bytes straddle 2^32 and the last slab ends at the output's last byte."""
+    mx, my, mz = dims
+    sb = mx * my * itemsize
+    assert sb * mz > 1 << 32 and mz >= 6
+    zc = min(max((1 << 32) // sb - 1, 0), mz - 3)
+    slabs = ((0, 3), (zc, zc + 3), (mz - 3, mz))
+    assert slabs[1][0] * sb < 1 << 32 < slabs[1][1] * sb and slabs[2][1] * sb == sb * mz and slabs[0][1] * sb < 1 << 32
+    return slabs
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("vol", ["f32_above", "u8_above"], indirect=True)
+def test_volume_outputs_beyond_4_gib(vol):
+    """The whole volume derived, filtered and resampled into outputs of more than 2^32 bytes: derive's `dst`, stencil_item's `first` / `plane`, resample's
+    `at`.  (a) three slabs of each output against the model of the slab; (b) the calls that copy by contract -- derive at factor 1, a separable pass of
+    radius 0, NEAREST under the identity -- against the source regenerated on the device, every byte; (c) the guard bytes; (d) derive and the stencils
+    once more under a grid cap of 4096 blocks: their grid-stride loops then carry the item counters past 2^32 bytes."""
+    import torch
+    V, ctx, host = vol, vol.ctx, vol.models.host
+    dims = nx, ny, nz = V.spec.dims
+    n, size = nx * ny * nz, host.itemsize
+    own = int(host.dtype == np.float32)
+    assert n * size > 1 << 32
+    taps1 = AV.StM.taps(AV.StM.BINOMIAL, 1)
+    rot = vv.resample_matrix(AV.EULER, 1.0, (0.5, 0.5, 0.5))
+    assert rot.tobytes() == AV.RM.matrix(AV.EULER, 1.0, (0.5, 0.5, 0.5)).tobytes()
+    zbox = lambda s, z_off=0: ((0, 0, s[0] + z_off), (nx, ny, s[1] + z_off))
+    sep = dict(kind=AV.StM.SEPARABLE, radius=(1, 1, 1), taps=taps1, out_type=own)
+    med = dict(kind=AV.StM.MEDIAN, out_type=own)
+    # name -> (device call, the model of an output slab (z0, z1), output dims, output dtype)
+    calls = {
+        "derive": (lambda p, cap: ctx.derive_device(p, cap, None, 1, AV.DM.MEAN, own), lambda s: AV.DM.derive(host, zbox(s), 1, AV.DM.MEAN, own), dims, host.dtype),
+        "separable": (lambda p, cap: ctx.stencil_device(p, cap, sep["kind"], None, own, sep["radius"], taps1), lambda s: AV.want("stencil", sep, host, zbox(s)), dims, host.dtype),
+        "median": (lambda p, cap: ctx.stencil_device(p, cap, med["kind"], None, own), lambda s: AV.want("stencil", med, host, zbox(s)), dims, host.dtype),
+        "resample": (lambda p, cap: ctx.resample_device(p, cap, dims, rot, AV.RM.TEX8, 0.0, own), lambda s: AV.RM.resample(host, dims, rot, AV.RM.TEX8, 0.0, own, zbox(s)),
+                     dims, host.dtype),
+    }
+    if not own:                                                 # u8 -> f32 of the last slices: an output just above 2^32 bytes
+        zr = (1 << 32) // (nx * ny * 4) + 1
+        assert (zr - 1) * nx * ny * 4 <= 1 << 32 < zr * nx * ny * 4 <= n and zr < nz
+        calls["derive u8 -> f32"] = (lambda p, cap: ctx.derive_device(p, cap, zbox((nz - zr, nz)), 1, AV.DM.MEAN, AV.DM.F32),
+                                     lambda s: AV.DM.derive(host, zbox(s, nz - zr), 1, AV.DM.MEAN, AV.DM.F32), (nx, ny, zr), np.dtype(np.float32))
+    copies = {"derive": calls["derive"][0], "separable, radius 0": lambda p, cap: ctx.stencil_device(p, cap, AV.StM.SEPARABLE, None, own, (0, 0, 0)),
+              "nearest, identity": lambda p, cap: ctx.resample_device(p, cap, dims, None, AV.RM.NEAREST, 0.0, own)}
+    with MO.knobs(ctx, {}):
+        V.prepare("linear")
+        out = _BigOut(torch, n * size)
+        wants = {name: [V.models.get(("outputs", name, s), lambda: c[1](s)) for s in _output_slabs(c[2], c[3].itemsize)] for name, c in calls.items()}
+
+        def slabs_match(name, what):
+            _, _, odims, dtype = calls[name]
+            for s, want in zip(_output_slabs(odims, dtype.itemsize), wants[name]):
+                got = out.slices(s[0], s[1], odims, dtype)
+                assert len(np.unique(want)) >= 20, (what, s)
+                VO.report(got, want, AV.DM.same(got, want), f"{V.name} {what}: output slices {s}")
+
+        for name, (call, _, odims, dtype) in calls.items():
+            out.run(call, odims[0] * odims[1] * odims[2] * dtype.itemsize, odims, f"{V.name} {name}")
+            slabs_match(name, name)
+        try:                                                    # (d)
+            os.environ["VV_DERIVE_BLOCKS"] = os.environ["VV_STENCIL_BLOCKS"] = "4096"
+            ctx.reread_env()
+            for name in ("derive", "separable", "median"):
+                out.run(calls[name][0], n * size, dims, f"{V.name} {name} under a grid cap of 4096")
+                slabs_match(name, name + " under a grid cap of 4096")
+        finally:
+            os.environ.pop("VV_DERIVE_BLOCKS", None)
+            os.environ.pop("VV_STENCIL_BLOCKS", None)
+            ctx.reread_env()
+        # (b) the source as Loaded made it, in a scratch tensor; the copies against it, 64 slices at a time
+        tdev = torch.device("cuda", 0)
+        src = torch.empty(n, dtype=torch.uint8, device=tdev)
+        for z0, z1, seed in _noise_parts(dims):
+            ctx.generate_noise_device(src.data_ptr() + z0 * ny * nx, nx, ny, z1 - z0, seed)
+        if own:
+            v8, src = src, torch.empty(n, dtype=torch.float32, device=tdev)
+            ctx.promote_device(v8.data_ptr(), src.data_ptr(), n)
+            torch.cuda.synchronize()
+            del v8
+        torch.cuda.synchronize()
+        src = src.view(torch.int32) if own else src
+        assert bool((src[:nx * ny] == torch.from_numpy(np.ascontiguousarray(host[0]).view(np.int32 if own else np.uint8).ravel().copy()).to(tdev)).all()), "the regenerated source"
+        step = 64 * nx * ny
+        for name, call in copies.items():
+            out.run(call, n * size, dims, f"{V.name} {name}")
+            got = out.tensor(n * size, torch.int32 if own else torch.uint8)
+            bad = [a // (nx * ny) for a in range(0, n, step) if not torch.equal(got[a:a + step], src[a:a + step])]
+            assert not bad, f"{V.name} {name}: the output is not the source in the slices from {bad[:8]} on (64 at a time; {len(bad)} such runs)"
+        del src, out
+        torch.cuda.empty_cache()
+
+
+@pytest.mark.gpu
+def test_label_box_of_more_than_2_to_31_voxels(ctx):
+    """2047 x 2049 x 1023 voxels, a sparse foreground (addressing_volumes.wide_foreground): vv_label_volume's 32-bit parent pointers, its unsigned
+    atomicMin, the division of indices in label_flatten_kernel and the stats key with indices and labels at and above 2^31, against the sparse model;
+    then vv_mask_volume into 17 GB of f32.  Everything volume-sized stays on the device."""
+    import torch
+    dims = nx, ny, nz = AV.WIDE_DIMS
+    n = nx * ny * nz
+    assert 1 << 31 < n <= (1 << 32) - 2 and all(d % t for d, t in zip(dims, (16, 8, 8))) and (1 << 31) // (nx * ny) == 512
+    tdev = torch.device("cuda", 0)
+    free_b, total_b = torch.cuda.mem_get_info(tdev)
+    if total_b < 100 * 2 ** 30:                                  # (Loaded's rule: only a physically smaller GPU model skips)
+        pytest.skip(f"device has {total_b / 2 ** 30:.0f} GiB in all: not an MI355X-class GPU")
+    assert free_b >= 60 * 2 ** 30, f"the wide label box needs 60 GiB of free HBM, the device reports {free_b / 2 ** 30:.1f} of {total_b / 2 ** 30:.0f} GiB free"
+    idx, parts = AV.wide_foreground(**AV.WIDE)
+    assert idx[-1] == n - 1 > (1 << 32) - (1 << 24)
+    models = {conn: AV.sparse_label(idx, dims, conn) for conn in (6, 26)}
+    for conn, m in models.items():
+        _wide_conditions(idx, parts, m, AV.WIDE["half"], AV.WIDE["stairs"], conn)
+    tf = _table()
+    chunk = 64 * nx * ny                                        # 64 slices at a time: every torch call sees fewer than 2^31 elements
+    cuts = np.searchsorted(idx, np.arange(0, n + chunk, chunk))
+    at = [(a, torch.from_numpy(idx[cuts[i]:cuts[i + 1]] - a).to(tdev)) for i, a in enumerate(range(0, n, chunk))]       # per chunk: its foreground, relative
+
+    def gathered(t):
+        return torch.cat([t[a:a + chunk][rel] for a, rel in at]).cpu().numpy().view(np.uint32)
+
+    def nonzero(t):
+        return sum(int(torch.count_nonzero(t[a:a + chunk])) for a, _ in at)
+
+    try:
+        with MO.knobs(ctx, {}):
+            v = torch.zeros(n, dtype=torch.uint8, device=tdev)
+            for a, rel in at:
+                v[a:a + chunk][rel] = WIDE_FG
+            assert nonzero(v) == len(idx)
+            ctx.load_volume_device(v.data_ptr(), vv.VOXEL_U8, nx, ny, nz, tf)
+            torch.cuda.synchronize()
+            del v
+            torch.cuda.empty_cache()
+            garbage = 0xA5A5A5A5 - (1 << 32)
+            lab_t = torch.empty(n + 32, dtype=torch.int32, device=tdev)
+            for blocks, conn in ((None, 6), (None, 26), ("4096", 6), ("4096", 26)):
+                labels, sizes, stats = models[conn]
+                what = f"connectivity {conn} VV_LABEL_BLOCKS={blocks}"
+                if blocks is not None:
+                    os.environ["VV_LABEL_BLOCKS"] = blocks
+                ctx.reread_env()
+                siz_t = torch.empty(n + 32, dtype=torch.int32, device=tdev)
+                st_t = torch.full((6,), -1, dtype=torch.int64, device=tdev)
+                lab_t.fill_(garbage); siz_t.fill_(garbage)
+                torch.cuda.synchronize()
+                lab, siz = lab_t[16:16 + n], siz_t[16:16 + n]
+                assert ctx.label_device(lab.data_ptr(), n * 4, (WIDE_FG, WIDE_FG), conn, sizes_ptr=siz.data_ptr(), stats_ptr=st_t.data_ptr() + 8) == dims
+                torch.cuda.synchronize()
+                for t in (lab_t, siz_t):
+                    assert bool((t[:16] == garbage).all()) and bool((t[16 + n:] == garbage).all()), f"words outside the output were written ({what})"
+                assert nonzero(lab) == len(idx) and nonzero(siz) == stats[1], (what, nonzero(lab), nonzero(siz), stats)
+                got_l, got_s = gathered(lab), gathered(siz)
+                bad = np.flatnonzero(got_l != labels)
+                assert len(bad) == 0, f"{what}: {len(bad)} labels differ, first at index {idx[bad[0]]}: {got_l[bad[0]]} vs {labels[bad[0]]}"
+                bad = np.flatnonzero(got_s != sizes)
+                assert len(bad) == 0, f"{what}: {len(bad)} sizes differ, first at index {idx[bad[0]]}: {got_s[bad[0]]} vs {sizes[bad[0]]}"
+                st = st_t.cpu().numpy()
+                got = vv.LabelStats.from_bytes(st[1:5].tobytes())
+                assert st[0] == -1 and st[5] == -1 and (got.foreground, got.components, got.largest_size, got.largest_label, got.reserved) == stats, (what, got, stats)
+                os.environ.pop("VV_LABEL_BLOCKS", None)
+                if blocks is None and conn == 6:                 # the mask, fed the labels and sizes of this call (under 6 the staircase's voxels are components of one)
+                    wire = int(labels[np.searchsorted(idx, parts["wire"][0])])
+                    assert wire == stats[3]
+                    count = np.bincount(np.searchsorted(idx, labels.astype(np.int64) - 1), minlength=len(idx))      # per listed voxel: its component's size
+                    comp = count[np.searchsorted(idx, labels.astype(np.int64) - 1)]
+                    keeps = (("KEEP_LABEL", dict(keep=vv.KEEP_LABEL, label=wire), labels == wire), ("KEEP_MIN_SIZE", dict(keep=vv.KEEP_MIN_SIZE, min_size=2), comp >= 2))
+                    out_t = torch.empty(n + 32, dtype=torch.float32, device=tdev)
+                    kept_bits = LM.copy_stage(np.full(1, WIDE_FG, np.uint8), LM.F32).view(np.uint32)[0]         # 200 / 255 as binary32
+                    fill_bits = int(LM.fill_stage(0.25, np.uint8, LM.F32).reshape(1).view(np.uint32)[0])          # rule M2: the fill is in storage units, 0.25 / 255
+                    assert kept_bits == (np.float32(WIDE_FG) / np.float32(255)).view(np.uint32) and fill_bits == int((np.float32(0.25) / np.float32(255)).view(np.uint32))
+                    for kname, kw, keep in keeps:
+                        assert 0 < keep.sum() < len(idx), kname
+                        out_t.view(torch.int32).fill_(garbage)
+                        torch.cuda.synchronize()
+                        o = out_t[16:16 + n]
+                        assert ctx.mask_device(o.data_ptr(), n * 4, lab.data_ptr(), sizes_ptr=siz.data_ptr(), fill=0.25, out_type=vv.VOXEL_F32, **kw) == dims
+                        torch.cuda.synchronize()
+                        ob = out_t.view(torch.int32)
+                        assert bool((ob[:16] == garbage).all()) and bool((ob[16 + n:] == garbage).all()), f"words outside the mask output were written ({kname})"
+                        ob = ob[16:16 + n]
+                        other = sum(int(torch.count_nonzero(ob[a:a + chunk] != fill_bits)) for a, _ in at)
+                        got_o = gathered(ob)
+                        assert other == int(keep.sum()) and np.array_equal(got_o, np.where(keep, kept_bits, np.uint32(fill_bits))), \
+                            (kname, other, int(keep.sum()), [hex(v) for v in got_o[:4]], [hex(int(v)) for v in ob[:4].cpu().numpy().view(np.uint32)])
+                    del out_t, o, ob
+                del siz_t, siz
+                torch.cuda.empty_cache()
+    finally:
+        os.environ.pop("VV_LABEL_BLOCKS", None)
         with MO.knobs(ctx, {}):
             ctx.load_volume(np.zeros((4, 4, 4), np.uint8), tf)
