@@ -646,6 +646,57 @@ typedef struct vv_mask {
 int  vv_mask_volume(vv_context *ctx, const vv_mask *m, const uint32_t *labels, const uint32_t *sizes /* or NULL */,
                     void *out, size_t capacity, int on_device, void *stream);
 
+/* ---- distance transform: the exact squared Euclidean distance of every voxel of a box to a voxel set (no reference counterpart) ----
+ * vv_distance_volume writes, for a box of the loaded volume, how far each voxel lies from the nearest SEED: a voxel chosen by its classification
+ * index or by a test on labels that vv_label_volume (or this call) wrote for the box.  With integer voxel pitches the squared distance is an
+ * integer and a property of the input alone.  Growing a margin, and opening or closing a segmentation with a ball, are this call composed with
+ * itself on the device (Context.morphology of the Python binding).
+ *  1. SEEDS: a voxel of the box is a seed iff test != invert.  VV_SEED_BINS: bin_lo <= bin <= bin_hi, bin the classification index of
+ *     vv_label_volume's rule 1 read from the loaded volume (a NaN has bin 0, +Inf has bin 255).  VV_SEED_LABEL: labels[i] == label.
+ *     VV_SEED_NONZERO: labels[i] != 0.
+ *  2. LABELS: `labels` is dense, x fastest, with the box's extents (i as in vv_label_volume's rule 4): what vv_label_volume or a VV_DIST_WITHIN
+ *     call wrote for that box.  NULL for VV_SEED_BINS.
+ *  3. BOX: voxels outside the box do not exist (vv_label_volume's rule 2): a seed one voxel outside the box is not seen, and the complement of
+ *     a set ends at the box's faces (an erosion does not eat in from them).  The result for a box is NOT the crop of the whole volume's.
+ *  4. DISTANCE: D(i) = min over the seeds s of sum_a (spacing_a (i_a - s_a))^2, an integer.  VV_DIST_SQUARED writes D(i) as uint32; 0xFFFFFFFF
+ *     at every voxel if the box has no seed.  VV_DIST_WITHIN writes 1 where D(i) <= within_r2 and 0 elsewhere (everywhere without a seed).
+ *  5. COMPOSITION: a VV_DIST_WITHIN result is a valid `labels` for vv_mask_volume (VV_KEEP_FOREGROUND) and for another vv_distance_volume.
+ *  6. EXACTNESS: every output word is exact and the same from run to run.  Nothing depends on the pitch of the source, on the 64-bit addressing
+ *     build, on the launch geometry, on how the volume was loaded or on what `out` held.  No byte outside the box is read as data; no byte
+ *     beyond 4 b_x b_y b_z of `out` is written.
+ *  7. LIMITS: every extent of the box is at most 2048 (a line and its working arrays live in one block's LDS); the box holds at most 2^32 - 2
+ *     voxels; sum_a (spacing_a (b_a - 1))^2, formed in 64 bits, is at most 0xFFFFFFFE, so every D(i) is below the no-seed marker.
+ *  8. ALIASING: out == labels, the identical pointer, is allowed for host and for device buffers (a line is read completely by the one block
+ *     that owns it before that block writes it).  Any other overlap of a device `out` with `labels` or with the context's linear volume
+ *     allocation is refused.
+ *  9. STREAM AND MEMORY (vv_label_volume's rule 8): labels and out are both host or both device pointers (on_device); device pointers must be
+ *     4-byte aligned.  A device call allocates nothing: `out` is the only volume-sized working array and the call takes no scratch.  The call is
+ *     three kernel launches, with no host read-back: `stream` NULL = the context's stream, the call returns when the work is complete; any other
+ *     handle with device buffers only enqueues.  Host buffers are staged through device buffers of the call's own (out == labels: one buffer,
+ *     uploaded and downloaded), released before it returns.  The context's volume, table, layout copies and residency state are not touched;
+ *     vv_last_frame_ms keeps its value.
+ * 10. Errors, in this order.  VV_ERR_INVALID: NULL ctx / d / out.  VV_ERR_NO_VOLUME: no volume loaded (for the labels sources too: the box is
+ *     measured against the volume).  VV_ERR_INVALID, each in turn: a box outside vv_derive's rule 5; more than 2^32 - 2 voxels in the box; an
+ *     extent above 2048; a seed outside its enum; VV_SEED_BINS with bins outside 0 <= bin_lo <= bin_hi <= 255; labels == NULL for a labels
+ *     source or labels != NULL for VV_SEED_BINS; invert not 0 or 1; a spacing below 1; the distance bound of rule 7; an `out` mode outside its
+ *     enum; capacity (bytes) below 4 b_x b_y b_z; a misaligned device pointer; an overlap that rule 8 refuses.  VV_ERR_NOMEM: a staging buffer
+ *     could not be allocated.  A refused call writes nothing and leaves the context usable.                                                  */
+#define VV_DISTANCE_MAX_EXTENT 2048
+typedef enum { VV_SEED_BINS = 0, VV_SEED_LABEL = 1, VV_SEED_NONZERO = 2 } vv_seed;
+typedef enum { VV_DIST_SQUARED = 0, VV_DIST_WITHIN = 1 } vv_dist_out;
+typedef struct vv_distance {
+    int      box_lo[3], box_hi[3];   /* as vv_label */
+    int      seed;                   /* vv_seed */
+    int      bin_lo, bin_hi;         /* VV_SEED_BINS: vv_label's rule 1 */
+    uint32_t label;                  /* VV_SEED_LABEL */
+    int      invert;                 /* 0 / 1: the seeds are the voxels where the test FAILS */
+    int      spacing[3];             /* x, y, z voxel pitch as positive integers (1,1,1 = isotropic) */
+    int      out;                    /* vv_dist_out */
+    uint32_t within_r2;              /* VV_DIST_WITHIN */
+} vv_distance;                       /* 64 bytes */
+int  vv_distance_volume(vv_context *ctx, const vv_distance *d, const uint32_t *labels /* NULL for VV_SEED_BINS */,
+                        uint32_t *out, size_t capacity, int on_device, void *stream);
+
 /* The first pass on its own (firstpass.vert:6, firstpass.frag:4, glwidget.cpp:198-228): the
  * RGBA8 images the reference's two FBOs would hold for this camera -- cube-space entry (front
  * faces) and exit (back faces) positions, UNORM8-rounded, alpha 255 where a face is visible and

@@ -34,6 +34,8 @@ struct vv_knobs {
     int label_blocks = -1;                  // VV_LABEL_BLOCKS: the same for the label kernels and mask_kernel (tests vary the block order with it)
     int label_phases = -1;                  // VV_LABEL_PHASES = 1 / 2 / 3: vv_label_volume stops behind its local / merge / flatten launch (tools/time_label.py times the
                                             // launches by difference; the outputs are then unfinished)
+    int distance_blocks = -1;               // VV_DISTANCE_BLOCKS: cap on the grids of the distance kernels (tests vary the block order with it)
+    int distance_phases = -1;               // VV_DISTANCE_PHASES = 1 / 2: vv_distance_volume stops behind its x / y launch (tools/time_distance.py, as VV_LABEL_PHASES)
     // finalize_layout: VV_PITCH_PAD = bytes of row padding (0 or anything that is no number: rows stay dense; not a multiple of 16 in 16..4096: the default),
     // VV_PITCH_FORCE (set: any row length is padded), VV_PITCH_ROWS = extra rows per slice (0..64, anything else: the default)
     int pitch_pad = 32, pitch_rows = -1; bool pitch_force = false;
@@ -49,6 +51,7 @@ struct vv_knobs {
         hist_blocks = geti("VV_HIST_BLOCKS", -1); derive_blocks = geti("VV_DERIVE_BLOCKS", -1);
         stencil_blocks = geti("VV_STENCIL_BLOCKS", -1); resample_blocks = geti("VV_RESAMPLE_BLOCKS", -1);
         label_blocks = geti("VV_LABEL_BLOCKS", -1); label_phases = geti("VV_LABEL_PHASES", -1);
+        distance_blocks = geti("VV_DISTANCE_BLOCKS", -1); distance_phases = geti("VV_DISTANCE_PHASES", -1);
         const int pad = geti("VV_PITCH_PAD", 32);
         pitch_pad = pad <= 0 ? 0 : ((pad >= 16 && pad <= 4096 && pad % 16 == 0) ? pad : 32);
         pitch_force = getenv("VV_PITCH_FORCE") != nullptr; pitch_rows = geti("VV_PITCH_ROWS", -1);
@@ -133,6 +136,7 @@ static_assert(sizeof(vv_histogram) == 2072 && sizeof(unsigned long long) == 8, "
 static const size_t kLabelStatsOffset = kLabelCounters * sizeof(unsigned long long);
 static const size_t kLabelScratchBytes = kLabelStatsOffset + sizeof(vv_label_stats);
 static_assert(sizeof(vv_label) == 36 && sizeof(vv_label_stats) == 32 && sizeof(vv_mask) == 48, "vv_label / vv_label_stats / vv_mask layout (include/volviz.h)");
+static_assert(sizeof(vv_distance) == 64, "vv_distance layout (include/volviz.h)");
 static const size_t kStageBytes = 64u << 20;      // streamed upload: pinned / device staging buffers (vv_context::pin, d_stage)
 
 static int fail(vv_context *c, int code, const std::string &msg)
@@ -2140,6 +2144,66 @@ int vv_mask_volume(vv_context *c, const vv_mask *m, const uint32_t *labels, cons
     return run_out_volumes(c, who, b, 3, stream, [&](CallBuf *bb, hipStream_t st) {
         A.labels = (const uint32_t *)bb[0].dev; A.sizes = (const uint32_t *)bb[1].dev; A.out = bb[2].dev;
         launch_mask(A, c->n_cu, c->knobs.label_blocks, st);
+        return (int)VV_OK;
+    });
+}
+
+// ---- distance transform (include/volviz.h: vv_distance_volume) ------------------------
+int vv_distance_volume(vv_context *c, const vv_distance *d, const uint32_t *labels, uint32_t *out, size_t capacity, int on_device, void *stream)
+{
+    static const char who[] = "vv_distance_volume";
+    if (!c) return fail(nullptr, VV_ERR_INVALID, "vv_distance_volume: NULL context");
+    if (!d || !out) return fail(c, VV_ERR_INVALID, "vv_distance_volume: NULL argument");
+    if (!c->d_vol) return fail(c, VV_ERR_NO_VOLUME, "vv_distance_volume: no volume loaded");
+    // the header's rule 10, in its order
+    int lo[3], hi[3];
+    DistanceArgs A;
+    memset(&A, 0, sizeof A);
+    unsigned long long voxels;
+    int rc = label_box(c, who, d->box_lo, d->box_hi, lo, hi, A.b, &voxels);
+    if (rc) return rc;
+    for (int a = 0; a < 3; ++a)
+        if (A.b[a] > (uint32_t)VV_DISTANCE_MAX_EXTENT) return fail(c, VV_ERR_INVALID, "vv_distance_volume: every extent of the box must be at most 2048");
+    if (d->seed != VV_SEED_BINS && d->seed != VV_SEED_LABEL && d->seed != VV_SEED_NONZERO)
+        return fail(c, VV_ERR_INVALID, "vv_distance_volume: seed must be VV_SEED_BINS, VV_SEED_LABEL or VV_SEED_NONZERO");
+    const bool bins = d->seed == VV_SEED_BINS;
+    if (bins && !(0 <= d->bin_lo && d->bin_lo <= d->bin_hi && d->bin_hi <= 255)) return fail(c, VV_ERR_INVALID, "vv_distance_volume: bins must satisfy 0 <= bin_lo <= bin_hi <= 255");
+    if (bins ? labels != nullptr : labels == nullptr) return fail(c, VV_ERR_INVALID, "vv_distance_volume: labels must be NULL for VV_SEED_BINS and given for the labels sources");
+    if (d->invert != 0 && d->invert != 1) return fail(c, VV_ERR_INVALID, "vv_distance_volume: invert must be 0 or 1");
+    for (int a = 0; a < 3; ++a)
+        if (d->spacing[a] < 1) return fail(c, VV_ERR_INVALID, "vv_distance_volume: every spacing must be at least 1");
+    unsigned long long bound = 0;
+    for (int a = 0; a < 3; ++a) {                                           // (a term alone may pass 2^64: stop at the first one above the bound)
+        const unsigned long long far = (unsigned long long)d->spacing[a] * (A.b[a] - 1);
+        if (far > 0xFFFFull || (bound += far * far) > 0xFFFFFFFEull)
+            return fail(c, VV_ERR_INVALID, "vv_distance_volume: the largest squared distance of the box, sum of (spacing (extent - 1))^2, must be at most 0xFFFFFFFE");
+    }
+    if (d->out != VV_DIST_SQUARED && d->out != VV_DIST_WITHIN) return fail(c, VV_ERR_INVALID, "vv_distance_volume: out must be VV_DIST_SQUARED or VV_DIST_WITHIN");
+    const size_t bytes = (size_t)voxels * sizeof(uint32_t);
+    if (capacity < bytes) return fail(c, VV_ERR_INVALID, "vv_distance_volume: capacity is below 4 bytes per voxel of the box");
+    const bool aliased = labels == out;
+    if (on_device) {
+        if ((((uintptr_t)labels | (uintptr_t)out) & 3) != 0) return fail(c, VV_ERR_INVALID, "vv_distance_volume: device labels and out must be 4-byte aligned");
+        if (ranges_overlap(out, bytes, c->d_vol, c->alloc_bytes)) return fail(c, VV_ERR_INVALID, "vv_distance_volume: out overlaps the loaded volume");
+        if (!aliased && ranges_overlap(out, bytes, labels, bytes))
+            return fail(c, VV_ERR_INVALID, "vv_distance_volume: out overlaps labels without being the same pointer");
+    }
+    if (!label_source_ok(c, hi)) return fail(c, VV_ERR_DEVICE, "vv_distance_volume: volume allocation is not what the kernel expects");
+    A.src0 = (const char *)c->d_vol + voxel_offset(c, lo[0], lo[1], lo[2]);
+    A.row_pitch = c->row_pitch; A.slice_pitch = c->slice_pitch;
+    for (int a = 0; a < 3; ++a) A.spacing[a] = (uint32_t)d->spacing[a];
+    A.bin_lo = (uint32_t)d->bin_lo; A.bin_hi = (uint32_t)d->bin_hi; A.label = d->label; A.within_r2 = d->within_r2;
+    A.src_type = c->vtype; A.seed = d->seed; A.invert = d->invert; A.mode = d->out;
+    const bool host = !on_device;
+    // out == labels: one buffer, uploaded and downloaded; else the labels (if any) are an input and out an output
+    CallBuf b[2] = {
+        {out, bytes, host, aliased, true, 0, nullptr, nullptr},
+        {(void *)labels, labels && !aliased ? bytes : 0, host, true, false, 0, nullptr, nullptr},
+    };
+    return run_out_volumes(c, who, b, 2, stream, [&](CallBuf *bb, hipStream_t st) {
+        A.out = (uint32_t *)bb[0].dev;
+        A.labels = bins ? nullptr : aliased ? (const uint32_t *)bb[0].dev : (const uint32_t *)bb[1].dev;
+        launch_distance(A, c->n_cu, c->knobs.distance_blocks, c->knobs.distance_phases, st);
         return (int)VV_OK;
     });
 }

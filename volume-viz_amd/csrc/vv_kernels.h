@@ -200,6 +200,19 @@ struct MaskArgs {
     float fill;
 };
 void launch_mask(const MaskArgs &a, int n_cu, int max_blocks, hipStream_t s);
+// distance transform (vv_distance.hip).  launch_distance: the squared Euclidean distance of every voxel of the box of b[0] x b[1] x b[2] voxels to the
+// nearest seed (vv_distance of include/volviz.h, checked by the caller), x fastest, at `out`; three launches, in place on `out`.  The caller vouches
+// for what launch_label's caller does, that every extent is at most VV_DISTANCE_MAX_EXTENT, that sum_a (spacing[a] (b[a] - 1))^2 <= 0xFFFFFFFE, and
+// that `labels` (the labels sources) holds b[0] * b[1] * b[2] words and is `out` itself or lies outside it.
+struct DistanceArgs {
+    const void *src0; const uint32_t *labels; uint32_t *out;
+    uint64_t row_pitch, slice_pitch;        // of the source, bytes
+    uint32_t b[3], spacing[3];
+    uint32_t bin_lo, bin_hi, label, within_r2;
+    int src_type, seed, invert, mode;       // vv_voxel_type, vv_seed, 0 / 1, vv_dist_out
+};
+void launch_distance(const DistanceArgs &a, int n_cu, int max_blocks /* <= 0: a block per four rows / per tile of lines */,
+                     int phases /* 1, 2: stop behind that launch (timing aid); anything else: all three */, hipStream_t s);
 void launch_first_pass(const FrameParams &P, uint32_t *front, uint32_t *back, hipStream_t s);
 
 size_t generate_scratch_floats(int nx, int ny, int nz, int n);

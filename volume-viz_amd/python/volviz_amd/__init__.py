@@ -38,6 +38,11 @@ TAPS_BOX, TAPS_BINOMIAL, TAPS_GAUSS = 0, 1, 2    # vv_taps_shape
 RESAMPLE_TEX8, RESAMPLE_EXACT, RESAMPLE_NEAREST = 0, 1, 2        # vv_resample_filter
 RESAMPLE_MAX_DIM = 16384
 KEEP_LABEL, KEEP_FOREGROUND, KEEP_MIN_SIZE = 0, 1, 2             # vv_keep
+SEED_BINS, SEED_LABEL, SEED_NONZERO = 0, 1, 2                    # vv_seed
+DIST_SQUARED, DIST_WITHIN = 0, 1                                 # vv_dist_out
+DISTANCE_MAX_EXTENT = 2048
+DISTANCE_NONE = 0xFFFFFFFF                                       # DIST_SQUARED of a box without a seed
+MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3  # Context.morphology
 RAYS_IMAGES, RAYS_ANALYTIC = 0, 1
 TF_ENGINE, TF_HEAD, TF_MRI = 0, 1, 2
 # `stream` arguments: 0/None = the context's own stream, synchronous; STREAM_DEFAULT_ASYNC = the device's default (null)
@@ -119,6 +124,11 @@ class vv_mask(C.Structure):               # 48 bytes
                 ("label", C.c_uint32), ("min_size", C.c_uint32), ("fill", C.c_float)]
 
 
+class vv_distance(C.Structure):           # 64 bytes
+    _fields_ = [("box_lo", C.c_int * 3), ("box_hi", C.c_int * 3), ("seed", C.c_int), ("bin_lo", C.c_int), ("bin_hi", C.c_int),
+                ("label", C.c_uint32), ("invert", C.c_int), ("spacing", C.c_int * 3), ("out", C.c_int), ("within_r2", C.c_uint32)]
+
+
 @dataclass
 class LabelStats:
     """vv_label_stats as Python ints."""
@@ -169,13 +179,13 @@ EXPORTS = [
     "vv_render_mip", "vv_classify_indices", "vv_render_iso", "vv_slice_slab", "vv_slice_advanced_slab",
     "vv_volume_histogram", "vv_histogram_indices", "vv_render_projection", "vv_debug_read_layout",
     "vv_derive_dims", "vv_derive_volume", "vv_stencil_volume", "vv_stencil_taps", "vv_resample_volume", "vv_resample_matrix",
-    "vv_label_volume", "vv_mask_volume",
+    "vv_label_volume", "vv_mask_volume", "vv_distance_volume",
 ]
 # entry points a variant library built from an earlier tree (A/B tools, load_library(path)) may lack
 _NEWER_EXPORTS = ("vv_render_mip", "vv_classify_indices", "vv_render_iso", "vv_slice_slab", "vv_slice_advanced_slab",
                   "vv_volume_histogram", "vv_histogram_indices", "vv_render_projection", "vv_debug_read_layout",
                   "vv_derive_dims", "vv_derive_volume", "vv_stencil_volume", "vv_stencil_taps", "vv_resample_volume", "vv_resample_matrix",
-                  "vv_label_volume", "vv_mask_volume")
+                  "vv_label_volume", "vv_mask_volume", "vv_distance_volume")
 
 _lib = None
 _libs = {}
@@ -240,6 +250,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     if hasattr(lib, "vv_label_volume"):
         lib.vv_label_volume.argtypes = [vp, C.POINTER(vv_label), vp, sz, vp, vp, i, vp]
         lib.vv_mask_volume.argtypes = [vp, C.POINTER(vv_mask), vp, vp, vp, sz, i, vp]
+    if hasattr(lib, "vv_distance_volume"):
+        lib.vv_distance_volume.argtypes = [vp, C.POINTER(vv_distance), vp, vp, sz, i, vp]
     lib.vv_generate_ellipsoids.argtypes = [vp, vp, i, i, i, i, i, vp, vp, vp, vp]
     lib.vv_generate_default_brain.argtypes = [vp, vp, i, i, i, i, vp]
     lib.vv_draw_ellipsoid.argtypes = [vp, vp, i, i, i, i, vp, vp, C.c_uint8, vp]
@@ -972,6 +984,94 @@ class Context:
         if lab == 0:
             raise ValueError(f"seed {tuple(seed)} is background for bins {bins}")
         return self.mask(labels, KEEP_LABEL, label=lab, invert=invert, fill=fill, box=box, out_type=out_type)
+
+    # vv_distance_volume (no reference counterpart)
+    def _distance(self, bins, have_labels, label, invert, spacing, box, within) -> vv_distance:
+        """bins = (bin_lo, bin_hi) or one bin: VV_SEED_BINS; else labels with `label` (VV_SEED_LABEL) or without (VV_SEED_NONZERO).  `within`:
+        None = VV_DIST_SQUARED, an integer r^2 = VV_DIST_WITHIN."""
+        if (bins is None) != bool(have_labels):
+            raise ValueError("give either bins or labels")
+        d = vv_distance()
+        if box is not None:
+            d.box_lo[:] = [int(v) for v in box[0]]
+            d.box_hi[:] = [int(v) for v in box[1]]
+        if bins is not None:
+            d.seed = SEED_BINS
+            d.bin_lo, d.bin_hi = (int(bins), int(bins)) if np.isscalar(bins) else (int(bins[0]), int(bins[1]))
+        else:
+            d.seed, d.label = (SEED_NONZERO, 0) if label is None else (SEED_LABEL, int(label))
+        d.invert = int(bool(invert))
+        d.spacing[:] = [int(v) for v in spacing]
+        d.out, d.within_r2 = (DIST_SQUARED, 0) if within is None else (DIST_WITHIN, int(within))
+        return d
+
+    def distance(self, bins=None, labels=None, label=None, invert=False, spacing=(1, 1, 1), box=None, within=None, prefill=None) -> np.ndarray:
+        """vv_distance_volume into a host array [bz, by, bx] uint32: the squared distance to the nearest seed (DISTANCE_NONE everywhere without
+        one), or with `within` = r^2 the 0 / 1 set of the voxels at most that far.  Seeds: the voxels in `bins`, or those of host `labels`
+        [bz, by, bx] that equal `label` (label None: that are not 0); `invert`: the others.  `prefill`: the byte the output holds before the call."""
+        d = self._distance(bins, labels is not None, label, invert, spacing, box, within)
+        shape = self._out_dims(d)[::-1]
+        if labels is not None:
+            labels = np.ascontiguousarray(labels, np.uint32)
+            if labels.shape != tuple(shape):
+                raise ValueError(f"labels have shape {labels.shape}, the box has {tuple(shape)}")
+        out = np.empty(shape, np.uint32)
+        if prefill is not None:
+            out.view(np.uint8)[...] = prefill
+        self._chk(self.lib.vv_distance_volume(self.h, C.byref(d), labels.ctypes.data if labels is not None else None,
+                                              out.ctypes.data if out.size else None, out.nbytes, 0, None))
+        return out
+
+    def distance_device(self, out_ptr: int, capacity: int, bins=None, label=None, invert=False, spacing=(1, 1, 1), box=None, within=None,
+                        labels_ptr: int = 0, stream: int = 0):
+        """vv_distance_volume on device buffers (4-byte aligned; labels_ptr may be out_ptr itself), enqueued on `stream`; returns the box's
+        (bx, by, bz)."""
+        d = self._distance(bins, bool(labels_ptr), label, invert, spacing, box, within)
+        self._chk(self.lib.vv_distance_volume(self.h, C.byref(d), labels_ptr or None, out_ptr or None, int(capacity), 1, stream or None))
+        return self._out_dims(d)
+
+    def morphology(self, op, radius, bins=None, labels=None, label=None, spacing=(1, 1, 1), box=None) -> np.ndarray:
+        """The set S of distance()'s seeds dilated, eroded, opened or closed (MORPH_*) with a ball of `radius` (in the units of `spacing`), as a
+        0 / 1 uint32 array [bz, by, bx] that Context.mask(..., KEEP_FOREGROUND) takes as labels.  A voxel belongs to the ball iff its squared
+        distance is at most r2 = floor(radius^2), formed in binary64.  dilate(S) = the voxels within r2 of S; erode(S) = the complement of the
+        voxels within r2 of S's complement; open = dilate(erode), close = erode(dilate).  The box is the world: nothing lies outside it, so an
+        erosion does not eat in from its faces.  Every step is a vv_distance_volume call in place on one device buffer of the call's own (a
+        complement is taken by the next step's `invert`; a last one by a call with r2 = 0); only the result leaves the device."""
+        if op not in (MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE):
+            raise ValueError("op must be MORPH_DILATE, MORPH_ERODE, MORPH_OPEN or MORPH_CLOSE")
+        radius = float(radius)
+        if not (radius >= 0.0 and np.isfinite(radius)):
+            raise ValueError("radius must be finite and not negative")
+        r2 = min(int(np.floor(radius * radius)), 0xFFFFFFFE)
+        probe = self._distance(bins, labels is not None, label, False, spacing, box, r2)
+        shape = self._out_dims(probe)[::-1]
+        out = np.empty(shape, np.uint32)
+        if labels is not None:
+            labels = np.ascontiguousarray(labels, np.uint32)
+            if labels.shape != tuple(shape):
+                raise ValueError(f"labels have shape {labels.shape}, the box has {tuple(shape)}")
+        vp, lib = C.c_void_p, self.lib
+        lib.hipMalloc.argtypes, lib.hipFree.argtypes, lib.hipMemcpy.argtypes = [C.POINTER(vp), C.c_size_t], [vp], [vp, vp, C.c_size_t, C.c_int]
+        buf = vp()
+        if lib.hipMalloc(C.byref(buf), max(out.nbytes, 4)) != 0 or not buf.value:
+            raise VolvizError(-4, "morphology: no device memory for the working buffer")
+        try:
+            p = buf.value
+            if labels is not None and lib.hipMemcpy(p, labels.ctypes.data, labels.nbytes, 1) != 0:
+                raise VolvizError(-3, "morphology: the upload of the labels failed")
+            src = dict(bins=bins, label=label, labels_ptr=p if labels is not None else 0)
+            again = dict(labels_ptr=p, invert=True)                 # the complement of what the buffer holds
+            first_invert = op in (MORPH_ERODE, MORPH_OPEN)
+            self.distance_device(p, out.nbytes, invert=first_invert, spacing=spacing, box=box, within=r2, **src)
+            if op in (MORPH_OPEN, MORPH_CLOSE):
+                self.distance_device(p, out.nbytes, spacing=spacing, box=box, within=r2, **again)
+            if op in (MORPH_ERODE, MORPH_CLOSE):
+                self.distance_device(p, out.nbytes, spacing=spacing, box=box, within=0, **again)
+            if lib.hipMemcpy(out.ctypes.data, p, out.nbytes, 2) != 0:
+                raise VolvizError(-3, "morphology: the download of the result failed")
+        finally:
+            lib.hipFree(buf)
+        return out
 
     # VolumeGenerator::drawEllipsoid x n / drawDefaultBrain (volumegenerator.cpp:31-119)
     def generate_ellipsoids(self, nx: int, ny: int, nz: int, centers, axes, colors) -> np.ndarray:
