@@ -843,6 +843,24 @@ int                vv_debug_read_layout(vv_context *ctx, int layout, unsigned lo
 int                vv_debug_screen_rect(int width, int height, const struct camera_params *cam, const vv_ray_source *rays, double out[4]);
 int                vv_debug_counters(vv_context *ctx, unsigned long long out[16]);  /* developer statistics of the last instrumented frame: [0] executed samples,
                                                                                      * [1] lane slots spent, [2] / [3] waves that sampled the bricked / a pair copy */
+/* The radius pre-pass of unshaded frames (vv_render without Phong shading, vv_render_mip, vv_render_iso, vv_render_projection).  Its results -- one
+ * radius per 14 x 14 pixel slab and, where the launch policy asks for one, the tile order table -- are a pure function of the arguments it is launched
+ * with: the frame's parameters (camera, frame size, steps, slice plane, shard, row range, ...), the screen rectangle, the tile grid, the two buffers,
+ * the stream and the device.  The context keeps those arguments as bytes.  A frame with an analytic ray source whose arguments are byte-identical to
+ * those of the last pre-pass launches none: a host that keeps the view and changes the transfer function, or redraws on a timer, pays for the march
+ * alone.  Frames with an image ray source always launch (the images may change under the same pointers), and so does the first frame after a volume
+ * load, vv_reread_env, a failed frame, a frame on another stream, and a frame that made the context's radius / order buffers grow.  Phong frames have
+ * no such pre-pass and neither use nor disturb it.  The (0,0,0,0) pixels beside the volume's screen rectangle of a composite unshaded frame are
+ * written by blocks appended to the march launch, which fill the slots its last marching blocks leave empty.  No pixel depends on either.
+ * The reuse relies on the stream's order: the earlier pre-pass has run, on that stream, before the later march.  A frame issued while its stream
+ * is being captured into a graph therefore always records its own pre-pass and leaves nothing to reuse; a host that REPLAYS captured frames between
+ * live ones (a replay rewrites the radii at a time the library does not see), or that destroys a stream and goes on with a new one, calls
+ * vv_reread_env in between or runs with VV_RAD_REUSE=0.
+ *   VV_RAD_REUSE=0   the pre-pass is launched on every frame
+ *   VV_TAIL_FILL=0   the pre-pass writes those pixels, as it does for frames in which nothing marches; it then runs on every frame that has any
+ * out = { pre-passes launched since the context was created, frames that reused the last one's results, whether the last frame did (0 / 1),
+ *         the fill blocks of the last frame's march launch }  (developer aid; tests/test_prepass.py) */
+int                vv_debug_prepass_state(vv_context *ctx, int out[4]);
 /* The VV_* developer knobs of the environment are read when a context is created and at every volume load, never
  * per frame; this reads them again (tests that flip a knob between two frames of one volume). */
 int                vv_reread_env(vv_context *ctx);

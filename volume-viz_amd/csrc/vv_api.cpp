@@ -27,6 +27,8 @@ struct vv_knobs {
     int tile_log2w = -1, xcd_band = -1, unroll = -1, lds_reserve = -1, lds_reserve_phong = -1;
     int bricked = -1, zpair = -1, zfast = -1, force_big = 0;
     int block_w = -1, tail = -1, rect = -1, lpt = -1, lpt_run = -1, phong_bricks = -1;
+    int rad_reuse = -1;                     // VV_RAD_REUSE=0: the radius pre-pass is launched on every frame (issue_prepass)
+    int tail_fill = -1;                     // VV_TAIL_FILL=0: the zeros beside the rectangle stay with rad_kernel (no fill blocks in the march launch)
     int hist_blocks = -1;                   // VV_HIST_BLOCKS: cap on hist_kernel's grid (tests drive its grid-stride loop with it)
     int derive_blocks = -1;                 // VV_DERIVE_BLOCKS: the same for derive_kernel
     int stencil_blocks = -1;                // VV_STENCIL_BLOCKS: the same for the stencil kernels (their loop over (tile, z segment) items)
@@ -48,6 +50,7 @@ struct vv_knobs {
         block_w = geti("VV_BLOCK_W", -1); tail = geti("VV_TAIL", -1);
         zfast = geti("VV_ZFAST", -1); force_big = getenv("VV_FORCE_BIG") != nullptr;
         rect = geti("VV_RECT", -1); lpt = geti("VV_LPT", -1); lpt_run = geti("VV_LPT_RUN", -1); phong_bricks = geti("VV_PHONG_BRICKS", -1);
+        rad_reuse = geti("VV_RAD_REUSE", -1); tail_fill = geti("VV_TAIL_FILL", -1);
         hist_blocks = geti("VV_HIST_BLOCKS", -1); derive_blocks = geti("VV_DERIVE_BLOCKS", -1);
         stencil_blocks = geti("VV_STENCIL_BLOCKS", -1); resample_blocks = geti("VV_RESAMPLE_BLOCKS", -1);
         label_blocks = geti("VV_LABEL_BLOCKS", -1); label_phases = geti("VV_LABEL_PHASES", -1);
@@ -87,6 +90,16 @@ enum {
 };
 struct scratch_buf { void *p = nullptr; size_t cap = 0; };
 
+// Everything the last radius pre-pass of an unshaded frame was launched with (issue_prepass): the radii in SC_RAD and the order table in SC_ORDER are a pure
+// function of it.  Compared as bytes: zeroed before it is filled, so the padding compares equal.
+struct prepass_key {
+    FrameParams P; PixelRect rect; StripMap strips;
+    int want_order;                         // a table was asked for (MarchArgs::order_out)
+    float *rad; uint32_t *order;            // SC_RAD / SC_ORDER as the launch saw them ...
+    unsigned long long gen;                 // ... and the allocation generation of the two (ensure may hand back the same address with other contents)
+    hipStream_t stream; int device;
+};
+
 struct vv_context {
     int device = 0;
     vv_knobs knobs;
@@ -113,6 +126,10 @@ struct vv_context {
     bool view_key_valid = false, view_est_ok = false; float view_side[3] = {0, 0, 0}, view_px_cube = 0.f;
     std::vector<uint8_t> row_buf;
     int last_launch[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // vv_debug_last_launch
+    // the radius pre-pass of unshaded frames (issue_prepass): what SC_RAD / SC_ORDER hold, and vv_debug_prepass_state's counts
+    prepass_key prepass; bool prepass_valid = false;
+    unsigned long long prepass_gen = 0;              // bumped whenever SC_RAD or SC_ORDER is allocated anew or freed
+    int prepass_launched = 0, prepass_reused = 0, last_reused = 0, last_fill_blocks = 0;
     unsigned long long *d_counter = nullptr;
     unsigned long long *d_hist = nullptr;       // histogram calls: the accumulator (kHistAccWords), then a vv_histogram for host-output calls
     int n_cu = 0;                               // compute units of the device (hist_kernel's grid)
@@ -141,7 +158,8 @@ static const size_t kStageBytes = 64u << 20;      // streamed upload: pinned / d
 
 static int fail(vv_context *c, int code, const std::string &msg)
 {
-    if (c) c->err = msg; else g_err = msg;
+    // (a failed call of the context, a HIP error in a frame among them: what SC_RAD / SC_ORDER hold is no longer vouched for, issue_prepass)
+    if (c) { c->err = msg; c->prepass_valid = false; } else g_err = msg;
     return code;
 }
 #define HIPCHK(c, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) \
@@ -164,6 +182,7 @@ static void drop_copies(vv_context *c)
     }
     c->builds_in_render = 0;
     c->view_key_valid = false;             // (a new volume: the launch-policy estimate taken from first-pass images is re-taken)
+    c->prepass_valid = false;              // (and the next unshaded frame computes its radii)
 }
 
 static size_t voxel_bytes(int vtype) { return vtype == VV_VOXEL_F32 ? 4 : 1; }
@@ -201,6 +220,7 @@ static int alloc_volume(vv_context *c, int vtype, int nx, int ny, int nz, hipStr
     HIPCHK(c, hipMalloc(&c->d_vol, bytes + pad));
     HIPCHK(c, hipMemsetAsync((char *)c->d_vol + bytes, 0, pad, st));
     c->vol_bytes = bytes; c->vtype = vtype; c->nx = nx; c->ny = ny; c->nz = nz;
+    c->prepass_valid = false;
     c->row_pitch = (size_t)nx * vsz; c->slice_pitch = c->row_pitch * ny; c->alloc_bytes = bytes + pad;
     return VV_OK;
 }
@@ -209,6 +229,7 @@ static int ensure(vv_context *c, int id, size_t need)
 {
     scratch_buf &s = c->scratch[id];
     if (s.cap >= need && s.p) return VV_OK;
+    if (id == SC_RAD || id == SC_ORDER) { ++c->prepass_gen; c->prepass_valid = false; }      // (the radii / the order table go with their buffer)
     if (s.p) { HIPCHK(c, hipFree(s.p)); s.p = nullptr; s.cap = 0; }
     HIPCHK(c, hipMalloc(&s.p, need));
     s.cap = need;
@@ -579,6 +600,7 @@ int vv_shutdown(vv_context *c)
     if (!c) return VV_OK;
     hipSetDevice(c->device);
     if (c->stream) hipStreamSynchronize(c->stream);
+    c->prepass_valid = false; ++c->prepass_gen;
     (void)release_volume(c);
     if (c->d_tf) hipFree(c->d_tf);
     for (scratch_buf &s : c->scratch)
@@ -687,6 +709,7 @@ int vv_reread_env(vv_context *c)
 {
     if (!c) return VV_ERR_INVALID;
     c->knobs.read();
+    c->prepass_valid = false;
     return VV_OK;
 }
 
@@ -897,6 +920,7 @@ int vv_volume_dims(const vv_context *c, int dims[3], int *vtype)
 static int finalize_layout(vv_context *c, hipStream_t st)
 {
     const vv_knobs &K = c->knobs;
+    c->prepass_valid = false;              // (every volume load ends here)
     if (K.pitch_pad == 0) return VV_OK;
     const size_t pad_bytes = (size_t)K.pitch_pad;
     const size_t dense_row = c->row_pitch;
@@ -1433,16 +1457,57 @@ static int stage_images(vv_context *c, Frame &F, int out_on_device)
     return VV_OK;
 }
 
-// stage 7: the kernels.  Unshaded frames: the rad pre-pass, the fill beside the rectangle (not composite frames: rad_kernel writes theirs), the march.
-static void launch_kernels(Frame &F)
+// The radius pre-pass of an unshaded frame (composite, MIP, isosurface, projection): rad_kernel writes the radii into SC_RAD and, where the frame asked for
+// one, the order table into SC_ORDER -- both a pure function of the launch's arguments.  The context keeps a byte image of the arguments of the last
+// pre-pass (prepass_key: the whole argument block, not the fields the radii happen to depend on -- a spurious miss costs one short launch, a false hit
+// a wrong frame).  A frame whose key is byte-identical launches nothing: the radii and the table stand in the buffers from the earlier launch on the
+// same stream.  Never reused: image ray sources (the images' contents may change under the same pointers) and frames whose pre-pass also writes
+// pixels (`rad_pixels`: the zeros beside the rectangle, when the march launch has no fill blocks for them).  The key is dropped when SC_RAD or
+// SC_ORDER is allocated anew (ensure; the generation counts those, the address alone may come back), by every volume load, by vv_reread_env, by a
+// failed call (fail(): every error return of render_frame passes through it) and with the context.  A frame issued while its stream is being
+// captured into a graph neither reuses nor records: its pre-pass has not run when the call returns, and a replay runs at a time of the caller's
+// choosing.  VV_RAD_REUSE=0: every frame launches.
+static void issue_prepass(vv_context *c, Frame &F)
+{
+    MarchArgs &A = F.A;
+    prepass_key key;
+    memset(&key, 0, sizeof key);
+    key.P = A.P; key.rect = A.rect; key.strips = A.strips; key.want_order = A.order_out != nullptr;
+    key.rad = A.rad_out; key.order = A.order_out; key.gen = c->prepass_gen; key.stream = F.st; key.device = c->device;
+    hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+    const bool live = hipStreamIsCapturing(F.st, &capture) == hipSuccess && capture == hipStreamCaptureStatusNone;
+    if (!live) { (void)hipGetLastError(); c->prepass_valid = false; }       // (a captured pre-pass overwrites SC_RAD whenever the graph is replayed)
+    const bool reusable = live && c->knobs.rad_reuse != 0 && A.P.ray_mode == VV_RAYS_ANALYTIC;
+    if (reusable && !A.rad_pixels && c->prepass_valid && memcmp(&key, &c->prepass, sizeof key) == 0) {
+        ++c->prepass_reused; c->last_reused = 1;
+        return;
+    }
+    launch_rad(A, F.st);
+    ++c->prepass_launched;
+    memcpy(&c->prepass, &key, sizeof key); c->prepass_valid = reusable;
+}
+
+// stage 7: the kernels.  Unshaded frames: the rad pre-pass (unless its results stand from an earlier frame), the fill beside the rectangle (composite
+// frames: fill blocks of the march launch, vv_fill.h, or rad_kernel with VV_TAIL_FILL=0 and where nothing marches), the march.
+static void launch_kernels(vv_context *c, Frame &F)
 {
     MarchArgs &A = F.A;
     hipStream_t st = F.st;
+    c->last_reused = 0; c->last_fill_blocks = 0;
+    A.rad_pixels = A.pixels; A.fill_blocks = 0;
     if (A.phong) {
         if (A.fill_outside) { A.rad_out = nullptr; launch_rad(A, st); }          // the pixels beside the volume's screen rectangle (rad_kernel writes them; no radii here)
         launch_build(F.kind, A, st);
     } else if (A.strips.n_strips > 0) {
-        if (F.W >= 2 && F.H >= 2) launch_rad(A, st);
+        const bool rect_given = A.rect.x1 != INT_MAX || A.rect.y1 != INT_MAX;    // (else rad_kernel has no pixel to write: tiles_under_rect)
+        if (!rect_given) A.rad_pixels = nullptr;
+        else if (F.kind == FRAME_COMPOSITE && c->knobs.tail_fill != 0 && grid_blocks(A.strips) > 0 && (long long)F.W * F.H < (1ll << 31)) {
+            const FrameParams &P = A.P;
+            A.fill_blocks = fill_map(A.fill, F.W, F.H, A.rect.x0, A.rect.x1, A.rect.y0, A.rect.y1, P.rb, P.re, P.band, P.count, P.index);
+            A.rad_pixels = nullptr;
+            c->last_fill_blocks = A.fill_blocks;
+        }
+        if (F.W >= 2 && F.H >= 2) issue_prepass(c, F);
         if (F.kind != FRAME_COMPOSITE && F.rect_limits) launch_fill(A, F.fill_rect, st);
         launch_build(F.kind, A, st);
     }
@@ -1523,7 +1588,7 @@ static int render_frame(vv_context *c, int W, int H, const slice_params *slice, 
         memcpy(c->last_launch, v, sizeof v);
     }
     if (c->time_frames) HIPCHK(c, hipEventRecord(c->ev0, st));
-    launch_kernels(F);
+    launch_kernels(c, F);
     if (c->time_frames) HIPCHK(c, hipEventRecord(c->ev1, st));
     if (A.instr) HIPCHK(c, hipEventRecord(c->ev_count, st));      // frame timing may be off, and the read-back's null-stream copy does not order behind a non-blocking stream
     HIPCHK(c, hipGetLastError());
@@ -1643,6 +1708,15 @@ int vv_debug_screen_rect(int W, int H, const camera_params *cam, const vv_ray_so
     int rc = camera_basis(nullptr, A.P, cam, rays, W, H);
     if (rc) return rc;
     return screen_rect(A, W, H, &out[0], &out[1], &out[2], &out[3]) ? 1 : 0;
+}
+
+// the radius pre-pass (issue_prepass; developer aid, tests): {pre-passes launched since the context was created, frames that reused the last one's
+// results, whether the last frame did, the fill blocks of the last frame's march launch}
+int vv_debug_prepass_state(vv_context *c, int out[4])
+{
+    if (!c || !out) return VV_ERR_INVALID;
+    out[0] = c->prepass_launched; out[1] = c->prepass_reused; out[2] = c->last_reused; out[3] = c->last_fill_blocks;
+    return VV_OK;
 }
 
 // what vv_render chose for its last frame (developer aid, tests): {wave tile log2 width, block log2 width, samples per trip, LDS reserve, layout (0 linear,

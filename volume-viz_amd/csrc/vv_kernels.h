@@ -3,8 +3,11 @@
 #include <hip/hip_runtime.h>
 #include "vv_device.h"
 #include "vv_tiles.h"       // StripMap and the tile grid of the march kernels
+#include "vv_fill.h"        // FillMap and the fill blocks of march_kernel
 
 namespace vv {
+
+static_assert(kFillSlab == kSlab, "vv_fill.h decides row ownership per slab row of vv_device.h (fill_writes restates row_owned)");
 
 // the rectangle of a StripMap / SlabMap launch in pixels: [x0, x1) x [y0, y1).  Every owned pixel outside it is a pixel whose ray misses the volume: rad_kernel writes its 0,
 // and computes no radius for slabs that do not meet the rectangle (march_kernel, which reads them, is not launched there).  No rectangle: x1 = y1 = INT_MAX.
@@ -59,6 +62,9 @@ struct MarchArgs {
     float *rad_out;             // same buffer (written by rad_kernel)
     const float4 *fill_tf;      // fill_outside_kernel: the table whose entry 0 is the RGBA of the pixels beside the rectangle, or null for RGBA 0 (isosurface frames)
     uint32_t *pixels;           // device RGBA8 frame (MIP frames: may be null)
+    uint32_t *rad_pixels;       // rad_kernel: `pixels` where it writes the zeros beside `rect`, null where it has none to write or march_kernel's fill blocks write them
+    FillMap fill;               // march_kernel: the fill blocks behind its marching blocks (vv_fill.h; `first` is the launcher's to set)
+    int fill_blocks;            // how many of them (0: none)
     uint8_t *index;             // MIP frames: device image of the per-pixel maxima, W * H bytes, or null (isosurface frames: of the hits' indices)
     float4 *hit;                // isosurface frames: device image of the hit records (x, y, z, ordinal), W * H * 16 bytes, or null
     IsoParams iso;              // isosurface frames

@@ -96,7 +96,8 @@ __global__ __launch_bounds__(256) void rad_kernel(FrameParams P, float *__restri
     // (bands are whole slab rows) and, when H == 1 (mod 14), the last slab row (pin 10)
     if (!row_owned(P, by * kSlab) && !(P.conflict_y && by == P.nby - 1)) return;
     // Pixels outside the rectangle march_kernel's tiles cover: their rays miss the volume (vv_render: screen_rect), the frame holds 0 there
-    // (kernel.cu:334-338).  This wave writes the ones among the slab's 14 x 14 pixels that the frame owns (not column W-1 / row H-1, not another shard's rows).
+    // (kernel.cu:334-338).  This wave writes the ones among the slab's 14 x 14 pixels that the frame owns (not column W-1 / row H-1, not another shard's rows)
+    // -- unless the march launch's fill blocks do (vv_fill.h) or there is nothing to write: then `pixels` is null.
     const int sx0 = bx * kSlab, sy0 = by * kSlab;
     const bool meets = sx0 < R.x1 && sx0 + kSlab > R.x0 && sy0 < R.y1 && sy0 + kSlab > R.y0;
     const bool inside = sx0 >= R.x0 && sx0 + kSlab <= R.x1 && sy0 >= R.y0 && sy0 + kSlab <= R.y1;
@@ -105,7 +106,7 @@ __global__ __launch_bounds__(256) void rad_kernel(FrameParams P, float *__restri
         for (int q = 0; q < 4; ++q) {
             const int t = lane + 64 * q, tx = t % kSlab, ty = t / kSlab;
             const int x = sx0 + tx, y = sy0 + ty;
-            if (t < kSlab * kSlab && x <= P.W - 2 && y <= P.H - 2 && !(x >= R.x0 && x < R.x1 && y >= R.y0 && y < R.y1)) pixels[(size_t)y * P.W + x] = 0u;
+            if (pixels && t < kSlab * kSlab && x <= P.W - 2 && y <= P.H - 2 && !(x >= R.x0 && x < R.x1 && y >= R.y0 && y < R.y1)) pixels[(size_t)y * P.W + x] = 0u;
         }
     }
     // no radius for a slab none of whose own pixels march_kernel visits (it reads rad[owner_slab(pixel)]); the slabs that own pixel W-2 / H-2
@@ -132,6 +133,15 @@ __global__ __launch_bounds__(256) void rad_kernel(FrameParams P, float *__restri
 // ---------------------------------------------------------------------------
 // helpers
 // ---------------------------------------------------------------------------
+// A fill block of march_kernel (vv_fill.h): 0 to its share of the owned pixels beside the rectangle.  No LDS, no counter, no barrier.
+__device__ __forceinline__ void fill_block(const FillMap &F, int b, uint32_t *__restrict__ pixels)
+{
+#pragma unroll 4
+    for (int k = 0; k < kFillBlockPixels / 256; ++k) {
+        int x, y;
+        if (fill_pixel(F, b, (int)threadIdx.x, k, x, y) && fill_writes(F, x, y)) pixels[(size_t)y * F.W + x] = 0u;
+    }
+}
 __device__ __forceinline__ void stage_tf(float4 *lds_tf, const float4 *__restrict__ tf)
 {
     for (int i = threadIdx.x; i < 256; i += blockDim.x) lds_tf[i] = tf[i];
@@ -158,10 +168,13 @@ __global__ __launch_bounds__(256) void march_kernel(FrameParams P, VolumeView V,
                                                     const float *__restrict__ rad,
                                                     uint32_t *__restrict__ pixels,
                                                     unsigned long long *__restrict__ counter,
-                                                    InstrArgs I, StripMap M)
+                                                    InstrArgs I, StripMap M, FillMap F)
 {
     __shared__ float lds_tf[1024];
 
+    // The blocks behind the marching ones write the zeros beside the volume's screen rectangle (vv_fill.h) and leave: block-uniform, before the
+    // table load and any barrier.  They fill the slots the last marching blocks leave empty; no block waits for another.
+    if (blockIdx.x >= F.first) { fill_block(F, (int)(blockIdx.x - F.first), pixels); return; }
 #ifdef VV_TIMELINE
     const unsigned long long tl0 = wall_clock64();
 #endif
@@ -656,15 +669,18 @@ static void launch_march(const MarchArgs &a, hipStream_t s)
 {
     const unsigned nblocks = grid_blocks(a.strips);                       // the tiles under the volume's screen rectangle (vv_tiles.h)
     if (!nblocks) return;
-    dim3 grid(nblocks);
+    // the fill blocks (vv_fill.h) stand behind the marching blocks: blockIdx % 8 -> XCD, and with it the strip order, stays as it is
+    FillMap fill = a.fill;
+    fill.first = a.fill_blocks > 0 ? nblocks : ~0u;
+    dim3 grid(nblocks + (a.fill_blocks > 0 ? (unsigned)a.fill_blocks : 0u));
     // a.lds_reserve bytes of (unused) dynamic LDS cap the number of resident blocks per CU:
     // fewer waves share the 32 KB L1, which this gather kernel needs more than latency hiding
     if (a.unroll == 3)
         hipLaunchKernelGGL((march_kernel<SLICE, VOXEL, TEX8, GRAY, INSTR, 3>), grid, dim3(256), (size_t)a.lds_reserve, s,
-                           a.P, a.V, a.tf, a.rad, a.pixels, a.counter, a.I, a.strips);
+                           a.P, a.V, a.tf, a.rad, a.pixels, a.counter, a.I, a.strips, fill);
     else
         hipLaunchKernelGGL((march_kernel<SLICE, VOXEL, TEX8, GRAY, INSTR, 2>), grid, dim3(256), (size_t)a.lds_reserve, s,
-                           a.P, a.V, a.tf, a.rad, a.pixels, a.counter, a.I, a.strips);
+                           a.P, a.V, a.tf, a.rad, a.pixels, a.counter, a.I, a.strips, fill);
 }
 template <int SLICE, int VOXEL, bool TEX8, bool INSTR>
 static void launch_phong(const MarchArgs &a, hipStream_t s)
@@ -699,7 +715,7 @@ static void launch_rad_impl(const MarchArgs &a, hipStream_t s)
 {
     // one wave per slab of the frame; waves of slab rows this shard does not own exit at once
     dim3 grid((unsigned)((a.P.nbx * a.P.nby + 3) / 4) + (a.order_out ? 1u : 0u));        // (+ the block that sorts the tiles: StripMap::order)
-    hipLaunchKernelGGL(rad_kernel, grid, dim3(256), 0, s, a.P, a.rad_out, a.rect, a.pixels, a.strips, a.order_out);
+    hipLaunchKernelGGL(rad_kernel, grid, dim3(256), 0, s, a.P, a.rad_out, a.rect, a.rad_pixels, a.strips, a.order_out);
 }
 
 static void launch_raymarch_impl(const MarchArgs &a, hipStream_t s)

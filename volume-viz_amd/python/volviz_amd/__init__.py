@@ -179,13 +179,13 @@ EXPORTS = [
     "vv_render_mip", "vv_classify_indices", "vv_render_iso", "vv_slice_slab", "vv_slice_advanced_slab",
     "vv_volume_histogram", "vv_histogram_indices", "vv_render_projection", "vv_debug_read_layout",
     "vv_derive_dims", "vv_derive_volume", "vv_stencil_volume", "vv_stencil_taps", "vv_resample_volume", "vv_resample_matrix",
-    "vv_label_volume", "vv_mask_volume", "vv_distance_volume",
+    "vv_label_volume", "vv_mask_volume", "vv_distance_volume", "vv_debug_prepass_state",
 ]
 # entry points a variant library built from an earlier tree (A/B tools, load_library(path)) may lack
 _NEWER_EXPORTS = ("vv_render_mip", "vv_classify_indices", "vv_render_iso", "vv_slice_slab", "vv_slice_advanced_slab",
                   "vv_volume_histogram", "vv_histogram_indices", "vv_render_projection", "vv_debug_read_layout",
                   "vv_derive_dims", "vv_derive_volume", "vv_stencil_volume", "vv_stencil_taps", "vv_resample_volume", "vv_resample_matrix",
-                  "vv_label_volume", "vv_mask_volume", "vv_distance_volume")
+                  "vv_label_volume", "vv_mask_volume", "vv_distance_volume", "vv_debug_prepass_state")
 
 _lib = None
 _libs = {}
@@ -276,6 +276,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.vv_cut_plane_drag.argtypes = [vp, vp, vp, i, i, i, i]
     lib.vv_debug_counters.argtypes = [vp, vp]
     lib.vv_debug_last_launch.argtypes = [vp, vp]
+    if hasattr(lib, "vv_debug_prepass_state"):
+        lib.vv_debug_prepass_state.argtypes = [vp, vp]
     if hasattr(lib, "vv_debug_read_layout"):
         lib.vv_debug_read_layout.argtypes = [vp, i, vp, vp, sz]
     lib.vv_set_frame_timing.argtypes = [vp, i]
@@ -633,6 +635,13 @@ class Context:
         self._chk(self.lib.vv_debug_last_launch(self.h, out))
         k = ("tile_log2w", "blk_log2w", "unroll", "lds_reserve", "layout", "view_known", "density_x1000", "phong")     # phong: 0 unshaded, 1 Phong, 2 MIP, 3 isosurface, 4 projection
         return dict(zip(k, list(out)))
+
+    def prepass_state(self) -> tuple:
+        """vv_debug_prepass_state: (radius pre-passes launched since the context was created, frames that reused the last one's results, whether the
+        last frame did, the fill blocks of the last frame's march launch)."""
+        out = (C.c_int * 4)()
+        self._chk(self.lib.vv_debug_prepass_state(self.h, out))
+        return tuple(out)
 
     def read_layout(self, code: int):
         """vv_debug_read_layout: the resident layout `code` (last_launch()["layout"]'s codes) as it lies in HBM: (uint8 array of the whole allocation,
