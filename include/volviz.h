@@ -697,6 +697,74 @@ typedef struct vv_distance {
 int  vv_distance_volume(vv_context *ctx, const vv_distance *d, const uint32_t *labels /* NULL for VV_SEED_BINS */,
                         uint32_t *out, size_t capacity, int on_device, void *stream);
 
+/* ---- region measurements: one table row per region of a label volume, and consecutive labels 1..K (no reference counterpart) ----
+ * vv_region_table measures what vv_label_volume, vv_mask_volume and vv_distance_volume segmented, where it lies, in HBM: every region's voxel count,
+ * bounding box, coordinate moments, intensity range, surface faces and, with `aux` (e.g. the squared distances vv_distance_volume wrote), its thickness;
+ * and it rewrites the sparse canonical labels (1 + least voxel index) as consecutive ones.  i, b, lo, hi are those of vv_label_volume's rule 4.
+ *  1. REGIONS, VV_REGION_LABELS: voxel r is a ROOT iff labels[r] == r + 1.  Voxel i is OWNED by root r iff labels[i] != 0, r = labels[i] - 1 < voxels
+ *     (voxels = b_x b_y b_z) and r is a root.  A voxel with labels[i] != 0 that is not owned is a STRAY.  The rule is total on any caller data, and no
+ *     label ever makes an address unchecked; on what vv_label_volume wrote there are no strays.  K = the number of roots; the RANK of a root is the
+ *     number of roots with a smaller index: rows are in ascending label order.
+ *  2. VV_REGION_NONZERO: all voxels with labels[i] != 0 form one region whose label is 1 + the least such i; K is 1 or 0; there are no strays.  (How a
+ *     VV_DIST_WITHIN or morphology result is measured.)
+ *  3. COMPACT: compact[i] = rank + 1 of the owning root, 0 for background and strays.  Every word is written, whatever max_regions is.  A device
+ *     `compact` may not overlap labels, aux, table or the context's linear volume allocation.
+ *  4. TABLE: row k < min(K, max_regions) describes the region of rank k; rows at and beyond that are not written.  Every field is an integer or a
+ *     bit-for-bit copy of a voxel: exact, and the same from run to run.  label: the region's label.  voxels: its voxel count.  lo, hi: its bounding box
+ *     in VOLUME coordinates (box_lo + the box's coordinate), hi exclusive.  sum: the sums of x, y, z in volume coordinates (centroid = sum / voxels on
+ *     the host).  sum2: the sums of xx, yy, zz, xy, xz, yz.  bin_min, bin_max, bin_sum, bin_sum2: over the classification index of
+ *     vv_volume_histogram's rule 1.  vmin, vmax: as vv_histogram's rule 2 (integer keys compared, NaN excluded, +Inf / -Inf when there is none; u8:
+ *     (float)byte).  faces[a]: the number of voxel faces of the region perpendicular to axis a whose neighbour across the face lies outside the box or
+ *     is not owned by the same root (NONZERO: is 0), both directions counted; surface area = sum_a faces[a] pitch_b pitch_c on the host.  aux_sum,
+ *     aux_max: the sum and the maximum of aux over the region; aux_argmax: the least box index i among the maxima; all three 0 without aux.  reserved: 0.
+ *     OVERFLOW BOUNDS: with every volume coordinate of the box below 2^14 and fewer than 2^32 voxels in the box, sum < 2^46 and sum2 < 2^60: exact.
+ *     (A volume with a longer axis is not refused: its sums are then taken modulo 2^64.)  aux_sum < 2^64 always: fewer than 2^32 words below 2^32.
+ *  5. SUMMARY (optional): regions = K; written = min(K, max_regions); foreground = the number of non-zero labels; stray = the number of strays.
+ *  6. What follows: (a) with labels from vv_label_volume, table[k].voxels == sizes[table[k].label - 1] and summary.regions == vv_label_stats.components.
+ *     (b) The sum of voxels over a complete table is foreground - stray.  (c) Nothing depends on the pitch of the source, on the 64-bit addressing
+ *     build, on the layout copies, on the launch geometry, on how the volume was loaded or on what the outputs held.  (d) No byte outside the box is read
+ *     as data; no byte beyond 4 b_x b_y b_z of compact, sizeof(vv_region) * min(K, max_regions) of table and sizeof(vv_region_summary) of summary is written.
+ *  7. STREAM AND MEMORY (vv_label_volume's rule 8): labels, aux, compact, table and summary are all host pointers or all device pointers (on_device).
+ *     Device labels, aux and compact must be 4-byte aligned, device table and summary 8-byte aligned.  A device call allocates nothing: the chunk
+ *     counters live in scratch the context holds from vv_init on (keep enqueue-only calls of one context on one stream).  The call is five kernel
+ *     launches whatever the data, with no host read-back: `stream` NULL = the context's stream, the call returns when the work is complete; any other
+ *     handle with device buffers only enqueues.  Host buffers are staged through device buffers of the call's own (labels and aux as inputs; a host
+ *     table is uploaded first, so the rows that are not written keep the caller's bytes), released before it returns.  The context's volume, table,
+ *     layout copies and residency state are not touched; vv_last_frame_ms keeps its value.
+ *  8. Errors, in this order.  VV_ERR_INVALID: NULL ctx / d / labels / compact.  VV_ERR_NO_VOLUME: no volume loaded (the box is measured against the
+ *     volume, and the intensity fields read it).  VV_ERR_INVALID, each in turn: a box outside vv_derive's rule 5 or above 2^32 - 2 voxels; a source
+ *     outside its enum; table == NULL with max_regions != 0; compact_capacity (bytes) below 4 b_x b_y b_z; table_capacity (bytes) below
+ *     sizeof(vv_region) * max_regions, formed in 64 bits; a misaligned device pointer; a device compact whose byte range overlaps labels, aux, table or
+ *     the context's linear volume allocation, or a device table that overlaps labels, aux or that allocation.  VV_ERR_NOMEM: a staging buffer could
+ *     not be allocated.  A refused call writes nothing and leaves the context usable.                                                          */
+typedef enum { VV_REGION_LABELS = 0, VV_REGION_NONZERO = 1 } vv_region_source;
+typedef struct vv_regions {
+    int      box_lo[3], box_hi[3];   /* the box the labels were made for (as vv_label) */
+    int      source;                 /* vv_region_source */
+    uint32_t max_regions;            /* rows of `table` */
+} vv_regions;                        /* 32 bytes */
+typedef struct vv_region {
+    uint32_t label;                     /*   0 */
+    uint32_t reserved;                  /*   4: written as 0 */
+    unsigned long long voxels;          /*   8 */
+    int      lo[3], hi[3];              /*  16, 28: volume coordinates, hi exclusive */
+    unsigned long long sum[3];          /*  40: x, y, z */
+    unsigned long long sum2[6];         /*  64: xx, yy, zz, xy, xz, yz */
+    uint32_t bin_min, bin_max;          /* 112, 116 */
+    unsigned long long bin_sum, bin_sum2;   /* 120, 128 */
+    float    vmin, vmax;                /* 136, 140 */
+    unsigned long long faces[3];        /* 144: faces perpendicular to x, y, z */
+    unsigned long long aux_sum;         /* 168 */
+    uint32_t aux_argmax;                /* 176: with aux_max one 8-byte slot (the kernels keep aux_max << 32 | (0xFFFFFFFF - i) there and take its maximum) */
+    uint32_t aux_max;                   /* 180 */
+} vv_region;                            /* 184 bytes, 8-byte aligned */
+typedef struct vv_region_summary {
+    unsigned long long regions, written, foreground, stray;
+} vv_region_summary;                    /* 32 bytes */
+int  vv_region_table(vv_context *ctx, const vv_regions *d, const uint32_t *labels, const uint32_t *aux /* or NULL */,
+                     uint32_t *compact, size_t compact_capacity, vv_region *table /* or NULL with max_regions == 0 */, size_t table_capacity,
+                     vv_region_summary *summary /* or NULL */, int on_device, void *stream);
+
 /* The first pass on its own (firstpass.vert:6, firstpass.frag:4, glwidget.cpp:198-228): the
  * RGBA8 images the reference's two FBOs would hold for this camera -- cube-space entry (front
  * faces) and exit (back faces) positions, UNORM8-rounded, alpha 255 where a face is visible and

@@ -38,6 +38,9 @@ struct vv_knobs {
                                             // launches by difference; the outputs are then unfinished)
     int distance_blocks = -1;               // VV_DISTANCE_BLOCKS: cap on the grids of the distance kernels (tests vary the block order with it)
     int distance_phases = -1;               // VV_DISTANCE_PHASES = 1 / 2: vv_distance_volume stops behind its x / y launch (tools/time_distance.py, as VV_LABEL_PHASES)
+    int region_blocks = -1;                 // VV_REGION_BLOCKS: cap on the grids of the region kernels (tests vary the block order with it)
+    int region_chunks = -1;                 // VV_REGION_CHUNKS: lowers the cap on the chunks of a call (small test boxes reach the long-chunk path with it)
+    int region_phases = -1;                 // VV_REGION_PHASES = 1..4: vv_region_table stops behind that launch (tools/time_regions.py, as VV_LABEL_PHASES)
     // finalize_layout: VV_PITCH_PAD = bytes of row padding (0 or anything that is no number: rows stay dense; not a multiple of 16 in 16..4096: the default),
     // VV_PITCH_FORCE (set: any row length is padded), VV_PITCH_ROWS = extra rows per slice (0..64, anything else: the default)
     int pitch_pad = 32, pitch_rows = -1; bool pitch_force = false;
@@ -55,6 +58,7 @@ struct vv_knobs {
         stencil_blocks = geti("VV_STENCIL_BLOCKS", -1); resample_blocks = geti("VV_RESAMPLE_BLOCKS", -1);
         label_blocks = geti("VV_LABEL_BLOCKS", -1); label_phases = geti("VV_LABEL_PHASES", -1);
         distance_blocks = geti("VV_DISTANCE_BLOCKS", -1); distance_phases = geti("VV_DISTANCE_PHASES", -1);
+        region_blocks = geti("VV_REGION_BLOCKS", -1); region_chunks = geti("VV_REGION_CHUNKS", -1); region_phases = geti("VV_REGION_PHASES", -1);
         const int pad = geti("VV_PITCH_PAD", 32);
         pitch_pad = pad <= 0 ? 0 : ((pad >= 16 && pad <= 4096 && pad % 16 == 0) ? pad : 32);
         pitch_force = getenv("VV_PITCH_FORCE") != nullptr; pitch_rows = geti("VV_PITCH_ROWS", -1);
@@ -86,6 +90,7 @@ enum {
     SC_GEN,         // per-axis tables of the ellipsoid generator
     SC_TF_ARG,      // vv_classify_indices: the caller's table
     SC_LABEL,       // vv_label_volume: the kernels' counters, then the vv_label_stats of a host-output call (kLabelScratchBytes, held from vv_init on)
+    SC_REGION,      // vv_region_table: the header counters, the chunk partials, then the vv_region_summary of a host call (kRegionScratchBytes, held from vv_init on)
     SC_N
 };
 struct scratch_buf { void *p = nullptr; size_t cap = 0; };
@@ -154,6 +159,15 @@ static const size_t kLabelStatsOffset = kLabelCounters * sizeof(unsigned long lo
 static const size_t kLabelScratchBytes = kLabelStatsOffset + sizeof(vv_label_stats);
 static_assert(sizeof(vv_label) == 36 && sizeof(vv_label_stats) == 32 && sizeof(vv_mask) == 48, "vv_label / vv_label_stats / vv_mask layout (include/volviz.h)");
 static_assert(sizeof(vv_distance) == 64, "vv_distance layout (include/volviz.h)");
+// scratch entry SC_REGION: the header counters, the chunk partials, then (8-byte aligned) the vv_region_summary a host call copies back
+static const size_t kRegionPartialsOffset = kRegionHeader * sizeof(unsigned long long);
+static const size_t kRegionSummaryOffset = kRegionPartialsOffset + kRegionMaxChunks * sizeof(uint32_t);
+static const size_t kRegionScratchBytes = kRegionSummaryOffset + sizeof(vv_region_summary);
+static_assert(sizeof(vv_regions) == 32 && sizeof(vv_region) == 184 && alignof(vv_region) == 8 && sizeof(vv_region_summary) == 32, "vv_regions / vv_region / vv_region_summary layout (include/volviz.h)");
+static_assert(offsetof(vv_region, voxels) == 8 && offsetof(vv_region, lo) == 16 && offsetof(vv_region, hi) == 28 && offsetof(vv_region, sum) == 40 &&
+              offsetof(vv_region, sum2) == 64 && offsetof(vv_region, bin_min) == 112 && offsetof(vv_region, bin_sum) == 120 && offsetof(vv_region, vmin) == 136 &&
+              offsetof(vv_region, faces) == 144 && offsetof(vv_region, aux_sum) == 168 && offsetof(vv_region, aux_argmax) == 176 && offsetof(vv_region, aux_max) == 180,
+              "vv_region offsets (include/volviz.h)");
 static const size_t kStageBytes = 64u << 20;      // streamed upload: pinned / device staging buffers (vv_context::pin, d_stage)
 
 static int fail(vv_context *c, int code, const std::string &msg)
@@ -587,7 +601,8 @@ int vv_init(int device, vv_context **out)
         hipMalloc((void **)&c->d_hist, kHistScratchBytes) != hipSuccess ||
         hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess ||
         hipMalloc((void **)&c->d_tf, 256 * sizeof(float4)) != hipSuccess ||
-        ensure(c, SC_LABEL, kLabelScratchBytes) != VV_OK) {               // (held from here on: a label call allocates nothing)
+        ensure(c, SC_LABEL, kLabelScratchBytes) != VV_OK ||               // (held from here on: a label call allocates nothing)
+        ensure(c, SC_REGION, kRegionScratchBytes) != VV_OK) {             // (nor does a region call)
         vv_shutdown(c);                           // (gives back whatever was created before the failure)
         return fail(nullptr, VV_ERR_DEVICE, "vv_init: device set-up failed");
     }
@@ -2278,6 +2293,61 @@ int vv_distance_volume(vv_context *c, const vv_distance *d, const uint32_t *labe
         A.out = (uint32_t *)bb[0].dev;
         A.labels = bins ? nullptr : aliased ? (const uint32_t *)bb[0].dev : (const uint32_t *)bb[1].dev;
         launch_distance(A, c->n_cu, c->knobs.distance_blocks, c->knobs.distance_phases, st);
+        return (int)VV_OK;
+    });
+}
+
+// ---- region measurements (include/volviz.h: vv_region_table) ------------------------
+int vv_region_table(vv_context *c, const vv_regions *d, const uint32_t *labels, const uint32_t *aux, uint32_t *compact, size_t compact_capacity,
+                    vv_region *table, size_t table_capacity, vv_region_summary *summary, int on_device, void *stream)
+{
+    static const char who[] = "vv_region_table";
+    if (!c) return fail(nullptr, VV_ERR_INVALID, "vv_region_table: NULL context");
+    if (!d || !labels || !compact) return fail(c, VV_ERR_INVALID, "vv_region_table: NULL argument");
+    if (!c->d_vol) return fail(c, VV_ERR_NO_VOLUME, "vv_region_table: no volume loaded");
+    // the header's rule 8, in its order
+    int lo[3], hi[3];
+    RegionArgs A;
+    memset(&A, 0, sizeof A);
+    unsigned long long voxels;
+    int rc = label_box(c, who, d->box_lo, d->box_hi, lo, hi, A.b, &voxels);
+    if (rc) return rc;
+    if (d->source != VV_REGION_LABELS && d->source != VV_REGION_NONZERO) return fail(c, VV_ERR_INVALID, "vv_region_table: source must be VV_REGION_LABELS or VV_REGION_NONZERO");
+    if (!table && d->max_regions != 0) return fail(c, VV_ERR_INVALID, "vv_region_table: table is NULL with max_regions != 0");
+    const size_t bytes = (size_t)voxels * sizeof(uint32_t);
+    const unsigned long long tbytes = (unsigned long long)sizeof(vv_region) * d->max_regions;      // (below 2^40)
+    if (compact_capacity < bytes) return fail(c, VV_ERR_INVALID, "vv_region_table: compact capacity is below 4 bytes per voxel of the box");
+    if ((unsigned long long)table_capacity < tbytes) return fail(c, VV_ERR_INVALID, "vv_region_table: table capacity is below sizeof(vv_region) * max_regions");
+    if (on_device) {
+        if ((((uintptr_t)labels | (uintptr_t)aux | (uintptr_t)compact) & 3) != 0) return fail(c, VV_ERR_INVALID, "vv_region_table: device labels, aux and compact must be 4-byte aligned");
+        if ((((uintptr_t)table | (uintptr_t)summary) & 7) != 0) return fail(c, VV_ERR_INVALID, "vv_region_table: a device table and summary must be 8-byte aligned");
+        if (ranges_overlap(compact, bytes, labels, bytes) || ranges_overlap(compact, bytes, aux, bytes) || ranges_overlap(compact, bytes, table, (size_t)tbytes) ||
+            ranges_overlap(compact, bytes, c->d_vol, c->alloc_bytes))
+            return fail(c, VV_ERR_INVALID, "vv_region_table: compact overlaps labels, aux, table or the loaded volume");
+        if (ranges_overlap(table, (size_t)tbytes, labels, bytes) || ranges_overlap(table, (size_t)tbytes, aux, bytes) || ranges_overlap(table, (size_t)tbytes, c->d_vol, c->alloc_bytes))
+            return fail(c, VV_ERR_INVALID, "vv_region_table: table overlaps labels, aux or the loaded volume");
+    }
+    if (!label_source_ok(c, hi) || !c->scratch[SC_REGION].p) return fail(c, VV_ERR_DEVICE, "vv_region_table: volume allocation is not what the kernel expects");
+    A.src0 = (const char *)c->d_vol + voxel_offset(c, lo[0], lo[1], lo[2]);
+    A.row_pitch = c->row_pitch; A.slice_pitch = c->slice_pitch;
+    for (int a = 0; a < 3; ++a) A.lo[a] = lo[a];
+    A.max_regions = d->max_regions; A.src_type = c->vtype; A.source = d->source;
+    char *sc = (char *)c->scratch[SC_REGION].p;
+    A.hdr = (unsigned long long *)sc; A.partials = (uint32_t *)(sc + kRegionPartialsOffset);
+    const bool host = !on_device;
+    // (a host table goes up before it comes down: the rows the kernels do not write keep the caller's bytes)
+    CallBuf b[5] = {
+        {(void *)labels, bytes, host, true, false, 0, nullptr, nullptr},
+        {(void *)aux, aux ? bytes : 0, host, true, false, 0, nullptr, nullptr},
+        {compact, bytes, host, false, true, 0, nullptr, nullptr},
+        {table, table ? (size_t)tbytes : 0, host, true, true, 0, nullptr, nullptr},
+        {summary, summary ? sizeof(vv_region_summary) : 0, host, false, true, 0, sc + kRegionSummaryOffset, nullptr},
+    };
+    return run_out_volumes(c, who, b, 5, stream, [&](CallBuf *bb, hipStream_t st) {
+        A.labels = (const uint32_t *)bb[0].dev; A.aux = aux ? (const uint32_t *)bb[1].dev : nullptr; A.compact = (uint32_t *)bb[2].dev;
+        A.table = d->max_regions ? (vv_region *)bb[3].dev : nullptr; A.summary = (vv_region_summary *)bb[4].dev;
+        HIPCHK(c, hipMemsetAsync(A.hdr, 0, kRegionHeader * sizeof(unsigned long long), st));
+        launch_region(A, c->knobs.region_blocks, c->knobs.region_chunks, c->knobs.region_phases, st);
         return (int)VV_OK;
     });
 }

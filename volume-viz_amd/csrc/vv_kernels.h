@@ -219,6 +219,23 @@ struct DistanceArgs {
 };
 void launch_distance(const DistanceArgs &a, int n_cu, int max_blocks /* <= 0: a block per four rows / per tile of lines */,
                      int phases /* 1, 2: stop behind that launch (timing aid); anything else: all three */, hipStream_t s);
+// region measurements (vv_region.hip).  launch_region: the regions of `labels` (vv_regions of include/volviz.h, checked by the caller) ranked, relabelled
+// 1..K at `compact` and measured into `table` (max_regions rows; null with 0), with `summary` a vv_region_summary.  hdr: kRegionHeader words, all zero
+// before the launch; partials: kRegionMaxChunks words, whatever they hold.  The caller vouches for what launch_mask's caller does, that labels, aux (or
+// null) and compact hold b[0] * b[1] * b[2] words each, compact outside everything else, and that table and summary are 8-byte aligned.  Five launches.
+constexpr int kRegionForeground = 0, kRegionStray = 1, kRegionCount = 2, kRegionFirst = 3, kRegionHeader = 4;
+constexpr int kRegionMaxChunks = 8192;      // the cap on the chunks of a call: the partials of scratch entry SC_REGION
+constexpr int kRegionMinChunk = 1024;       // voxels; tests/test_regions.py names it CHUNK
+struct RegionArgs {
+    const void *src0; const uint32_t *labels, *aux; uint32_t *compact; vv_region *table; vv_region_summary *summary;
+    unsigned long long *hdr; uint32_t *partials;
+    uint64_t row_pitch, slice_pitch;        // of the source, bytes
+    uint32_t b[3]; int32_t lo[3];           // the box's extents and its origin in the volume
+    uint32_t max_regions;
+    int src_type, source;                   // vv_voxel_type, vv_region_source
+};
+void launch_region(const RegionArgs &a, int max_blocks /* <= 0: a block per kRgWaves chunks */, int max_chunks /* <= 0: kRegionMaxChunks */,
+                   int phases /* 1..4: stop behind that launch (timing aid); anything else: all five */, hipStream_t s);
 void launch_first_pass(const FrameParams &P, uint32_t *front, uint32_t *back, hipStream_t s);
 
 size_t generate_scratch_floats(int nx, int ny, int nz, int n);

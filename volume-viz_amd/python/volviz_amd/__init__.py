@@ -43,6 +43,7 @@ DIST_SQUARED, DIST_WITHIN = 0, 1                                 # vv_dist_out
 DISTANCE_MAX_EXTENT = 2048
 DISTANCE_NONE = 0xFFFFFFFF                                       # DIST_SQUARED of a box without a seed
 MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3  # Context.morphology
+REGION_LABELS, REGION_NONZERO = 0, 1                             # vv_region_source
 RAYS_IMAGES, RAYS_ANALYTIC = 0, 1
 TF_ENGINE, TF_HEAD, TF_MRI = 0, 1, 2
 # `stream` arguments: 0/None = the context's own stream, synchronous; STREAM_DEFAULT_ASYNC = the device's default (null)
@@ -129,6 +130,69 @@ class vv_distance(C.Structure):           # 64 bytes
                 ("label", C.c_uint32), ("invert", C.c_int), ("spacing", C.c_int * 3), ("out", C.c_int), ("within_r2", C.c_uint32)]
 
 
+class vv_regions(C.Structure):            # 32 bytes
+    _fields_ = [("box_lo", C.c_int * 3), ("box_hi", C.c_int * 3), ("source", C.c_int), ("max_regions", C.c_uint32)]
+
+
+class vv_region(C.Structure):             # 184 bytes, 8-byte aligned
+    _fields_ = [("label", C.c_uint32), ("reserved", C.c_uint32), ("voxels", C.c_ulonglong), ("lo", C.c_int * 3), ("hi", C.c_int * 3),
+                ("sum", C.c_ulonglong * 3), ("sum2", C.c_ulonglong * 6), ("bin_min", C.c_uint32), ("bin_max", C.c_uint32),
+                ("bin_sum", C.c_ulonglong), ("bin_sum2", C.c_ulonglong), ("vmin", C.c_float), ("vmax", C.c_float),
+                ("faces", C.c_ulonglong * 3), ("aux_sum", C.c_ulonglong), ("aux_argmax", C.c_uint32), ("aux_max", C.c_uint32)]
+
+
+class vv_region_summary(C.Structure):     # 32 bytes
+    _fields_ = [("regions", C.c_ulonglong), ("written", C.c_ulonglong), ("foreground", C.c_ulonglong), ("stray", C.c_ulonglong)]
+
+
+# vv_region as a numpy structured dtype: a table is np.ndarray[max_regions] of it (vmin / vmax: compare them as uint32 patterns)
+REGION_DTYPE = np.dtype({
+    "names": ["label", "reserved", "voxels", "lo", "hi", "sum", "sum2", "bin_min", "bin_max", "bin_sum", "bin_sum2", "vmin", "vmax",
+              "faces", "aux_sum", "aux_argmax", "aux_max"],
+    "formats": ["<u4", "<u4", "<u8", ("<i4", 3), ("<i4", 3), ("<u8", 3), ("<u8", 6), "<u4", "<u4", "<u8", "<u8", "<f4", "<f4",
+                ("<u8", 3), "<u8", "<u4", "<u4"],
+    "offsets": [0, 4, 8, 16, 28, 40, 64, 112, 116, 120, 128, 136, 140, 144, 168, 176, 180],
+    "itemsize": 184})
+assert C.sizeof(vv_regions) == 32 and C.sizeof(vv_region) == 184 and C.alignment(vv_region) == 8 and C.sizeof(vv_region_summary) == 32
+assert all(getattr(vv_region, n).offset == REGION_DTYPE.fields[n][1] for n in REGION_DTYPE.names), "vv_region layout (include/volviz.h)"
+
+
+@dataclass
+class RegionSummary:
+    """vv_region_summary as Python ints."""
+    regions: int
+    written: int
+    foreground: int
+    stray: int
+
+    @staticmethod
+    def from_bytes(raw) -> "RegionSummary":
+        """From the 32 bytes of a vv_region_summary (e.g. read back from a device buffer)."""
+        q = np.frombuffer(bytes(raw), np.uint8, C.sizeof(vv_region_summary)).view(np.uint64)
+        return RegionSummary(int(q[0]), int(q[1]), int(q[2]), int(q[3]))
+
+
+def region_properties(table, spacing=(1.0, 1.0, 1.0)) -> dict:
+    """What a vv_region table says in physical units, in binary64 (host only).  spacing = the voxel pitch (x, y, z).  Per row: voxels, volume,
+    centroid [n, 3] (voxel-centre coordinates times the pitch), surface_area (faces[a] times the product of the other two pitches), covariance
+    [n, 3, 3] of the coordinates (population covariance: E[pq] - E[p]E[q], scaled by the pitches), bbox_lo / bbox_hi [n, 3] in voxels, mean_bin,
+    and inscribed_radius = sqrt(aux_max) (the unit of aux: with the squared distances of vv_distance_volume to the complement, the radius of the
+    largest ball centred on a voxel of the region that stays inside it)."""
+    t = np.atleast_1d(np.asarray(table))
+    sp = np.asarray(spacing, np.float64).reshape(3)
+    n = t["voxels"].astype(np.float64)
+    mean = t["sum"].astype(np.float64) / n[:, None]
+    s2 = t["sum2"].astype(np.float64) / n[:, None]
+    cov = np.empty((len(t), 3, 3), np.float64)
+    for (p, q), k in {(0, 0): 0, (1, 1): 1, (2, 2): 2, (0, 1): 3, (0, 2): 4, (1, 2): 5}.items():
+        cov[:, p, q] = cov[:, q, p] = (s2[:, k] - mean[:, p] * mean[:, q]) * sp[p] * sp[q]
+    faces = t["faces"].astype(np.float64)
+    area = faces[:, 0] * sp[1] * sp[2] + faces[:, 1] * sp[0] * sp[2] + faces[:, 2] * sp[0] * sp[1]
+    return dict(label=t["label"].copy(), voxels=t["voxels"].copy(), volume=n * sp.prod(), centroid=mean * sp, surface_area=area, covariance=cov,
+                bbox_lo=t["lo"].copy(), bbox_hi=t["hi"].copy(), mean_bin=t["bin_sum"].astype(np.float64) / n,
+                inscribed_radius=np.sqrt(t["aux_max"].astype(np.float64)))
+
+
 @dataclass
 class LabelStats:
     """vv_label_stats as Python ints."""
@@ -179,13 +243,13 @@ EXPORTS = [
     "vv_render_mip", "vv_classify_indices", "vv_render_iso", "vv_slice_slab", "vv_slice_advanced_slab",
     "vv_volume_histogram", "vv_histogram_indices", "vv_render_projection", "vv_debug_read_layout",
     "vv_derive_dims", "vv_derive_volume", "vv_stencil_volume", "vv_stencil_taps", "vv_resample_volume", "vv_resample_matrix",
-    "vv_label_volume", "vv_mask_volume", "vv_distance_volume", "vv_debug_prepass_state",
+    "vv_label_volume", "vv_mask_volume", "vv_distance_volume", "vv_debug_prepass_state", "vv_region_table",
 ]
 # entry points a variant library built from an earlier tree (A/B tools, load_library(path)) may lack
 _NEWER_EXPORTS = ("vv_render_mip", "vv_classify_indices", "vv_render_iso", "vv_slice_slab", "vv_slice_advanced_slab",
                   "vv_volume_histogram", "vv_histogram_indices", "vv_render_projection", "vv_debug_read_layout",
                   "vv_derive_dims", "vv_derive_volume", "vv_stencil_volume", "vv_stencil_taps", "vv_resample_volume", "vv_resample_matrix",
-                  "vv_label_volume", "vv_mask_volume", "vv_distance_volume", "vv_debug_prepass_state")
+                  "vv_label_volume", "vv_mask_volume", "vv_distance_volume", "vv_debug_prepass_state", "vv_region_table")
 
 _lib = None
 _libs = {}
@@ -252,6 +316,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib.vv_mask_volume.argtypes = [vp, C.POINTER(vv_mask), vp, vp, vp, sz, i, vp]
     if hasattr(lib, "vv_distance_volume"):
         lib.vv_distance_volume.argtypes = [vp, C.POINTER(vv_distance), vp, vp, sz, i, vp]
+    if hasattr(lib, "vv_region_table"):
+        lib.vv_region_table.argtypes = [vp, C.POINTER(vv_regions), vp, vp, vp, sz, vp, sz, vp, i, vp]
     lib.vv_generate_ellipsoids.argtypes = [vp, vp, i, i, i, i, i, vp, vp, vp, vp]
     lib.vv_generate_default_brain.argtypes = [vp, vp, i, i, i, i, vp]
     lib.vv_draw_ellipsoid.argtypes = [vp, vp, i, i, i, i, vp, vp, C.c_uint8, vp]
@@ -1081,6 +1147,99 @@ class Context:
         finally:
             lib.hipFree(buf)
         return out
+
+    # vv_region_table (no reference counterpart)
+    def _regions(self, source, box, max_regions) -> vv_regions:
+        d = vv_regions()
+        if box is not None:
+            d.box_lo[:] = [int(v) for v in box[0]]
+            d.box_hi[:] = [int(v) for v in box[1]]
+        d.source, d.max_regions = int(source), int(max_regions)
+        return d
+
+    def regions(self, labels: np.ndarray, aux=None, source=REGION_LABELS, box=None, max_regions=None, return_compact=False, return_summary=False,
+                prefill=None):
+        """vv_region_table with host labels (and aux) [bz, by, bx] uint32: the table as a structured array of REGION_DTYPE with max_regions rows
+        (None: as many as the labels have regions, counted here; rows beyond the regions keep `prefill`), then with return_compact the consecutive
+        labels [bz, by, bx] uint32 and with return_summary a RegionSummary (in that order, as a tuple)."""
+        labels = np.ascontiguousarray(labels, np.uint32)
+        if max_regions is None:
+            flat = labels.ravel()
+            max_regions = int((flat == np.arange(1, flat.size + 1, dtype=np.uint64)).sum()) if source == REGION_LABELS else int(flat.any())
+        d = self._regions(source, box, max_regions)
+        shape = self._out_dims(d)[::-1]
+        if labels.shape != tuple(shape):
+            raise ValueError(f"labels have shape {labels.shape}, the box has {tuple(shape)}")
+        if aux is not None:
+            aux = np.ascontiguousarray(aux, np.uint32)
+            if aux.shape != labels.shape:
+                raise ValueError(f"aux has shape {aux.shape}, the box has {labels.shape}")
+        table = np.zeros(int(max_regions), REGION_DTYPE)
+        compact = np.empty(shape, np.uint32)
+        st = vv_region_summary() if return_summary else None
+        if prefill is not None:
+            table.view(np.uint8)[...] = prefill
+            compact.view(np.uint8)[...] = prefill
+            if return_summary:
+                C.memset(C.byref(st), prefill, C.sizeof(st))
+        self._chk(self.lib.vv_region_table(self.h, C.byref(d), labels.ctypes.data, aux.ctypes.data if aux is not None else None,
+                                           compact.ctypes.data, compact.nbytes, table.ctypes.data if max_regions else None, table.nbytes,
+                                           C.addressof(st) if return_summary else None, 0, None))
+        out = [table]
+        if return_compact:
+            out.append(compact)
+        if return_summary:
+            out.append(RegionSummary.from_bytes(st))
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def regions_device(self, labels_ptr: int, compact_ptr: int, compact_capacity: int, table_ptr: int = 0, max_regions: int = 0, aux_ptr: int = 0,
+                       summary_ptr: int = 0, source=REGION_LABELS, box=None, stream: int = 0):
+        """vv_region_table on device buffers (labels, aux, compact: 4 bytes per voxel, 4-byte aligned; table: max_regions rows of 184 bytes and
+        summary: 32 bytes, both 8-byte aligned), enqueued on `stream`; returns the box's (bx, by, bz)."""
+        d = self._regions(source, box, max_regions)
+        self._chk(self.lib.vv_region_table(self.h, C.byref(d), labels_ptr or None, aux_ptr or None, compact_ptr or None, int(compact_capacity),
+                                           table_ptr or None, C.sizeof(vv_region) * int(max_regions), summary_ptr or None, 1, stream or None))
+        return self._out_dims(d)
+
+    def measure(self, bins, connectivity=6, box=None, spacing=(1, 1, 1), thickness=False) -> np.ndarray:
+        """The region table of the components of `bins`, composed on device buffers of the call's own: label(bins, connectivity, box); with
+        `thickness` the squared distance of every foreground voxel to the background (distance of the labels, inverted, with the integer `spacing`)
+        as aux; then regions with one row per component.  Only the label statistics (32 bytes, for the row count) and the table leave the device.
+        region_properties(table, spacing) turns the rows into centroids, areas and radii."""
+        d = self._label(bins, connectivity, box)
+        voxels = int(np.prod(self._out_dims(d)))
+        nbytes = 4 * voxels
+        vp, lib = C.c_void_p, self.lib
+        lib.hipMalloc.argtypes, lib.hipFree.argtypes, lib.hipMemcpy.argtypes = [C.POINTER(vp), C.c_size_t], [vp], [vp, vp, C.c_size_t, C.c_int]
+        bufs = []
+
+        def alloc(n):
+            p = vp()
+            if lib.hipMalloc(C.byref(p), max(int(n), 8)) != 0 or not p.value:
+                raise VolvizError(-4, "measure: no device memory for a working buffer")
+            bufs.append(p)
+            return p.value
+
+        try:
+            lab, comp, st = alloc(nbytes), alloc(nbytes), alloc(32)
+            self.label_device(lab, nbytes, bins, connectivity, box, stats_ptr=st)
+            raw = np.empty(32, np.uint8)
+            if lib.hipMemcpy(raw.ctypes.data, st, 32, 2) != 0:
+                raise VolvizError(-3, "measure: the download of the label statistics failed")
+            k = LabelStats.from_bytes(raw).components
+            aux = 0
+            if thickness:
+                aux = alloc(nbytes)
+                self.distance_device(aux, nbytes, invert=True, spacing=spacing, box=box, labels_ptr=lab)
+            table = np.zeros(k, REGION_DTYPE)
+            tab = alloc(table.nbytes)
+            self.regions_device(lab, comp, nbytes, tab if k else 0, k, aux_ptr=aux, box=box)
+            if k and lib.hipMemcpy(table.ctypes.data, tab, table.nbytes, 2) != 0:
+                raise VolvizError(-3, "measure: the download of the table failed")
+        finally:
+            for p in bufs:
+                lib.hipFree(p)
+        return table
 
     # VolumeGenerator::drawEllipsoid x n / drawDefaultBrain (volumegenerator.cpp:31-119)
     def generate_ellipsoids(self, nx: int, ny: int, nz: int, centers, axes, colors) -> np.ndarray:
