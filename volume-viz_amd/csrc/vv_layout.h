@@ -56,6 +56,26 @@ constexpr vv::MarchBuild kBuild = vv::MB_LINEAR;
 constexpr int kLayout = vv::LAYOUT_LINEAR;
 #endif
 
+// march_kernel, per build: what the trip loop does with sample slots no lane needs (vv_raymarch.hip).  kParkIdle: a lane that has no sample left when a
+// trip begins gathers texel 0, as iso_kernel's lanes do, instead of marching on along its ray with only its blend predicated.  kLeaveEarly: the wave leaves
+// a chunk's trip loop once no lane has a sample left in it.  Both are on in the builds whose bench workloads gained in the A/B against the parent commit
+// (profiles/idle_lanes_ab.txt): big (C3), brick (C3 rotated), zfast (C3 from the side).  They are off, and the kernels instruction for instruction what they
+// were, in the others: the builds for cache-resident volumes pay for the selects (C2 and C1 +5 % with parking; VALU-bound), and no bench workload runs
+// the linear, the brick_cached or the x-pair build.  (The macros exist for A/B builds: make variant VFLAGS="-DVV_PARK_IDLE=0 -DVV_LEAVE_EARLY=1".)
+#if defined(VV_BIG_VOLUME) || (defined(VV_BRICKED) && !defined(VV_BRICKED_CACHED)) || defined(VV_ZFAST)
+#define VV_IDLE_LANES_DEFAULT 1
+#else
+#define VV_IDLE_LANES_DEFAULT 0
+#endif
+#ifndef VV_PARK_IDLE
+#define VV_PARK_IDLE VV_IDLE_LANES_DEFAULT
+#endif
+#ifndef VV_LEAVE_EARLY
+#define VV_LEAVE_EARLY VV_IDLE_LANES_DEFAULT
+#endif
+constexpr bool kParkIdle = VV_PARK_IDLE != 0;
+constexpr bool kLeaveEarly = VV_LEAVE_EARLY != 0;
+
 namespace vv {
 namespace VV_BIG_NS {
 

@@ -270,6 +270,11 @@ __global__ __launch_bounds__(256) void march_kernel(FrameParams P, VolumeView V,
                 tx[u] = __builtin_fmaf(qx - 0.5f, P.inv_scale[0], 0.5f);
                 ty[u] = __builtin_fmaf(qy - 0.5f, P.inv_scale[1], 0.5f);
                 tz[u] = __builtin_fmaf(qz - 0.5f, P.inv_scale[2], 0.5f);
+                if constexpr (kParkIdle) {
+                    // a lane without sample 1 of this chunk (`live` below, as far as it is known before the batch's gathers are issued) is parked: see the trip loop
+                    const bool on = nu[u] >= 1 && !(P.ert_true && ert);
+                    tx[u] = on ? tx[u] : 0.f; ty[u] = on ? ty[u] : 0.f; tz[u] = on ? tz[u] : 0.f;
+                }
                 fetch_any<VOXEL, TEX8>(V, tx[u], ty[u], tz[u], C[u]);
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -310,20 +315,33 @@ __global__ __launch_bounds__(256) void march_kernel(FrameParams P, VolumeView V,
             continue;
         }
 #endif
-        if (INSTR) slots += (unsigned long long)((nmax + U - 1) / U * U) * 64ull;   // lane slots this wave spends
+        if constexpr (!kLeaveEarly) { if (INSTR) slots += (unsigned long long)((nmax + U - 1) / U * U) * 64ull; }   // lane slots this wave spends
         // U samples per trip: their gathers are all issued before the first is consumed.  With
         // the block count per CU capped (lds_reserve) registers are plentiful and the extra
         // loads in flight pay.
         for (int i0 = 1; i0 <= nmax; i0 += U) {
+            // kLeaveEarly (vv_layout.h): no lane has a sample left in this chunk -- every ray of the wave has crossed the threshold or ended: the rays of a wave
+            // end within a few samples of each other -- so the remaining trips up to nmax would gather for nobody.  One wave-uniform test per trip; `slots`
+            // then counts the trips that ran (the same number as the line above when no ray ends early: the test first fails behind nmax).
+            if constexpr (kLeaveEarly) { if (!__any(i0 <= n && !stop)) break; if (INSTR) slots += 64ull * U; }
             float tx[U], ty[U], tz[U];
             typename CornerSel<VOXEL>::type C[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
+                // kParkIdle (vv_layout.h): a lane that has no sample left when the trip begins -- the trip lies past its n, or the lane had crossed the ERT
+                // threshold when the last trip ended -- gathers texel 0 with the others of its kind, as iso_kernel's lanes do, instead of marching on through
+                // slices no sample reads: one line for all of them (three selects per sample).  Both conditions only ever turn on inside a chunk (n is fixed,
+                // stop is only set), so a parked lane stays parked until the next chunk recomputes px, py, pz from dist.  A lane whose samples end inside a
+                // trip still issues the rest of that trip (at most U - 1 samples) along its ray.  Blend, stop / ert, dist and n do not see the parking.
                 px += r.sdir.x; py += r.sdir.y; pz += r.sdir.z;      // :141 (sample i = i increments)
                 // (pos - .5) / scale + .5 as fma(pos - .5, 1/scale, .5)   :136, DESIGN.md pin 3
                 tx[u] = __builtin_fmaf(px - 0.5f, P.inv_scale[0], 0.5f);
                 ty[u] = __builtin_fmaf(py - 0.5f, P.inv_scale[1], 0.5f);
                 tz[u] = __builtin_fmaf(pz - 0.5f, P.inv_scale[2], 0.5f);
+                if constexpr (kParkIdle) {
+                    const bool on = i0 <= n && !stop;
+                    tx[u] = on ? tx[u] : 0.f; ty[u] = on ? ty[u] : 0.f; tz[u] = on ? tz[u] : 0.f;
+                }
                 fetch_any<VOXEL, TEX8>(V, tx[u], ty[u], tz[u], C[u]);
             }
             __builtin_amdgcn_sched_barrier(0);           // all 4U gathers are issued before the first is consumed
