@@ -765,6 +765,82 @@ int  vv_region_table(vv_context *ctx, const vv_regions *d, const uint32_t *label
                      uint32_t *compact, size_t compact_capacity, vv_region *table /* or NULL with max_regions == 0 */, size_t table_capacity,
                      vv_region_summary *summary /* or NULL */, int on_device, void *stream);
 
+/* ---- surface meshes: the surface-nets quads of a level or of a segmentation, indexed, in HBM (no reference counterpart) ----
+ * vv_surface_mesh gives the surface that vv_render_iso shows, or the boundary of what vv_label_volume, vv_distance_volume or vv_region_table
+ * segmented, as geometry: one vertex per grid cell the surface crosses, one quad per grid edge it crosses (naive surface nets).  Vertices are shared
+ * by construction and both outputs have a canonical order, so every output word, floats included, is a property of the input alone.  b, lo, hi and i
+ * are those of vv_label_volume's rule 4.
+ *  1. FIELD: every voxel of the box has an integer g in 0..255, the call a level in 1..255; a voxel is INSIDE iff g >= level.  VV_MESH_INDEX: g is the
+ *     classification index of vv_volume_histogram's rule 1 (the byte of a u8 voxel; a NaN gives 0, +Inf 255), level the descriptor's.  VV_MESH_BINS:
+ *     g = 1 iff bin_lo <= bin <= bin_hi, else 0.  VV_MESH_LABEL: g = (labels[i] == label).  VV_MESH_NONZERO: g = (labels[i] != 0).  The three binary
+ *     sources have level 1 and ignore the descriptor's.  `labels` is what vv_label_volume, vv_distance_volume (VV_DIST_WITHIN) or vv_region_table
+ *     (compact) wrote for the box; NULL for the first two sources.
+ *  2. BOX AND CAP: voxels outside the box do not exist.  cap = 1 surrounds the box with one layer of virtual voxels with g = 0, which are never loaded
+ *     from anywhere: the surface closes at the box's faces.  cap = 0 leaves it open there.  The SITE grid has extents m_a = b_a - 1 + 2 cap, which may
+ *     be 0 (vv_mesh_dims); site s = (s_x, s_y, s_z) has the number j = (s_z m_y + s_y) m_x + s_x and is the cell whose eight corner voxels are the box
+ *     voxels s - cap + (dx, dy, dz), d in {0, 1}^3.
+ *  3. EDGES of a cell: e = 4 a + db + 2 dc for the axis a in (x, y, z) = (0, 1, 2) with (a, b, c) cyclic: the edge along a from corner p (offset 0 on
+ *     a, db on b, dc on c) to corner q = p + e_a.  It is ACTIVE iff exactly one of p, q is inside.  Its crossing lies at
+ *     t = (float)(2 level - 1 - 2 g_p) / (float)(2 (g_q - g_p)) from p: one IEEE binary32 division of two exactly represented integers of equal sign.
+ *     0 < t < 1 always, t = 0.5 for the binary sources: the surface is at level - 1/2, no crossing sits on a voxel.
+ *  4. VERTICES: a site is ACTIVE iff its corners are not all inside and not all outside (iff it has an active edge).  The active sites in ascending j
+ *     are the vertices 0..V-1.  S_k = the binary32 sum over the active edges, in the order e = 0..11, of the crossing's offset on axis k (t on the
+ *     edge's own axis, else its db or dc as 0.0f / 1.0f); n = the number of active edges; the coordinate is (float)(lo_k + s_k - cap) + S_k / (float)n
+ *     (one division, one addition; no expression holds a multiplication), in volume voxel coordinates.  vv_mesh_vertex: x, y, z, site = j.  The
+ *     optional vv_mesh_normal at the same rank: g[k] = the sum of g over the four corners at offset 0 on axis k minus the sum over the four at offset
+ *     1 (an exact integer, unnormalised, pointing out of the inside); edges = the 12-bit mask of the active edges.
+ *  5. INDEX: index[j] = vertex number + 1 at active sites, 0 elsewhere.  Every word (4 m_x m_y m_z bytes) is written whatever the maxima are.  index
+ *     == NULL is allowed only with max_vertices == 0 && max_quads == 0: a COUNT-ONLY call, which writes the summary alone.
+ *  6. QUADS: for each axis a, site s OWNS the edge along a that ends at its corner (1, 1, 1).  The owned edge EMITS iff it is active and s_b + 1 < m_b
+ *     and s_c + 1 < m_c (the four sites around it exist; with cap = 1 every active edge of the padded grid emits exactly once).  The quads in
+ *     ascending (j, a) are the quads 0..Q-1.  With c0 = s, c1 = s + e_b, c2 = s + e_b + e_c, c3 = s + e_c the record is the vertex numbers of
+ *     (c0, c1, c2, c3) if the edge's lower end p is inside, else of (c0, c3, c2, c1): four uint32, 0-based, counter-clockwise seen from outside.
+ *  7. CAPACITIES: the vertex and normal records of rank < max_vertices and the quad records of rank < max_quads are written, nothing beyond them
+ *     (`normals` holds as many records as `vertices`).  A written quad may name a vertex of rank >= max_vertices.  vv_mesh_summary (optional):
+ *     vertices = V, quads = Q, written_vertices = min(V, max_vertices), written_quads = min(Q, max_quads).  Intended use: a count-only call, an
+ *     allocation, the full call.
+ *  8. What follows: (a) with cap = 1 every directed edge (u, v) of the quads occurs as often as (v, u): the mesh is closed and consistently oriented;
+ *     no undirected edge is used more than 4 times.  (b) With cap = 1 and a binary source, Q = the number of voxel faces between an inside voxel and
+ *     an outside or non-existent one (VV_MESH_NONZERO: faces[0] + faces[1] + faces[2] of vv_region_table's VV_REGION_NONZERO row).  (c) The cap = 0
+ *     mesh is the sub-mesh of the cap = 1 mesh on the sites whose eight corners are real, with the same coordinates.  (d) A box entirely inside gives
+ *     V = prod(b_a + 1) - prod(b_a - 1), Q = 2 (b_x b_y + b_y b_z + b_x b_z) with cap = 1 and nothing with cap = 0.  (e) Nothing depends on the pitch,
+ *     the 64-bit addressing build, the layout copies, the launch geometry, the load path or what the outputs held.  (f) No byte outside the box is
+ *     read as data.
+ *  9. LIMITS: the box holds at most 2^32 - 2 voxels, the site grid at most 2^32 - 2 sites; quad ranks and the summary are formed in 64 bits.
+ * 10. STREAM AND MEMORY (vv_region_table's rule 7): all buffers are host pointers or all device pointers (on_device).  Device labels and index must be
+ *     4-byte aligned, vertices, normals and quads 16-byte aligned, summary 8-byte aligned.  A device call allocates nothing: the chunk partials live
+ *     in scratch the context holds from vv_init on.  The call is four kernel launches (count, scan, vertices, quads), two for a count-only call,
+ *     whatever the data, with no host read-back.  Host buffers are staged through device buffers of the call's own; the tables go up before they come
+ *     down, so the records that are not written keep the caller's bytes.  The context's volume, table, layout copies and residency state are not
+ *     touched; vv_last_frame_ms keeps its value.
+ * 11. Errors, in this order.  VV_ERR_INVALID: NULL ctx / d.  VV_ERR_NO_VOLUME: no volume loaded.  VV_ERR_INVALID, each in turn: a box outside
+ *     vv_derive's rule 5 or above 2^32 - 2 voxels; more than 2^32 - 2 sites; a source outside its enum; VV_MESH_INDEX with a level outside 1..255;
+ *     VV_MESH_BINS with bins outside 0 <= bin_lo <= bin_hi <= 255; labels == NULL for a labels source or != NULL for the other two; cap not 0 or 1;
+ *     index == NULL with a non-zero maximum; vertices == NULL with max_vertices != 0; quads == NULL with max_quads != 0; a capacity (bytes, formed in
+ *     64 bits: 4 per site of a given index, 16 per record) below what it must hold; a misaligned device pointer; a device output that overlaps
+ *     another buffer of the call or the context's linear volume allocation.  VV_ERR_NOMEM: a staging buffer could not be allocated.  A refused call
+ *     writes nothing and leaves the context usable.                                                                                              */
+typedef enum { VV_MESH_INDEX = 0, VV_MESH_BINS = 1, VV_MESH_LABEL = 2, VV_MESH_NONZERO = 3 } vv_mesh_source;
+typedef struct vv_mesh {
+    int      box_lo[3], box_hi[3];   /* as vv_label */
+    int      source;                 /* vv_mesh_source */
+    int      level;                  /* VV_MESH_INDEX: 1..255 */
+    int      bin_lo, bin_hi;         /* VV_MESH_BINS: vv_label's rule 1 */
+    uint32_t label;                  /* VV_MESH_LABEL */
+    int      cap;                    /* 0 / 1 */
+    uint32_t max_vertices, max_quads;    /* records of `vertices` (and `normals`) / of `quads` */
+} vv_mesh;                           /* 56 bytes */
+typedef struct vv_mesh_vertex { float x, y, z; uint32_t site; } vv_mesh_vertex;      /* 16 bytes */
+typedef struct vv_mesh_normal { int32_t g[3]; uint32_t edges; } vv_mesh_normal;      /* 16 bytes */
+typedef struct vv_mesh_summary {
+    unsigned long long vertices, quads, written_vertices, written_quads;
+} vv_mesh_summary;                   /* 32 bytes */
+int  vv_mesh_dims(const vv_context *ctx, const vv_mesh *d, int dims[3]);   /* host only; m_a = b_a - 1 + 2 cap (the box, the cap) */
+int  vv_surface_mesh(vv_context *ctx, const vv_mesh *d, const uint32_t *labels /* NULL for VV_MESH_INDEX / VV_MESH_BINS */,
+                     uint32_t *index /* or NULL: count only */, size_t index_capacity,
+                     vv_mesh_vertex *vertices, size_t vertices_capacity, vv_mesh_normal *normals /* or NULL */,
+                     uint32_t *quads, size_t quads_capacity, vv_mesh_summary *summary /* or NULL */, int on_device, void *stream);
+
 /* The first pass on its own (firstpass.vert:6, firstpass.frag:4, glwidget.cpp:198-228): the
  * RGBA8 images the reference's two FBOs would hold for this camera -- cube-space entry (front
  * faces) and exit (back faces) positions, UNORM8-rounded, alpha 255 where a face is visible and

@@ -41,6 +41,9 @@ struct vv_knobs {
     int region_blocks = -1;                 // VV_REGION_BLOCKS: cap on the grids of the region kernels (tests vary the block order with it)
     int region_chunks = -1;                 // VV_REGION_CHUNKS: lowers the cap on the chunks of a call (small test boxes reach the long-chunk path with it)
     int region_phases = -1;                 // VV_REGION_PHASES = 1..4: vv_region_table stops behind that launch (tools/time_regions.py, as VV_LABEL_PHASES)
+    int mesh_blocks = -1;                   // VV_MESH_BLOCKS: cap on the grids of the mesh kernels (tests vary the block order with it)
+    int mesh_chunks = -1;                   // VV_MESH_CHUNKS: lowers the cap on the chunks of a call (small test boxes reach the long-chunk path with it)
+    int mesh_phases = -1;                   // VV_MESH_PHASES = 1..3: vv_surface_mesh stops behind that launch (tools/time_mesh.py, as VV_LABEL_PHASES)
     // finalize_layout: VV_PITCH_PAD = bytes of row padding (0 or anything that is no number: rows stay dense; not a multiple of 16 in 16..4096: the default),
     // VV_PITCH_FORCE (set: any row length is padded), VV_PITCH_ROWS = extra rows per slice (0..64, anything else: the default)
     int pitch_pad = 32, pitch_rows = -1; bool pitch_force = false;
@@ -59,6 +62,7 @@ struct vv_knobs {
         label_blocks = geti("VV_LABEL_BLOCKS", -1); label_phases = geti("VV_LABEL_PHASES", -1);
         distance_blocks = geti("VV_DISTANCE_BLOCKS", -1); distance_phases = geti("VV_DISTANCE_PHASES", -1);
         region_blocks = geti("VV_REGION_BLOCKS", -1); region_chunks = geti("VV_REGION_CHUNKS", -1); region_phases = geti("VV_REGION_PHASES", -1);
+        mesh_blocks = geti("VV_MESH_BLOCKS", -1); mesh_chunks = geti("VV_MESH_CHUNKS", -1); mesh_phases = geti("VV_MESH_PHASES", -1);
         const int pad = geti("VV_PITCH_PAD", 32);
         pitch_pad = pad <= 0 ? 0 : ((pad >= 16 && pad <= 4096 && pad % 16 == 0) ? pad : 32);
         pitch_force = getenv("VV_PITCH_FORCE") != nullptr; pitch_rows = geti("VV_PITCH_ROWS", -1);
@@ -91,6 +95,7 @@ enum {
     SC_TF_ARG,      // vv_classify_indices: the caller's table
     SC_LABEL,       // vv_label_volume: the kernels' counters, then the vv_label_stats of a host-output call (kLabelScratchBytes, held from vv_init on)
     SC_REGION,      // vv_region_table: the header counters, the chunk partials, then the vv_region_summary of a host call (kRegionScratchBytes, held from vv_init on)
+    SC_MESH,        // vv_surface_mesh: the header, the chunk partials, then the vv_mesh_summary of a host call (kMeshScratchBytes, held from vv_init on)
     SC_N
 };
 struct scratch_buf { void *p = nullptr; size_t cap = 0; };
@@ -168,6 +173,16 @@ static_assert(offsetof(vv_region, voxels) == 8 && offsetof(vv_region, lo) == 16 
               offsetof(vv_region, sum2) == 64 && offsetof(vv_region, bin_min) == 112 && offsetof(vv_region, bin_sum) == 120 && offsetof(vv_region, vmin) == 136 &&
               offsetof(vv_region, faces) == 144 && offsetof(vv_region, aux_sum) == 168 && offsetof(vv_region, aux_argmax) == 176 && offsetof(vv_region, aux_max) == 180,
               "vv_region offsets (include/volviz.h)");
+// scratch entry SC_MESH: the header (V, Q), the chunk partials, then (8-byte aligned) the vv_mesh_summary a host call copies back
+static const size_t kMeshPartialsOffset = kMeshHeader * sizeof(unsigned long long);
+static const size_t kMeshSummaryOffset = kMeshPartialsOffset + kMeshMaxChunks * sizeof(MeshPartial);
+static const size_t kMeshScratchBytes = kMeshSummaryOffset + sizeof(vv_mesh_summary);
+static_assert(sizeof(vv_mesh) == 56 && sizeof(vv_mesh_vertex) == 16 && sizeof(vv_mesh_normal) == 16 && sizeof(vv_mesh_summary) == 32 && sizeof(MeshPartial) == 16,
+              "vv_mesh / vv_mesh_vertex / vv_mesh_normal / vv_mesh_summary layout (include/volviz.h)");
+static_assert(offsetof(vv_mesh, box_hi) == 12 && offsetof(vv_mesh, source) == 24 && offsetof(vv_mesh, level) == 28 && offsetof(vv_mesh, bin_lo) == 32 &&
+              offsetof(vv_mesh, bin_hi) == 36 && offsetof(vv_mesh, label) == 40 && offsetof(vv_mesh, cap) == 44 && offsetof(vv_mesh, max_vertices) == 48 &&
+              offsetof(vv_mesh, max_quads) == 52 && offsetof(vv_mesh_vertex, site) == 12 && offsetof(vv_mesh_normal, edges) == 12 &&
+              offsetof(vv_mesh_summary, written_vertices) == 16, "vv_mesh offsets (include/volviz.h)");
 static const size_t kStageBytes = 64u << 20;      // streamed upload: pinned / device staging buffers (vv_context::pin, d_stage)
 
 static int fail(vv_context *c, int code, const std::string &msg)
@@ -602,7 +617,8 @@ int vv_init(int device, vv_context **out)
         hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess ||
         hipMalloc((void **)&c->d_tf, 256 * sizeof(float4)) != hipSuccess ||
         ensure(c, SC_LABEL, kLabelScratchBytes) != VV_OK ||               // (held from here on: a label call allocates nothing)
-        ensure(c, SC_REGION, kRegionScratchBytes) != VV_OK) {             // (nor does a region call)
+        ensure(c, SC_REGION, kRegionScratchBytes) != VV_OK ||             // (nor does a region call)
+        ensure(c, SC_MESH, kMeshScratchBytes) != VV_OK) {                 // (nor a mesh call)
         vv_shutdown(c);                           // (gives back whatever was created before the failure)
         return fail(nullptr, VV_ERR_DEVICE, "vv_init: device set-up failed");
     }
@@ -2348,6 +2364,117 @@ int vv_region_table(vv_context *c, const vv_regions *d, const uint32_t *labels, 
         A.table = d->max_regions ? (vv_region *)bb[3].dev : nullptr; A.summary = (vv_region_summary *)bb[4].dev;
         HIPCHK(c, hipMemsetAsync(A.hdr, 0, kRegionHeader * sizeof(unsigned long long), st));
         launch_region(A, c->knobs.region_blocks, c->knobs.region_chunks, c->knobs.region_phases, st);
+        return (int)VV_OK;
+    });
+}
+
+// ---- surface meshes (include/volviz.h: vv_mesh_dims, vv_surface_mesh) ------------------------
+// The checks both calls share, rule 11 up to the site grid: the box (lo, hi, extents b) and the site grid's extents m.  A cap outside 0 / 1 is refused
+// further down (rule 11's order); the grid is measured with it as it stands only where it is 0 or 1.
+static int mesh_box(const vv_context *c, vv_context *err_to, const char *who, const vv_mesh *d, int lo[3], int hi[3], uint32_t b[3], uint32_t m[3])
+{
+    const std::string w(who);
+    if (!c->d_vol) return fail(err_to, VV_ERR_NO_VOLUME, w + ": no volume loaded");
+    const int dims[3] = {c->nx, c->ny, c->nz};
+    const int rc = check_box(err_to, who, d->box_lo, d->box_hi, dims, lo, hi);
+    if (rc) return rc;
+    for (int a = 0; a < 3; ++a) b[a] = (uint32_t)(hi[a] - lo[a]);
+    if ((unsigned long long)b[0] * b[1] * b[2] > 0xFFFFFFFEull) return fail(err_to, VV_ERR_INVALID, w + ": the box may hold at most 2^32 - 2 voxels");
+    const uint32_t pad = d->cap == 1 ? 2u : 0u;
+    for (int a = 0; a < 3; ++a) m[a] = b[a] - 1u + pad;
+    // (each extent is below 2^24 + 2: the product of two fits 64 bits, and the third is applied only to a product below 2^32)
+    const unsigned long long two = (unsigned long long)m[0] * m[1];
+    if (two > 0xFFFFFFFEull || two * m[2] > 0xFFFFFFFEull) return fail(err_to, VV_ERR_INVALID, w + ": the site grid may hold at most 2^32 - 2 sites");
+    return VV_OK;
+}
+
+int vv_mesh_dims(const vv_context *c, const vv_mesh *d, int out_dims[3])
+{
+    if (!c) return fail(nullptr, VV_ERR_INVALID, "vv_mesh_dims: NULL context");
+    vv_context *e = const_cast<vv_context *>(c);                    // (the message alone)
+    if (!d || !out_dims) return fail(e, VV_ERR_INVALID, "vv_mesh_dims: NULL argument");
+    int lo[3], hi[3];
+    uint32_t b[3], m[3];
+    const int rc = mesh_box(c, e, "vv_mesh_dims", d, lo, hi, b, m);
+    if (rc) return rc;
+    if (d->cap != 0 && d->cap != 1) return fail(e, VV_ERR_INVALID, "vv_mesh_dims: cap must be 0 or 1");
+    for (int a = 0; a < 3; ++a) out_dims[a] = (int)m[a];
+    return VV_OK;
+}
+
+int vv_surface_mesh(vv_context *c, const vv_mesh *d, const uint32_t *labels, uint32_t *index, size_t index_capacity,
+                    vv_mesh_vertex *vertices, size_t vertices_capacity, vv_mesh_normal *normals, uint32_t *quads, size_t quads_capacity,
+                    vv_mesh_summary *summary, int on_device, void *stream)
+{
+    static const char who[] = "vv_surface_mesh";
+    if (!c) return fail(nullptr, VV_ERR_INVALID, "vv_surface_mesh: NULL context");
+    if (!d) return fail(c, VV_ERR_INVALID, "vv_surface_mesh: NULL argument");
+    // the header's rule 11, in its order
+    int lo[3], hi[3];
+    MeshArgs A;
+    memset(&A, 0, sizeof A);
+    int rc = mesh_box(c, c, who, d, lo, hi, A.b, A.m);
+    if (rc) return rc;
+    if (d->source != VV_MESH_INDEX && d->source != VV_MESH_BINS && d->source != VV_MESH_LABEL && d->source != VV_MESH_NONZERO)
+        return fail(c, VV_ERR_INVALID, "vv_surface_mesh: source must be VV_MESH_INDEX, VV_MESH_BINS, VV_MESH_LABEL or VV_MESH_NONZERO");
+    if (d->source == VV_MESH_INDEX && !(1 <= d->level && d->level <= 255)) return fail(c, VV_ERR_INVALID, "vv_surface_mesh: level must lie in 1..255");
+    if (d->source == VV_MESH_BINS && !(0 <= d->bin_lo && d->bin_lo <= d->bin_hi && d->bin_hi <= 255))
+        return fail(c, VV_ERR_INVALID, "vv_surface_mesh: bins must satisfy 0 <= bin_lo <= bin_hi <= 255");
+    const bool from_labels = d->source == VV_MESH_LABEL || d->source == VV_MESH_NONZERO;
+    if (from_labels ? labels == nullptr : labels != nullptr)
+        return fail(c, VV_ERR_INVALID, "vv_surface_mesh: labels must be given for the labels sources and NULL for VV_MESH_INDEX and VV_MESH_BINS");
+    if (d->cap != 0 && d->cap != 1) return fail(c, VV_ERR_INVALID, "vv_surface_mesh: cap must be 0 or 1");
+    if (!index && (d->max_vertices != 0 || d->max_quads != 0)) return fail(c, VV_ERR_INVALID, "vv_surface_mesh: index is NULL with a non-zero maximum");
+    if (!vertices && d->max_vertices != 0) return fail(c, VV_ERR_INVALID, "vv_surface_mesh: vertices is NULL with max_vertices != 0");
+    if (!quads && d->max_quads != 0) return fail(c, VV_ERR_INVALID, "vv_surface_mesh: quads is NULL with max_quads != 0");
+    const unsigned long long sites = (unsigned long long)A.m[0] * A.m[1] * A.m[2];                 // (at most 2^32 - 2: mesh_box)
+    const unsigned long long ibytes = index ? 4ull * sites : 0ull, vbytes = 16ull * d->max_vertices, qbytes = 16ull * d->max_quads;
+    if ((unsigned long long)index_capacity < ibytes) return fail(c, VV_ERR_INVALID, "vv_surface_mesh: index capacity is below 4 bytes per site (vv_mesh_dims)");
+    if ((unsigned long long)vertices_capacity < vbytes) return fail(c, VV_ERR_INVALID, "vv_surface_mesh: vertices capacity is below 16 bytes * max_vertices");
+    if ((unsigned long long)quads_capacity < qbytes) return fail(c, VV_ERR_INVALID, "vv_surface_mesh: quads capacity is below 16 bytes * max_quads");
+    const size_t lbytes = from_labels ? (size_t)A.b[0] * A.b[1] * A.b[2] * sizeof(uint32_t) : 0;
+    const size_t nbytes = normals ? (size_t)vbytes : 0;
+    if (on_device) {
+        if ((((uintptr_t)labels | (uintptr_t)index) & 3) != 0) return fail(c, VV_ERR_INVALID, "vv_surface_mesh: device labels and index must be 4-byte aligned");
+        if ((((uintptr_t)vertices | (uintptr_t)normals | (uintptr_t)quads) & 15) != 0)
+            return fail(c, VV_ERR_INVALID, "vv_surface_mesh: device vertices, normals and quads must be 16-byte aligned");
+        if (((uintptr_t)summary & 7) != 0) return fail(c, VV_ERR_INVALID, "vv_surface_mesh: a device summary must be 8-byte aligned");
+        // every output against the input, the volume and the outputs behind it in the list
+        const void *ptr[7] = {index, vertices, normals, quads, summary, labels, c->d_vol};
+        const size_t len[7] = {(size_t)ibytes, vertices ? (size_t)vbytes : 0, nbytes, quads ? (size_t)qbytes : 0, summary ? sizeof(vv_mesh_summary) : 0, lbytes, c->alloc_bytes};
+        static const char *const name[5] = {"index", "vertices", "normals", "quads", "summary"};
+        for (int i = 0; i < 5; ++i)
+            for (int k = i + 1; k < 7; ++k)
+                if (len[i] && len[k] && ranges_overlap(ptr[i], len[i], ptr[k], len[k]))
+                    return fail(c, VV_ERR_INVALID, std::string("vv_surface_mesh: ") + name[i] + " overlaps another buffer of the call or the loaded volume");
+    }
+    // what the kernels may read of [d_vol, d_vol + alloc_bytes): the box's voxels at the two pitches and nothing else (virtual voxels are clamped into
+    // the box before they are addressed); f32 voxels are loaded as aligned words
+    if (!label_source_ok(c, hi) || !c->scratch[SC_MESH].p) return fail(c, VV_ERR_DEVICE, "vv_surface_mesh: volume allocation is not what the kernel expects");
+    A.src0 = (const char *)c->d_vol + voxel_offset(c, lo[0], lo[1], lo[2]);
+    A.row_pitch = c->row_pitch; A.slice_pitch = c->slice_pitch;
+    for (int a = 0; a < 3; ++a) A.lo[a] = lo[a];
+    A.level = d->source == VV_MESH_INDEX ? (uint32_t)d->level : 1u;
+    A.bin_lo = (uint32_t)d->bin_lo; A.bin_hi = (uint32_t)d->bin_hi; A.label = d->label;
+    A.max_vertices = d->max_vertices; A.max_quads = d->max_quads;
+    A.src_type = c->vtype; A.source = d->source; A.cap = d->cap;
+    char *sc = (char *)c->scratch[SC_MESH].p;
+    A.hdr = (unsigned long long *)sc; A.partials = (MeshPartial *)(sc + kMeshPartialsOffset);
+    const bool host = !on_device;
+    // (host tables go up before they come down: the records the kernels do not write keep the caller's bytes)
+    CallBuf b[6] = {
+        {(void *)labels, lbytes, host, true, false, 0, nullptr, nullptr},
+        {index, (size_t)ibytes, host, false, true, 0, nullptr, nullptr},
+        {vertices, vertices ? (size_t)vbytes : 0, host, true, true, 0, nullptr, nullptr},
+        {normals, nbytes, host, true, true, 0, nullptr, nullptr},
+        {quads, quads ? (size_t)qbytes : 0, host, true, true, 0, nullptr, nullptr},
+        {summary, summary ? sizeof(vv_mesh_summary) : 0, host, false, true, 0, sc + kMeshSummaryOffset, nullptr},
+    };
+    return run_out_volumes(c, who, b, 6, stream, [&](CallBuf *bb, hipStream_t st) {
+        A.labels = from_labels ? (const uint32_t *)bb[0].dev : nullptr; A.index = index ? (uint32_t *)bb[1].dev : nullptr;
+        A.vertices = d->max_vertices ? (vv_mesh_vertex *)bb[2].dev : nullptr; A.normals = d->max_vertices && normals ? (vv_mesh_normal *)bb[3].dev : nullptr;
+        A.quads = d->max_quads ? (uint4 *)bb[4].dev : nullptr; A.summary = (vv_mesh_summary *)bb[5].dev;
+        launch_mesh(A, c->knobs.mesh_blocks, c->knobs.mesh_chunks, c->knobs.mesh_phases, st);
         return (int)VV_OK;
     });
 }

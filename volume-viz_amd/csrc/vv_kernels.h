@@ -236,6 +236,27 @@ struct RegionArgs {
 };
 void launch_region(const RegionArgs &a, int max_blocks /* <= 0: a block per kRgWaves chunks */, int max_chunks /* <= 0: kRegionMaxChunks */,
                    int phases /* 1..4: stop behind that launch (timing aid); anything else: all five */, hipStream_t s);
+// surface meshes (vv_mesh.hip).  launch_mesh: the surface-nets mesh of the box of b[0] x b[1] x b[2] voxels whose first voxel is src0 (vv_mesh of
+// include/volviz.h, checked by the caller): `index` (one word per site of the m[0] x m[1] x m[2] grid, m[a] = b[a] - 1 + 2 cap), the vertex and
+// normal records of rank < max_vertices, the quad records of rank < max_quads, with `summary` a vv_mesh_summary.  index == nullptr: a count-only call
+// (both maxima 0), two launches; else four.  hdr: kMeshHeader words and partials: kMeshMaxChunks pairs, whatever they hold.  The caller vouches for what
+// launch_mask's caller does, that the site grid holds at most 2^32 - 2 sites, that `labels` (the labels sources) holds b[0] * b[1] * b[2] words, that
+// index holds a word per site, vertices / normals max_vertices and quads max_quads 16-byte aligned records, all outside each other and the inputs.
+constexpr int kMeshVertices = 0, kMeshQuads = 1, kMeshHeader = 4;
+constexpr int kMeshMaxChunks = 8192;        // the cap on the chunks of a call: the partials of scratch entry SC_MESH
+constexpr int kMeshMinChunk = 1024;         // sites; tests/test_mesh.py names it CHUNK
+struct MeshPartial { unsigned long long vertices, quads; };      // of a chunk (launch 1); of all chunks below it (behind launch 2)
+struct MeshArgs {
+    const void *src0; const uint32_t *labels; uint32_t *index; vv_mesh_vertex *vertices; vv_mesh_normal *normals; uint4 *quads; vv_mesh_summary *summary;
+    unsigned long long *hdr; MeshPartial *partials;
+    uint64_t row_pitch, slice_pitch;        // of the source, bytes
+    uint32_t b[3], m[3]; int32_t lo[3];     // the box's extents, the site grid's, the box's origin in the volume
+    uint32_t level, bin_lo, bin_hi, label;  // level: 1 for the three binary sources
+    uint32_t max_vertices, max_quads;
+    int src_type, source, cap;              // vv_voxel_type, vv_mesh_source, 0 / 1
+};
+void launch_mesh(const MeshArgs &a, int max_blocks /* <= 0: a block per kMeshWaves chunks */, int max_chunks /* <= 0: kMeshMaxChunks */,
+                 int phases /* 1..3: stop behind that launch (timing aid); anything else: all */, hipStream_t s);
 void launch_first_pass(const FrameParams &P, uint32_t *front, uint32_t *back, hipStream_t s);
 
 size_t generate_scratch_floats(int nx, int ny, int nz, int n);

@@ -44,6 +44,7 @@ DISTANCE_MAX_EXTENT = 2048
 DISTANCE_NONE = 0xFFFFFFFF                                       # DIST_SQUARED of a box without a seed
 MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3  # Context.morphology
 REGION_LABELS, REGION_NONZERO = 0, 1                             # vv_region_source
+MESH_INDEX, MESH_BINS, MESH_LABEL, MESH_NONZERO = 0, 1, 2, 3     # vv_mesh_source
 RAYS_IMAGES, RAYS_ANALYTIC = 0, 1
 TF_ENGINE, TF_HEAD, TF_MRI = 0, 1, 2
 # `stream` arguments: 0/None = the context's own stream, synchronous; STREAM_DEFAULT_ASYNC = the device's default (null)
@@ -157,6 +158,94 @@ assert C.sizeof(vv_regions) == 32 and C.sizeof(vv_region) == 184 and C.alignment
 assert all(getattr(vv_region, n).offset == REGION_DTYPE.fields[n][1] for n in REGION_DTYPE.names), "vv_region layout (include/volviz.h)"
 
 
+class vv_mesh(C.Structure):               # 56 bytes
+    _fields_ = [("box_lo", C.c_int * 3), ("box_hi", C.c_int * 3), ("source", C.c_int), ("level", C.c_int), ("bin_lo", C.c_int), ("bin_hi", C.c_int),
+                ("label", C.c_uint32), ("cap", C.c_int), ("max_vertices", C.c_uint32), ("max_quads", C.c_uint32)]
+
+
+class vv_mesh_vertex(C.Structure):        # 16 bytes
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("site", C.c_uint32)]
+
+
+class vv_mesh_normal(C.Structure):        # 16 bytes
+    _fields_ = [("g", C.c_int32 * 3), ("edges", C.c_uint32)]
+
+
+class vv_mesh_summary(C.Structure):       # 32 bytes
+    _fields_ = [("vertices", C.c_ulonglong), ("quads", C.c_ulonglong), ("written_vertices", C.c_ulonglong), ("written_quads", C.c_ulonglong)]
+
+
+# vv_mesh_vertex / vv_mesh_normal as numpy structured dtypes (compare x, y, z as uint32 patterns)
+MESH_VERTEX_DTYPE = np.dtype({"names": ["x", "y", "z", "site"], "formats": ["<f4", "<f4", "<f4", "<u4"], "offsets": [0, 4, 8, 12], "itemsize": 16})
+MESH_NORMAL_DTYPE = np.dtype({"names": ["g", "edges"], "formats": [("<i4", 3), "<u4"], "offsets": [0, 12], "itemsize": 16})
+assert C.sizeof(vv_mesh) == 56 and C.sizeof(vv_mesh_vertex) == 16 and C.sizeof(vv_mesh_normal) == 16 and C.sizeof(vv_mesh_summary) == 32
+assert all(getattr(vv_mesh_vertex, n).offset == MESH_VERTEX_DTYPE.fields[n][1] for n in MESH_VERTEX_DTYPE.names), "vv_mesh_vertex layout (include/volviz.h)"
+assert all(getattr(vv_mesh_normal, n).offset == MESH_NORMAL_DTYPE.fields[n][1] for n in MESH_NORMAL_DTYPE.names), "vv_mesh_normal layout (include/volviz.h)"
+
+
+@dataclass
+class MeshSummary:
+    """vv_mesh_summary as Python ints."""
+    vertices: int
+    quads: int
+    written_vertices: int
+    written_quads: int
+
+    @staticmethod
+    def from_bytes(raw) -> "MeshSummary":
+        """From the 32 bytes of a vv_mesh_summary (e.g. read back from a device buffer)."""
+        q = np.frombuffer(bytes(raw), np.uint8, C.sizeof(vv_mesh_summary)).view(np.uint64)
+        return MeshSummary(int(q[0]), int(q[1]), int(q[2]), int(q[3]))
+
+
+@dataclass
+class Mesh:
+    """What Context.surface returns: vertices float32 [V, 3] in volume voxel coordinates, sites uint32 [V] (the cell each vertex lies in), quads uint32
+    [Q, 4] (0-based, counter-clockwise seen from outside), normals (MESH_NORMAL_DTYPE [V]) or None, index uint32 [m_z, m_y, m_x] or None."""
+    vertices: np.ndarray
+    sites: np.ndarray
+    quads: np.ndarray
+    normals: Optional[np.ndarray] = None
+    index: Optional[np.ndarray] = None
+
+
+def mesh_triangles(quads) -> np.ndarray:
+    """Every quad (a, b, c, d) split along (0, 2) into (a, b, c) and (a, c, d): uint32 [2 Q, 3], same winding (host only)."""
+    q = np.asarray(quads, np.uint32).reshape(-1, 4)
+    return np.stack([q[:, [0, 1, 2]], q[:, [0, 2, 3]]], axis=1).reshape(-1, 3)
+
+
+def mesh_area_volume(mesh, spacing=(1.0, 1.0, 1.0)):
+    """(area, signed volume) of the triangles of mesh_triangles, in binary64, with the voxel pitch `spacing` (x, y, z).  The volume is that of a
+    closed mesh (cap=True) and positive for the library's winding (host only)."""
+    v = np.asarray(mesh.vertices, np.float64).reshape(-1, 3) * np.asarray(spacing, np.float64).reshape(3)
+    t = mesh_triangles(mesh.quads).astype(np.int64)
+    if not len(t):
+        return 0.0, 0.0
+    a, b, c = v[t[:, 0]], v[t[:, 1]], v[t[:, 2]]
+    cross = np.cross(b - a, c - a)
+    return float(np.sqrt((cross * cross).sum(axis=1)).sum() / 2.0), float((a * np.cross(b, c)).sum() / 6.0)
+
+
+def write_obj(path, mesh, spacing=(1.0, 1.0, 1.0)) -> None:
+    """Wavefront OBJ of a Mesh: `v` lines (coordinates times `spacing`), `vn` lines from the normalised integer normals when the mesh has them (a zero
+    normal is written as 0 0 1), `f` lines with the quads, 1-based (host only)."""
+    sp = np.asarray(spacing, np.float64).reshape(3)
+    v = np.asarray(mesh.vertices, np.float64).reshape(-1, 3) * sp
+    with open(path, "w") as f:
+        f.write(f"# {len(v)} vertices, {len(mesh.quads)} quads\n")
+        for x, y, z in v:
+            f.write(f"v {x:.9g} {y:.9g} {z:.9g}\n")
+        if mesh.normals is not None:
+            n = mesh.normals["g"].astype(np.float64) / sp                # (a gradient: it scales with the inverse pitch)
+            length = np.sqrt((n * n).sum(axis=1))
+            n = np.where(length[:, None] > 0, n / np.maximum(length, 1e-300)[:, None], np.array([0.0, 0.0, 1.0]))
+            for x, y, z in n:
+                f.write(f"vn {x:.9g} {y:.9g} {z:.9g}\n")
+        for q in np.asarray(mesh.quads, np.int64).reshape(-1, 4) + 1:
+            f.write("f " + " ".join(f"{k}//{k}" if mesh.normals is not None else f"{k}" for k in q) + "\n")
+
+
 @dataclass
 class RegionSummary:
     """vv_region_summary as Python ints."""
@@ -244,12 +333,14 @@ EXPORTS = [
     "vv_volume_histogram", "vv_histogram_indices", "vv_render_projection", "vv_debug_read_layout",
     "vv_derive_dims", "vv_derive_volume", "vv_stencil_volume", "vv_stencil_taps", "vv_resample_volume", "vv_resample_matrix",
     "vv_label_volume", "vv_mask_volume", "vv_distance_volume", "vv_debug_prepass_state", "vv_region_table",
+    "vv_mesh_dims", "vv_surface_mesh",
 ]
 # entry points a variant library built from an earlier tree (A/B tools, load_library(path)) may lack
 _NEWER_EXPORTS = ("vv_render_mip", "vv_classify_indices", "vv_render_iso", "vv_slice_slab", "vv_slice_advanced_slab",
                   "vv_volume_histogram", "vv_histogram_indices", "vv_render_projection", "vv_debug_read_layout",
                   "vv_derive_dims", "vv_derive_volume", "vv_stencil_volume", "vv_stencil_taps", "vv_resample_volume", "vv_resample_matrix",
-                  "vv_label_volume", "vv_mask_volume", "vv_distance_volume", "vv_debug_prepass_state", "vv_region_table")
+                  "vv_label_volume", "vv_mask_volume", "vv_distance_volume", "vv_debug_prepass_state", "vv_region_table",
+                  "vv_mesh_dims", "vv_surface_mesh")
 
 _lib = None
 _libs = {}
@@ -318,6 +409,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib.vv_distance_volume.argtypes = [vp, C.POINTER(vv_distance), vp, vp, sz, i, vp]
     if hasattr(lib, "vv_region_table"):
         lib.vv_region_table.argtypes = [vp, C.POINTER(vv_regions), vp, vp, vp, sz, vp, sz, vp, i, vp]
+    if hasattr(lib, "vv_surface_mesh"):
+        lib.vv_mesh_dims.argtypes = [vp, C.POINTER(vv_mesh), C.POINTER(i * 3)]
+        lib.vv_surface_mesh.argtypes = [vp, C.POINTER(vv_mesh), vp, vp, sz, vp, sz, vp, vp, sz, vp, i, vp]
     lib.vv_generate_ellipsoids.argtypes = [vp, vp, i, i, i, i, i, vp, vp, vp, vp]
     lib.vv_generate_default_brain.argtypes = [vp, vp, i, i, i, i, vp]
     lib.vv_draw_ellipsoid.argtypes = [vp, vp, i, i, i, i, vp, vp, C.c_uint8, vp]
@@ -1240,6 +1334,73 @@ class Context:
             for p in bufs:
                 lib.hipFree(p)
         return table
+
+    # vv_mesh_dims / vv_surface_mesh (no reference counterpart)
+    def _mesh(self, level, bins, have_labels, label, cap, box, max_vertices=0, max_quads=0) -> vv_mesh:
+        """Exactly one of level (MESH_INDEX), bins = (bin_lo, bin_hi) or one bin (MESH_BINS) and labels, with `label` (MESH_LABEL) or without
+        (MESH_NONZERO)."""
+        if (level is not None) + (bins is not None) + bool(have_labels) != 1:
+            raise ValueError("give exactly one of level, bins and labels")
+        d = vv_mesh()
+        if box is not None:
+            d.box_lo[:] = [int(v) for v in box[0]]
+            d.box_hi[:] = [int(v) for v in box[1]]
+        if level is not None:
+            d.source, d.level = MESH_INDEX, int(level)
+        elif bins is not None:
+            d.source = MESH_BINS
+            d.bin_lo, d.bin_hi = (int(bins), int(bins)) if np.isscalar(bins) else (int(bins[0]), int(bins[1]))
+        else:
+            d.source, d.label = (MESH_NONZERO, 0) if label is None else (MESH_LABEL, int(label))
+        d.cap, d.max_vertices, d.max_quads = int(cap), int(max_vertices), int(max_quads)
+        return d
+
+    def _mesh_dims(self, d: vv_mesh):
+        m = (C.c_int * 3)()
+        self._chk(self.lib.vv_mesh_dims(self.h, C.byref(d), C.byref(m)))
+        return int(m[0]), int(m[1]), int(m[2])
+
+    def mesh_dims(self, cap=True, box=None):
+        """vv_mesh_dims: (mx, my, mz) of the site grid of this box and cap (an extent may be 0)."""
+        return self._mesh_dims(self._mesh(1, None, False, None, cap, box))
+
+    def surface(self, level=None, bins=None, labels=None, label=None, cap=True, box=None, normals=False, return_index=False) -> Mesh:
+        """vv_surface_mesh with host buffers: the surface-nets mesh of the voxels whose classification index is at least `level`, or lies in `bins`, or
+        whose word of host `labels` [bz, by, bx] uint32 equals `label` (label None: is not 0).  cap: close the surface at the box's faces.  A
+        count-only call, then the full call into exactly sized arrays."""
+        if labels is not None:
+            labels = np.ascontiguousarray(labels, np.uint32)
+        d = self._mesh(level, bins, labels is not None, label, cap, box)
+        if labels is not None and labels.shape != tuple(self._out_dims(d)[::-1]):
+            raise ValueError(f"labels have shape {labels.shape}, the box has {tuple(self._out_dims(d)[::-1])}")
+        lp = labels.ctypes.data if labels is not None else None
+        st = vv_mesh_summary()
+        self._chk(self.lib.vv_surface_mesh(self.h, C.byref(d), lp, None, 0, None, 0, None, None, 0, C.addressof(st), 0, None))
+        V, Q = int(st.vertices), int(st.quads)
+        d.max_vertices, d.max_quads = V, Q
+        mx, my, mz = self._mesh_dims(d)
+        words = np.zeros(max(mx * my * mz, 1), np.uint32)                # (an empty site grid still gives the full call an index to name)
+        index = words[:mx * my * mz].reshape(mz, my, mx)
+        vert = np.zeros(V, MESH_VERTEX_DTYPE)
+        norm = np.zeros(V, MESH_NORMAL_DTYPE) if normals else None
+        quads = np.zeros((Q, 4), np.uint32)
+        self._chk(self.lib.vv_surface_mesh(self.h, C.byref(d), lp, words.ctypes.data, index.nbytes, vert.ctypes.data if V else None, vert.nbytes,
+                                           norm.ctypes.data if normals and V else None, quads.ctypes.data if Q else None, quads.nbytes,
+                                           C.addressof(st), 0, None))
+        assert (int(st.vertices), int(st.quads), int(st.written_vertices), int(st.written_quads)) == (V, Q, V, Q)
+        xyz = np.stack([vert["x"], vert["y"], vert["z"]], axis=1) if V else np.zeros((0, 3), np.float32)
+        return Mesh(np.ascontiguousarray(xyz, np.float32), vert["site"].copy(), quads, norm, index if return_index else None)
+
+    def surface_device(self, index_ptr: int, index_capacity: int, vertices_ptr: int = 0, max_vertices: int = 0, quads_ptr: int = 0, max_quads: int = 0,
+                       normals_ptr: int = 0, summary_ptr: int = 0, level=None, bins=None, labels_ptr: int = 0, label=None, cap=True, box=None,
+                       stream: int = 0):
+        """vv_surface_mesh on device buffers (labels, index: 4-byte aligned; vertices, normals, quads: 16-byte records, 16-byte aligned; summary: 32
+        bytes, 8-byte aligned), enqueued on `stream`; index_ptr 0 with both maxima 0: count only.  Returns the site grid's (mx, my, mz)."""
+        d = self._mesh(level, bins, bool(labels_ptr), label, cap, box, max_vertices, max_quads)
+        self._chk(self.lib.vv_surface_mesh(self.h, C.byref(d), labels_ptr or None, index_ptr or None, int(index_capacity), vertices_ptr or None,
+                                           16 * int(max_vertices), normals_ptr or None, quads_ptr or None, 16 * int(max_quads), summary_ptr or None,
+                                           1, stream or None))
+        return self._mesh_dims(d)
 
     # VolumeGenerator::drawEllipsoid x n / drawDefaultBrain (volumegenerator.cpp:31-119)
     def generate_ellipsoids(self, nx: int, ny: int, nz: int, centers, axes, colors) -> np.ndarray:
