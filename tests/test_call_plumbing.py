@@ -9,6 +9,8 @@ arguments a call reports, and what the context says it holds on the device.
   * error precedence: calls with two bad arguments, each of which is rejected on the host before the device is touched, report the
     code and the vv_last_error text recorded below.  The literals were taken from the library as it was before the staging path, the
     slice / slab host path and the volume allocator were unified (one run of this table against that build), not from the code under test.
+    The rows of the label, mask, distance, region-table and mesh calls were taken in the same way from the library as it was before those
+    five calls were given one opening, one buffer-role list and one overlap rule (every row observed on that build, code and text).
   * scratch accounting: vv_device_bytes()[3] counts every scratch buffer of the context.
 """
 import ctypes as C
@@ -314,6 +316,216 @@ ERROR_CASES = [
      "stream_begin: a volume row must be below 16 MiB and each dimension below 2^24"),
     ("vv_load_volume_stream_begin", "u8", (vv.VOXEL_F32, 2 ** 22, 1, 2 ** 24, None), INVALID,
      "stream_begin: a volume row must be below 16 MiB and each dimension below 2^24"),
+]
+
+
+# ---- the label, mask, distance, region-table and mesh calls: each call's refusal order walked from end to end, two adjacent steps violated per row ----
+# Device rows lay their buffers out in the 4096 bytes behind "dev+0"; the box is 4 x 4 x 4 (64 voxels, 256 bytes of words), so the site grid
+# without a cap is 3 x 3 x 3 (108 bytes of index).  Not reachable here: the 2^32 - 2 voxel / site limits and vv_distance_volume's extent
+# above 2048 (no such volume is loaded), the overlap of an output with the loaded volume (no public call tells the allocation's address),
+# and the accepted out == labels alias of vv_distance_volume (it reaches a launch: tests/test_distance.py has it).
+_BOX = ((0, 0, 0), (4, 4, 4))
+_BAD_BOX = ((0, 0, 0), (4, 99, 4))
+_WORDS = 256                                  # bytes of a word-per-voxel array of _BOX
+_DIMS = (C.c_int * 3)()
+_NAN = float("nan")
+
+
+def _desc(cls, box=_BOX, **fields):
+    d = cls()
+    d.box_lo[:], d.box_hi[:] = box
+    for k, v in fields.items():
+        if isinstance(v, tuple):
+            getattr(d, k)[:] = v
+        else:
+            setattr(d, k, v)
+    return C.byref(d)
+
+
+def _label(box=_BOX, bins=(3, 9), connectivity=6):
+    return _desc(vv.vv_label, box, bin_lo=bins[0], bin_hi=bins[1], connectivity=connectivity)
+
+
+def _mask(box=_BOX, out_type=vv.VOXEL_U8, keep=vv.KEEP_FOREGROUND, invert=0, fill=0.0):
+    return _desc(vv.vv_mask, box, out_type=out_type, keep=keep, invert=invert, fill=fill)
+
+
+def _dist(box=_BOX, seed=vv.SEED_NONZERO, bins=(3, 9), invert=0, spacing=(1, 1, 1), out=vv.DIST_SQUARED):
+    return _desc(vv.vv_distance, box, seed=seed, bin_lo=bins[0], bin_hi=bins[1], invert=invert, spacing=spacing, out=out)
+
+
+def _regions(box=_BOX, source=vv.REGION_LABELS, max_regions=2):
+    return _desc(vv.vv_regions, box, source=source, max_regions=max_regions)
+
+
+def _mesh(box=_BOX, source=vv.MESH_NONZERO, level=1, bins=(3, 9), cap=0, max_vertices=4, max_quads=4):
+    return _desc(vv.vv_mesh, box, source=source, level=level, bin_lo=bins[0], bin_hi=bins[1], cap=cap, max_vertices=max_vertices, max_quads=max_quads)
+
+
+_H = _p(_BYTES)                               # a host pointer no refused call reads
+_ROW = C.sizeof(vv.vv_region)
+# device layouts: region table {labels 0, aux 256, compact 512, table 1024 (2 rows), summary 2048}; mesh {labels 0, index 256, vertices 512,
+# normals 640, quads 768 (4 records of 16 bytes each), summary 1024}
+_RL, _RA, _RC, _RT, _RS = "dev+0", "dev+256", "dev+512", "dev+1024", "dev+2048"
+_ML, _MI, _MV, _MN, _MQ, _MS = "dev+0", "dev+256", "dev+512", "dev+640", "dev+768", "dev+1024"
+
+ERROR_CASES += [
+    # vv_label_volume (rule 9): context, d / labels, volume, box, bins, connectivity, capacity, 4-byte alignment, stats alignment, labels / sizes overlap
+    ("vv_label_volume", "null", (None, _H, _WORDS, None, None, 0, None), INVALID, "vv_label_volume: NULL context"),
+    ("vv_label_volume", "fresh", (None, _H, _WORDS, None, None, 0, None), INVALID, "vv_label_volume: NULL argument"),
+    ("vv_label_volume", "fresh", (_label(), None, _WORDS, None, None, 0, None), INVALID, "vv_label_volume: NULL argument"),
+    ("vv_label_volume", "fresh", (_label(box=_BAD_BOX), _H, _WORDS, None, None, 0, None), NO_VOLUME, "vv_label_volume: no volume loaded"),
+    ("vv_label_volume", "u8", (_label(box=_BAD_BOX, bins=(9, 3)), _H, _WORDS, None, None, 0, None), INVALID,
+     "vv_label_volume: the box must satisfy 0 <= lo < hi <= dims on every axis (or be all zeros)"),
+    ("vv_label_volume", "u8", (_label(bins=(9, 3), connectivity=8), _H, _WORDS, None, None, 0, None), INVALID,
+     "vv_label_volume: bins must satisfy 0 <= bin_lo <= bin_hi <= 255"),
+    ("vv_label_volume", "f32", (_label(bins=(0, 256), connectivity=8), _H, _WORDS, None, None, 0, None), INVALID,
+     "vv_label_volume: bins must satisfy 0 <= bin_lo <= bin_hi <= 255"),
+    ("vv_label_volume", "u8", (_label(connectivity=8), _H, _WORDS - 1, None, None, 0, None), INVALID, "vv_label_volume: connectivity must be 6, 18 or 26"),
+    ("vv_label_volume", "u8", (_label(), "dev+1", _WORDS - 1, None, None, 1, None), INVALID, "vv_label_volume: capacity is below 4 bytes per voxel of the box"),
+    ("vv_label_volume", "u8", (_label(), "dev+1", _WORDS, None, "dev+2052", 1, None), INVALID, "vv_label_volume: device labels and sizes must be 4-byte aligned"),
+    ("vv_label_volume", "u8", (_label(), "dev+0", _WORDS, "dev+514", "dev+2052", 1, None), INVALID, "vv_label_volume: device labels and sizes must be 4-byte aligned"),
+    ("vv_label_volume", "u8", (_label(), "dev+0", _WORDS, "dev+128", "dev+2052", 1, None), INVALID, "vv_label_volume: a device stats must be 8-byte aligned"),
+    ("vv_label_volume", "f32", (_label(), "dev+128", _WORDS, "dev+0", "dev+2048", 1, None), INVALID, "vv_label_volume: labels and sizes overlap"),
+    # vv_mask_volume (rule M5): context, m / labels / out, volume, box, out_type, keep, invert, fill, sizes under VV_KEEP_MIN_SIZE, capacity, a device
+    # f32 out's alignment, labels / sizes alignment, out over labels or sizes
+    ("vv_mask_volume", "null", (None, _H, None, _H, 64, 0, None), INVALID, "vv_mask_volume: NULL context"),
+    ("vv_mask_volume", "fresh", (None, _H, None, _H, 64, 0, None), INVALID, "vv_mask_volume: NULL argument"),
+    ("vv_mask_volume", "fresh", (_mask(), None, None, _H, 64, 0, None), INVALID, "vv_mask_volume: NULL argument"),
+    ("vv_mask_volume", "fresh", (_mask(), _H, None, None, 64, 0, None), INVALID, "vv_mask_volume: NULL argument"),
+    ("vv_mask_volume", "fresh", (_mask(box=_BAD_BOX), _H, None, _H, 64, 0, None), NO_VOLUME, "vv_mask_volume: no volume loaded"),
+    ("vv_mask_volume", "u8", (_mask(box=_BAD_BOX, out_type=7), _H, None, _H, 64, 0, None), INVALID,
+     "vv_mask_volume: the box must satisfy 0 <= lo < hi <= dims on every axis (or be all zeros)"),
+    ("vv_mask_volume", "u8", (_mask(out_type=7, keep=9), _H, None, _H, 64, 0, None), INVALID, "vv_mask_volume: out_type must be VV_VOXEL_U8 or VV_VOXEL_F32"),
+    ("vv_mask_volume", "u8", (_mask(keep=9, invert=2), _H, None, _H, 64, 0, None), INVALID,
+     "vv_mask_volume: keep must be VV_KEEP_LABEL, VV_KEEP_FOREGROUND or VV_KEEP_MIN_SIZE"),
+    ("vv_mask_volume", "u8", (_mask(invert=2, fill=_NAN), _H, None, _H, 64, 0, None), INVALID, "vv_mask_volume: invert must be 0 or 1"),
+    ("vv_mask_volume", "u8", (_mask(keep=vv.KEEP_MIN_SIZE, fill=_NAN), _H, None, _H, 64, 0, None), INVALID, "vv_mask_volume: fill must be finite"),
+    ("vv_mask_volume", "u8", (_mask(keep=vv.KEEP_MIN_SIZE), _H, None, _H, 63, 0, None), INVALID, "vv_mask_volume: VV_KEEP_MIN_SIZE needs sizes"),
+    ("vv_mask_volume", "f32", (_mask(out_type=vv.VOXEL_F32), "dev+0", None, "dev+1025", 255, 1, None), INVALID, "vv_mask_volume: capacity is below the output's bytes"),
+    ("vv_mask_volume", "f32", (_mask(out_type=vv.VOXEL_F32), "dev+2", None, "dev+1025", 256, 1, None), INVALID, "vv_mask_volume: a device f32 out must be 4-byte aligned"),
+    ("vv_mask_volume", "u8", (_mask(), "dev+2", None, "dev+3", 64, 1, None), INVALID, "vv_mask_volume: device labels and sizes must be 4-byte aligned"),
+    ("vv_mask_volume", "u8", (_mask(), "dev+0", "dev+514", "dev+3", 64, 1, None), INVALID, "vv_mask_volume: device labels and sizes must be 4-byte aligned"),
+    ("vv_mask_volume", "u8", (_mask(), "dev+0", None, "dev+255", 64, 1, None), INVALID, "vv_mask_volume: out overlaps labels or sizes (the pass is not in place)"),
+    ("vv_mask_volume", "u8", (_mask(), "dev+0", "dev+512", "dev+500", 64, 1, None), INVALID, "vv_mask_volume: out overlaps labels or sizes (the pass is not in place)"),
+    # vv_distance_volume (rule 10): context, d / out, volume, box, seed, bins, labels against the seed, invert, spacing, the squared-distance bound (one
+    # term above 0xFFFF; the sum above 0xFFFFFFFE), out mode, capacity, alignment, out over labels; out == labels meets the alignment check like any pair
+    ("vv_distance_volume", "null", (None, None, _H, _WORDS, 0, None), INVALID, "vv_distance_volume: NULL context"),
+    ("vv_distance_volume", "fresh", (None, None, _H, _WORDS, 0, None), INVALID, "vv_distance_volume: NULL argument"),
+    ("vv_distance_volume", "fresh", (_dist(), _H, None, _WORDS, 0, None), INVALID, "vv_distance_volume: NULL argument"),
+    ("vv_distance_volume", "fresh", (_dist(box=_BAD_BOX), _H, _H, _WORDS, 0, None), NO_VOLUME, "vv_distance_volume: no volume loaded"),
+    ("vv_distance_volume", "u8", (_dist(box=_BAD_BOX, seed=5), _H, _H, _WORDS, 0, None), INVALID,
+     "vv_distance_volume: the box must satisfy 0 <= lo < hi <= dims on every axis (or be all zeros)"),
+    ("vv_distance_volume", "u8", (_dist(seed=5, bins=(9, 3)), _H, _H, _WORDS, 0, None), INVALID,
+     "vv_distance_volume: seed must be VV_SEED_BINS, VV_SEED_LABEL or VV_SEED_NONZERO"),
+    ("vv_distance_volume", "u8", (_dist(seed=vv.SEED_BINS, bins=(-1, 3)), _H, _H, _WORDS, 0, None), INVALID,
+     "vv_distance_volume: bins must satisfy 0 <= bin_lo <= bin_hi <= 255"),
+    ("vv_distance_volume", "u8", (_dist(seed=vv.SEED_BINS, invert=2), _H, _H, _WORDS, 0, None), INVALID,
+     "vv_distance_volume: labels must be NULL for VV_SEED_BINS and given for the labels sources"),
+    ("vv_distance_volume", "f32", (_dist(seed=vv.SEED_LABEL, bins=(9, 3), invert=2), None, _H, _WORDS, 0, None), INVALID,
+     "vv_distance_volume: labels must be NULL for VV_SEED_BINS and given for the labels sources"),
+    ("vv_distance_volume", "u8", (_dist(invert=2, spacing=(1, 0, 1)), _H, _H, _WORDS, 0, None), INVALID, "vv_distance_volume: invert must be 0 or 1"),
+    ("vv_distance_volume", "u8", (_dist(spacing=(70000, 1, 0)), _H, _H, _WORDS, 0, None), INVALID, "vv_distance_volume: every spacing must be at least 1"),
+    ("vv_distance_volume", "u8", (_dist(spacing=(1, 1, 70000), out=2), _H, _H, _WORDS, 0, None), INVALID,
+     "vv_distance_volume: the largest squared distance of the box, sum of (spacing (extent - 1))^2, must be at most 0xFFFFFFFE"),
+    ("vv_distance_volume", "u8", (_dist(spacing=(21845, 21845, 1), out=2), _H, _H, _WORDS, 0, None), INVALID,
+     "vv_distance_volume: the largest squared distance of the box, sum of (spacing (extent - 1))^2, must be at most 0xFFFFFFFE"),
+    ("vv_distance_volume", "u8", (_dist(out=2), _H, _H, _WORDS - 1, 0, None), INVALID, "vv_distance_volume: out must be VV_DIST_SQUARED or VV_DIST_WITHIN"),
+    ("vv_distance_volume", "u8", (_dist(), "dev+0", "dev+1026", _WORDS - 1, 1, None), INVALID, "vv_distance_volume: capacity is below 4 bytes per voxel of the box"),
+    ("vv_distance_volume", "u8", (_dist(), "dev+4", "dev+2", _WORDS, 1, None), INVALID, "vv_distance_volume: device labels and out must be 4-byte aligned"),
+    ("vv_distance_volume", "u8", (_dist(), "dev+1", "dev+4", _WORDS, 1, None), INVALID, "vv_distance_volume: device labels and out must be 4-byte aligned"),
+    ("vv_distance_volume", "u8", (_dist(), "dev+2", "dev+2", _WORDS, 1, None), INVALID, "vv_distance_volume: device labels and out must be 4-byte aligned"),
+    ("vv_distance_volume", "u8", (_dist(), "dev+4", "dev+0", _WORDS, 1, None), INVALID, "vv_distance_volume: out overlaps labels without being the same pointer"),
+    ("vv_distance_volume", "f32", (_dist(), "dev+0", "dev+252", _WORDS, 1, None), INVALID, "vv_distance_volume: out overlaps labels without being the same pointer"),
+    # vv_region_table (rule 8): context, d / labels / compact, volume, box, source, table NULL with rows, compact capacity, table capacity, 4-byte
+    # alignment (labels, aux, compact), 8-byte alignment (table, summary), compact's overlaps, table's overlaps
+    ("vv_region_table", "null", (None, _H, None, _H, _WORDS, None, 0, None, 0, None), INVALID, "vv_region_table: NULL context"),
+    ("vv_region_table", "fresh", (None, _H, None, _H, _WORDS, None, 0, None, 0, None), INVALID, "vv_region_table: NULL argument"),
+    ("vv_region_table", "fresh", (_regions(), None, None, _H, _WORDS, None, 0, None, 0, None), INVALID, "vv_region_table: NULL argument"),
+    ("vv_region_table", "fresh", (_regions(), _H, None, None, _WORDS, None, 0, None, 0, None), INVALID, "vv_region_table: NULL argument"),
+    ("vv_region_table", "fresh", (_regions(box=_BAD_BOX), _H, None, _H, _WORDS, None, 0, None, 0, None), NO_VOLUME, "vv_region_table: no volume loaded"),
+    ("vv_region_table", "u8", (_regions(box=_BAD_BOX, source=4), _H, None, _H, _WORDS, None, 0, None, 0, None), INVALID,
+     "vv_region_table: the box must satisfy 0 <= lo < hi <= dims on every axis (or be all zeros)"),
+    ("vv_region_table", "u8", (_regions(source=4), _H, None, _H, _WORDS, None, 0, None, 0, None), INVALID,
+     "vv_region_table: source must be VV_REGION_LABELS or VV_REGION_NONZERO"),
+    ("vv_region_table", "u8", (_regions(), _H, None, _H, _WORDS - 1, None, 0, None, 0, None), INVALID, "vv_region_table: table is NULL with max_regions != 0"),
+    ("vv_region_table", "u8", (_regions(), _H, None, _H, _WORDS - 1, _H, 2 * _ROW - 1, None, 0, None), INVALID,
+     "vv_region_table: compact capacity is below 4 bytes per voxel of the box"),
+    ("vv_region_table", "u8", (_regions(), _RL, _RA, "dev+513", _WORDS, _RT, 2 * _ROW - 1, _RS, 1, None), INVALID,
+     "vv_region_table: table capacity is below sizeof(vv_region) * max_regions"),
+    ("vv_region_table", "u8", (_regions(), _RL, _RA, "dev+514", _WORDS, "dev+1028", 2 * _ROW, _RS, 1, None), INVALID,
+     "vv_region_table: device labels, aux and compact must be 4-byte aligned"),
+    ("vv_region_table", "u8", (_regions(), "dev+1", _RA, _RC, _WORDS, "dev+1028", 2 * _ROW, _RS, 1, None), INVALID,
+     "vv_region_table: device labels, aux and compact must be 4-byte aligned"),
+    ("vv_region_table", "u8", (_regions(), _RL, "dev+258", _RC, _WORDS, "dev+1028", 2 * _ROW, _RS, 1, None), INVALID,
+     "vv_region_table: device labels, aux and compact must be 4-byte aligned"),
+    ("vv_region_table", "u8", (_regions(), _RL, _RA, "dev+252", _WORDS, "dev+1028", 2 * _ROW, _RS, 1, None), INVALID,
+     "vv_region_table: a device table and summary must be 8-byte aligned"),
+    ("vv_region_table", "u8", (_regions(), _RL, _RA, "dev+252", _WORDS, _RT, 2 * _ROW, "dev+2052", 1, None), INVALID,
+     "vv_region_table: a device table and summary must be 8-byte aligned"),
+    ("vv_region_table", "u8", (_regions(), _RL, _RA, "dev+252", _WORDS, "dev+248", 2 * _ROW, _RS, 1, None), INVALID,
+     "vv_region_table: compact overlaps labels, aux, table or the loaded volume"),
+    ("vv_region_table", "u8", (_regions(), _RL, _RA, "dev+508", _WORDS, "dev+248", 2 * _ROW, _RS, 1, None), INVALID,
+     "vv_region_table: compact overlaps labels, aux, table or the loaded volume"),
+    ("vv_region_table", "f32", (_regions(), _RL, None, "dev+1020", _WORDS, _RT, 2 * _ROW, _RS, 1, None), INVALID,
+     "vv_region_table: compact overlaps labels, aux, table or the loaded volume"),
+    ("vv_region_table", "u8", (_regions(), _RL, _RA, "dev+2048", _WORDS, "dev+248", 2 * _ROW, None, 1, None), INVALID,
+     "vv_region_table: table overlaps labels, aux or the loaded volume"),
+    ("vv_region_table", "u8", (_regions(), "dev+2048", _RA, "dev+3072", _WORDS, "dev+504", 2 * _ROW, None, 1, None), INVALID,
+     "vv_region_table: table overlaps labels, aux or the loaded volume"),
+    # vv_mesh_dims (rule 11 up to the site grid, then cap): context, d / out_dims, volume, box, cap
+    ("vv_mesh_dims", "null", (None, _DIMS), INVALID, "vv_mesh_dims: NULL context"),
+    ("vv_mesh_dims", "fresh", (None, _DIMS), INVALID, "vv_mesh_dims: NULL argument"),
+    ("vv_mesh_dims", "fresh", (_mesh(box=_BAD_BOX), None), INVALID, "vv_mesh_dims: NULL argument"),
+    ("vv_mesh_dims", "fresh", (_mesh(box=_BAD_BOX), _DIMS), NO_VOLUME, "vv_mesh_dims: no volume loaded"),
+    ("vv_mesh_dims", "u8", (_mesh(box=_BAD_BOX, cap=2), _DIMS), INVALID, "vv_mesh_dims: the box must satisfy 0 <= lo < hi <= dims on every axis (or be all zeros)"),
+    ("vv_mesh_dims", "f32", (_mesh(cap=2), _DIMS), INVALID, "vv_mesh_dims: cap must be 0 or 1"),
+    # vv_surface_mesh (rule 11): context, d, volume, box, source, level, bins, labels against the source, cap, index / vertices / quads NULL with a
+    # maximum, the three capacities, 4-byte (labels, index), 16-byte (vertices, normals, quads) and 8-byte (summary) alignment, one overlap per output
+    ("vv_surface_mesh", "null", (None, None, None, 0, None, 0, None, None, 0, None, 0, None), INVALID, "vv_surface_mesh: NULL context"),
+    ("vv_surface_mesh", "fresh", (None, None, None, 0, None, 0, None, None, 0, None, 0, None), INVALID, "vv_surface_mesh: NULL argument"),
+    ("vv_surface_mesh", "fresh", (_mesh(box=_BAD_BOX), _H, None, 0, None, 0, None, None, 0, None, 0, None), NO_VOLUME, "vv_surface_mesh: no volume loaded"),
+    ("vv_surface_mesh", "u8", (_mesh(box=_BAD_BOX, source=9), _H, None, 0, None, 0, None, None, 0, None, 0, None), INVALID,
+     "vv_surface_mesh: the box must satisfy 0 <= lo < hi <= dims on every axis (or be all zeros)"),
+    ("vv_surface_mesh", "u8", (_mesh(source=9, level=0, bins=(9, 3), cap=2), _H, None, 0, None, 0, None, None, 0, None, 0, None), INVALID,
+     "vv_surface_mesh: source must be VV_MESH_INDEX, VV_MESH_BINS, VV_MESH_LABEL or VV_MESH_NONZERO"),
+    ("vv_surface_mesh", "u8", (_mesh(source=vv.MESH_INDEX, level=0, bins=(9, 3)), _H, None, 0, None, 0, None, None, 0, None, 0, None), INVALID,
+     "vv_surface_mesh: level must lie in 1..255"),
+    ("vv_surface_mesh", "u8", (_mesh(source=vv.MESH_INDEX, level=256), _H, None, 0, None, 0, None, None, 0, None, 0, None), INVALID,
+     "vv_surface_mesh: level must lie in 1..255"),
+    ("vv_surface_mesh", "u8", (_mesh(source=vv.MESH_BINS, level=0, bins=(9, 3)), _H, None, 0, None, 0, None, None, 0, None, 0, None), INVALID,
+     "vv_surface_mesh: bins must satisfy 0 <= bin_lo <= bin_hi <= 255"),
+    ("vv_surface_mesh", "u8", (_mesh(source=vv.MESH_BINS, cap=2), _H, None, 0, None, 0, None, None, 0, None, 0, None), INVALID,
+     "vv_surface_mesh: labels must be given for the labels sources and NULL for VV_MESH_INDEX and VV_MESH_BINS"),
+    ("vv_surface_mesh", "f32", (_mesh(source=vv.MESH_LABEL, level=0, bins=(9, 3), cap=2), None, None, 0, None, 0, None, None, 0, None, 0, None), INVALID,
+     "vv_surface_mesh: labels must be given for the labels sources and NULL for VV_MESH_INDEX and VV_MESH_BINS"),
+    ("vv_surface_mesh", "u8", (_mesh(cap=2), _H, None, 0, None, 0, None, None, 0, None, 0, None), INVALID, "vv_surface_mesh: cap must be 0 or 1"),
+    ("vv_surface_mesh", "u8", (_mesh(), _H, None, 0, None, 0, None, None, 0, None, 0, None), INVALID, "vv_surface_mesh: index is NULL with a non-zero maximum"),
+    ("vv_surface_mesh", "u8", (_mesh(max_vertices=0), _H, None, 0, None, 0, None, None, 0, None, 0, None), INVALID, "vv_surface_mesh: index is NULL with a non-zero maximum"),
+    ("vv_surface_mesh", "u8", (_mesh(), _H, _H, 0, None, 0, None, None, 0, None, 0, None), INVALID, "vv_surface_mesh: vertices is NULL with max_vertices != 0"),
+    ("vv_surface_mesh", "u8", (_mesh(), _H, _H, 0, _H, 0, None, None, 0, None, 0, None), INVALID, "vv_surface_mesh: quads is NULL with max_quads != 0"),
+    ("vv_surface_mesh", "u8", (_mesh(), _H, _H, 107, _H, 63, None, _H, 63, None, 0, None), INVALID, "vv_surface_mesh: index capacity is below 4 bytes per site (vv_mesh_dims)"),
+    ("vv_surface_mesh", "u8", (_mesh(), _H, _H, 108, _H, 63, None, _H, 63, None, 0, None), INVALID, "vv_surface_mesh: vertices capacity is below 16 bytes * max_vertices"),
+    ("vv_surface_mesh", "u8", (_mesh(), _ML, "dev+258", 108, _MV, 64, None, _MQ, 63, None, 1, None), INVALID, "vv_surface_mesh: quads capacity is below 16 bytes * max_quads"),
+    ("vv_surface_mesh", "u8", (_mesh(), _ML, "dev+258", 108, "dev+520", 64, None, _MQ, 64, None, 1, None), INVALID, "vv_surface_mesh: device labels and index must be 4-byte aligned"),
+    ("vv_surface_mesh", "u8", (_mesh(), "dev+1", _MI, 108, "dev+520", 64, None, _MQ, 64, None, 1, None), INVALID, "vv_surface_mesh: device labels and index must be 4-byte aligned"),
+    ("vv_surface_mesh", "u8", (_mesh(), _ML, _MI, 108, "dev+520", 64, None, _MQ, 64, "dev+1028", 1, None), INVALID,
+     "vv_surface_mesh: device vertices, normals and quads must be 16-byte aligned"),
+    ("vv_surface_mesh", "u8", (_mesh(), _ML, _MI, 108, _MV, 64, "dev+644", _MQ, 64, "dev+1028", 1, None), INVALID,
+     "vv_surface_mesh: device vertices, normals and quads must be 16-byte aligned"),
+    ("vv_surface_mesh", "u8", (_mesh(), _ML, _MI, 108, _MV, 64, None, "dev+776", 64, "dev+1028", 1, None), INVALID,
+     "vv_surface_mesh: device vertices, normals and quads must be 16-byte aligned"),
+    ("vv_surface_mesh", "u8", (_mesh(), _ML, "dev+252", 108, _MV, 64, None, _MQ, 64, "dev+1028", 1, None), INVALID, "vv_surface_mesh: a device summary must be 8-byte aligned"),
+    ("vv_surface_mesh", "u8", (_mesh(), _ML, "dev+252", 108, "dev+240", 64, _MN, _MQ, 64, _MS, 1, None), INVALID,
+     "vv_surface_mesh: index overlaps another buffer of the call or the loaded volume"),
+    ("vv_surface_mesh", "u8", (_mesh(), _ML, _MI, 108, _MV, 64, "dev+560", "dev+608", 64, _MS, 1, None), INVALID,
+     "vv_surface_mesh: vertices overlaps another buffer of the call or the loaded volume"),
+    ("vv_surface_mesh", "u8", (_mesh(), _ML, _MI, 108, _MV, 64, _MN, "dev+688", 64, "dev+744", 1, None), INVALID,
+     "vv_surface_mesh: normals overlaps another buffer of the call or the loaded volume"),
+    ("vv_surface_mesh", "u8", (_mesh(), _ML, _MI, 108, _MV, 64, _MN, _MQ, 64, "dev+824", 1, None), INVALID,
+     "vv_surface_mesh: quads overlaps another buffer of the call or the loaded volume"),
+    ("vv_surface_mesh", "f32", (_mesh(), _ML, _MI, 108, _MV, 64, _MN, _MQ, 64, "dev+224", 1, None), INVALID,
+     "vv_surface_mesh: summary overlaps another buffer of the call or the loaded volume"),
 ]
 
 

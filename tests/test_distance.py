@@ -196,10 +196,6 @@ def test_model_identities():
 # ---------------------------------------------------------------------------------------------------------------------
 # GPU
 # ---------------------------------------------------------------------------------------------------------------------
-def _clear_env(monkeypatch):
-    VO.clear_env(monkeypatch, LAYOUT_KNOBS)
-
-
 def _load(ctx, monkeypatch, vol):
     VO.load(ctx, monkeypatch, LAYOUT_KNOBS, vol, TF)
 
@@ -404,26 +400,12 @@ def test_distance_block_order(ctx, case, monkeypatch):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("kind,nx", [("u8", 64), ("f32", 20)])     # (rows of a multiple of 16 bytes are re-pitched)
-@pytest.mark.parametrize("knobs", [{"VV_PITCH_FORCE": "1"}, {"VV_PITCH_FORCE": "1", "VV_PITCH_ROWS": "1"}, {"VV_PITCH_FORCE": "1", "VV_FORCE_BIG": "1"}, {"VV_FORCE_BIG": "1"}],
-                         ids=["pitch", "pitch_rows", "pitch_big", "big"])
+@VO.layout_sweep
 def test_distance_layouts(kind, nx, knobs, monkeypatch):
     """A re-pitched volume (32 bytes of zeros behind every row, with and without an extra row of zeros per slice) and the 64-bit addressing build.
     The volume holds no zero: bin 0 has no voxel unless padding is read as data."""
-    _clear_env(monkeypatch)
-    for k, v in knobs.items():
-        monkeypatch.setenv(k, v)
-    ny, nz = 11, 10
-    rng = np.random.default_rng(43)
-    vol = rng.integers(1, 256, (nz, ny, nx), dtype=np.uint8)
-    if kind == "f32":
-        vol = (vol.astype(f32) / f32(255)).astype(f32)
-    with vv.Context(0) as c:                                    # a context created under the environment
-        c.load_volume(vol, TF)
-        if "VV_PITCH_FORCE" in knobs:
-            row = nx * vol.itemsize + 32
-            rows = ny + 1 if "VV_PITCH_ROWS" in knobs else ny
-            assert c.device_bytes()[0] == nz * rows * row + rows * row + 2 * row + 4096             # the volume is re-pitched
+    with VO.layout_context(kind, nx, knobs, monkeypatch, LAYOUT_KNOBS, TF) as (c, vol):
+        nz, ny, _ = vol.shape
         dev = VO.DeviceOut(vol.size * 4)
         for bins, box, spacing in (((1, 8), None, (1, 1, 1)), ((200, 255), ((1, 0, 1), (nx - 1, ny, nz - 1)), (1, 2, 5)), ((250, 255), ((3, 2, 1), (nx, ny - 1, nz)), (3, 1, 2))):
             _run_case(c, dev, f"layout {kind} {knobs}", DM.distance(vol, bins, spacing=spacing, box=box), bins=bins, spacing=spacing, box=box)
@@ -435,20 +417,11 @@ def test_distance_load_paths_and_streams(ctx, monkeypatch):
     """A volume that came from a device buffer and one promoted by the streamed upload; then enqueue-only calls on a torch stream, synchronised by
     the stream alone."""
     import torch
-    _clear_env(monkeypatch)
-    ctx.reread_env()
     tdev = torch.device("cuda", 0)
     vol8 = np.random.default_rng(5).integers(0, 256, (13, 21, 37), dtype=np.uint8)
-    nz, ny, nx = vol8.shape
     dev = VO.DeviceOut(vol8.size * 4)
-    t = torch.from_numpy(vol8.copy()).to(tdev)
-    ctx.load_volume_device(t.data_ptr(), vv.VOXEL_U8, nx, ny, nz, TF)
-    torch.cuda.synchronize()
-    del t
-    _run_case(ctx, dev, "load_volume_device", DM.distance(vol8, (0, 3), spacing=(1, 2, 5)), bins=(0, 3), spacing=(1, 2, 5))
-    promoted = (vol8.astype(f32) / f32(255)).astype(f32)
-    ctx.load_volume_streamed([(4, vol8[4:]), (0, vol8[:4])], vv.VOXEL_F32, nx, ny, nz, TF)
-    _run_case(ctx, dev, "streamed upload with promotion", DM.distance(promoted, (0, 3), spacing=(3, 1, 2)), bins=(0, 3), spacing=(3, 1, 2))
+    for (what, loaded), spacing in zip(VO.load_paths(ctx, monkeypatch, LAYOUT_KNOBS, vol8, TF), ((1, 2, 5), (3, 1, 2))):
+        _run_case(ctx, dev, what, DM.distance(loaded, (0, 3), spacing=spacing), bins=(0, 3), spacing=spacing)
     # enqueue only: the distances, a margin, and the margin's complement grown again, in place
     vol = _random("u8", 50)
     _load(ctx, monkeypatch, vol)
@@ -602,10 +575,7 @@ def test_distance_errors_and_state(ctx, monkeypatch):
     vol = TH._volume("aniso")
     _load(ctx, monkeypatch, vol)
     n = vol.size
-    cam = vv.Camera.orbit(3.0, 1.0, 0.6)
-    frame_before = ctx.render(57, 43, cam, fill=1)
-    hist_before = ctx.histogram()
-    state, dbytes, ms = ctx.layout_state(), ctx.device_bytes(), ctx.last_frame_ms()
+    before = VO.Untouched(ctx)
     out_t = torch.empty(n, dtype=torch.int32, device=tdev)
     lab_t = torch.ones(n, dtype=torch.int32, device=tdev)
 
@@ -615,18 +585,10 @@ def test_distance_errors_and_state(ctx, monkeypatch):
             ctx.distance_device(out_t.data_ptr(), n * 4, labels_ptr=out_t.data_ptr(), label=0, within=7, spacing=spacing)
             ctx.distance_device(out_t.data_ptr(), n * 4, labels_ptr=lab_t.data_ptr(), invert=True)
 
-    calls()
-    torch.cuda.synchronize()
-    free_before = torch.cuda.mem_get_info(tdev)[0]
-    calls()
-    torch.cuda.synchronize()
-    assert torch.cuda.mem_get_info(tdev)[0] == free_before, "a device call changed the device's free memory"
+    VO.free_memory_unchanged(calls)
     assert bool((out_t == -1).all()), "every voxel a label, inverted: no seed"
     with pytest.raises(vv.VolvizError):
         ctx.distance(bins=(300, 400))
     _check(ctx.distance(bins=(60, 100), prefill=GARBAGE), DM.distance(vol, (60, 100)), "a good call after the refused ones")
     _check(ctx.morphology(vv.MORPH_OPEN, 1, bins=(60, 100)), DM.morphology(DM.OPEN, DM.seeds(vol, (60, 100)), 1), "an opening after the refused calls")
-    assert ctx.layout_state() == state and ctx.device_bytes() == dbytes and ctx.last_frame_ms() == ms
-    TH._same(ctx.histogram(prefill=GARBAGE), hist_before, "the volume's histogram after the calls")
-    assert np.array_equal(ctx.render(57, 43, cam, fill=1), frame_before)
-    assert ctx.layout_state() == state and ctx.device_bytes() == dbytes
+    before.check()

@@ -209,48 +209,25 @@ def test_model_mask_identities():
 # ---------------------------------------------------------------------------------------------------------------------
 # GPU
 # ---------------------------------------------------------------------------------------------------------------------
-def _clear_env(monkeypatch):
-    VO.clear_env(monkeypatch, LAYOUT_KNOBS)
-
-
 def _load(ctx, monkeypatch, volname):
     VO.load(ctx, monkeypatch, LAYOUT_KNOBS, _volume(volname), TF)
 
 
-class LabelOut:
-    """The guarded device buffer of a label call: GARBAGE everywhere before each call; labels, sizes and stats lie GUARD bytes apart, labels and
-    sizes at a start that moves by 4 bytes from call to call (stats by 8); every byte outside the three outputs must survive."""
+class LabelOut(VO.GuardedOuts):
+    """The guarded device buffer of a label call: labels and sizes at a start that moves by 4 bytes (from call to call; every fourth call), stats by 8."""
 
     def __init__(self, voxels):
-        import torch
-        self.torch = torch
+        super().__init__(2 * (4 * voxels + 16) + 32 + 16 + 4 * GUARD, 8)
         self.voxels = voxels
-        self.buf = torch.empty(2 * (4 * voxels + 16) + 32 + 16 + 4 * GUARD, dtype=torch.uint8, device=torch.device("cuda", 0))
-        assert self.buf.data_ptr() % 8 == 0
-        self.calls = 0
 
     def run(self, call, shape, sizes=True, stats=True, what=""):
         """call(labels_ptr, capacity, sizes_ptr, stats_ptr), complete on return -> labels, sizes or None, stats tuple or None"""
-        self.calls += 1
         n = int(np.prod(shape)) * 4
         assert n <= 4 * self.voxels
-        l0 = GUARD + 4 * (self.calls % 4)
-        s0 = l0 + n + GUARD + 4 * ((self.calls // 4) % 4)
-        t0 = (s0 + n + GUARD + 7) // 8 * 8 + 8 * (self.calls % 2)
-        self.buf.fill_(GARBAGE)
-        self.torch.cuda.synchronize()
-        base = self.buf.data_ptr()
-        call(base + l0, n, base + s0 if sizes else 0, base + t0 if stats else 0)
-        raw = self.buf.cpu().numpy()
-        keep = np.ones(raw.size, bool)
-        keep[l0:l0 + n] = False
-        if sizes:
-            keep[s0:s0 + n] = False
-        if stats:
-            keep[t0:t0 + 32] = False
-        assert (raw[keep] == GARBAGE).all(), f"bytes outside the outputs were written ({what})"
-        return (raw[l0:l0 + n].copy().view(np.uint32).reshape(shape), raw[s0:s0 + n].copy().view(np.uint32).reshape(shape) if sizes else None,
-                _stats_tuple(vv.LabelStats.from_bytes(raw[t0:t0 + 32])) if stats else None)
+        outs = [VO.Out(n), VO.Out(n, digit=4, present=sizes), VO.Out(32, align=8, present=stats)]
+        l, s, t = self.run_outs(lambda p: call(p[0], n, p[1], p[2]), outs, what)
+        return (l.view(np.uint32).reshape(shape), s.view(np.uint32).reshape(shape) if sizes else None,
+                _stats_tuple(vv.LabelStats.from_bytes(t)) if stats else None)
 
 
 def _run_case(ctx, dev, what, want, bins, conn, box=None, host=True):
@@ -378,26 +355,12 @@ def test_label_block_order(ctx, volname, conn, bins, monkeypatch):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("kind,nx", [("u8", 64), ("f32", 20)])     # (rows of a multiple of 16 bytes are re-pitched)
-@pytest.mark.parametrize("knobs", [{"VV_PITCH_FORCE": "1"}, {"VV_PITCH_FORCE": "1", "VV_PITCH_ROWS": "1"}, {"VV_PITCH_FORCE": "1", "VV_FORCE_BIG": "1"}, {"VV_FORCE_BIG": "1"}],
-                         ids=["pitch", "pitch_rows", "pitch_big", "big"])
+@VO.layout_sweep
 def test_label_layouts(kind, nx, knobs, monkeypatch):
     """A re-pitched volume (32 bytes of zeros behind every row, with and without an extra row of zeros per slice) and the 64-bit addressing build.
     The volume holds no zero: bin 0 is empty unless padding is read as data."""
-    _clear_env(monkeypatch)
-    for k, v in knobs.items():
-        monkeypatch.setenv(k, v)
-    ny, nz = 11, 10
-    rng = np.random.default_rng(43)
-    vol = rng.integers(1, 256, (nz, ny, nx), dtype=np.uint8)
-    if kind == "f32":
-        vol = (vol.astype(f32) / f32(255)).astype(f32)
-    with vv.Context(0) as c:                                    # a context created under the environment
-        c.load_volume(vol, TF)
-        if "VV_PITCH_FORCE" in knobs:
-            row = nx * vol.itemsize + 32
-            rows = ny + 1 if "VV_PITCH_ROWS" in knobs else ny
-            assert c.device_bytes()[0] == nz * rows * row + rows * row + 2 * row + 4096             # the volume is re-pitched
+    with VO.layout_context(kind, nx, knobs, monkeypatch, LAYOUT_KNOBS, TF) as (c, vol):
+        nz, ny, _ = vol.shape
         dev = LabelOut(vol.size)
         for conn, bins, box in ((6, (1, 100), None), (18, (200, 255), ((1, 0, 1), (nx - 1, ny, nz - 1))), (26, (0, 40), None), (6, (0, 0), None)):
             want = LM.label(vol, bins, conn, box)
@@ -412,21 +375,12 @@ def test_label_load_paths_and_streams(ctx, monkeypatch):
     """A volume that came from a device buffer and one promoted by the streamed upload; then an enqueue-only call on a torch stream, synchronised
     by the stream alone."""
     import torch
-    _clear_env(monkeypatch)
-    ctx.reread_env()
     tdev = torch.device("cuda", 0)
     vol8 = _volume("u8:37x21x13")
-    nz, ny, nx = vol8.shape
     dev = LabelOut(vol8.size)
-    t = torch.from_numpy(vol8.copy()).to(tdev)
-    ctx.load_volume_device(t.data_ptr(), vv.VOXEL_U8, nx, ny, nz, TF)
-    torch.cuda.synchronize()
-    del t
-    _run_case(ctx, dev, "load_volume_device", _want("u8:37x21x13", (0, 100), 18), (0, 100), 18)
-    promoted = (vol8.astype(f32) / f32(255)).astype(f32)
-    ctx.load_volume_streamed([(4, vol8[4:]), (0, vol8[:4])], vv.VOXEL_F32, nx, ny, nz, TF)
-    _run_case(ctx, dev, "streamed upload with promotion", LM.label(promoted, (0, 100), 26), (0, 100), 26)
-    assert np.array_equal(HM.bins(promoted), vol8)
+    for (what, vol), conn in zip(VO.load_paths(ctx, monkeypatch, LAYOUT_KNOBS, vol8, TF), (18, 26)):
+        _run_case(ctx, dev, what, _want("u8:37x21x13", (0, 100), 18) if vol is vol8 else LM.label(vol, (0, 100), 26), (0, 100), conn)
+    assert np.array_equal(HM.bins(vol), vol8)
     # enqueue only
     _load(ctx, monkeypatch, "r70_u8")
     conn, bins = 6, (0, 78)
@@ -565,10 +519,7 @@ def test_label_and_mask_errors_and_state(ctx, monkeypatch):
     vol = _volume("aniso")
     nz, ny, nx = vol.shape
     n = vol.size
-    cam = vv.Camera.orbit(3.0, 1.0, 0.6)
-    frame_before = ctx.render(57, 43, cam, fill=1)
-    hist_before = ctx.histogram()
-    state, dbytes, ms = ctx.layout_state(), ctx.device_bytes(), ctx.last_frame_ms()
+    before = VO.Untouched(ctx)
 
     host = np.full(2 * n * 4 + 64 + GUARD, GARBAGE, np.uint8)
     raw = torch.full((2 * n * 4 + 64 + GUARD,), GARBAGE, dtype=torch.uint8, device=tdev)
@@ -661,15 +612,7 @@ def test_label_and_mask_errors_and_state(ctx, monkeypatch):
             for out_type in (vv.VOXEL_U8, vv.VOXEL_F32):
                 ctx.mask_device(out_t.data_ptr(), n * 4, lab_t.data_ptr(), vv.KEEP_MIN_SIZE, min_size=10, sizes_ptr=siz_t.data_ptr(), out_type=out_type)
 
-    calls()
-    torch.cuda.synchronize()
-    free_before = torch.cuda.mem_get_info(tdev)[0]
-    calls()
-    torch.cuda.synchronize()
-    assert torch.cuda.mem_get_info(tdev)[0] == free_before, "a device-output call changed the device's free memory"
+    VO.free_memory_unchanged(calls, "a device-output call")
     # the context is still usable and untouched: volume, layout copies, residency, scratch, frame time, histogram, frames
     _check(ctx.label((60, 100), 6, prefill=GARBAGE), _want("aniso", (60, 100), 6)[0], "a good call after the refused ones")
-    assert ctx.layout_state() == state and ctx.device_bytes() == dbytes and ctx.last_frame_ms() == ms
-    TH._same(ctx.histogram(prefill=GARBAGE), hist_before, "the volume's histogram after the calls")
-    assert np.array_equal(ctx.render(57, 43, cam, fill=1), frame_before)
-    assert ctx.layout_state() == state and ctx.device_bytes() == dbytes
+    before.check()

@@ -256,57 +256,28 @@ def _align(v, a):
     return (v + a - 1) // a * a
 
 
-class MeshOut:
-    """The guarded device buffer of a mesh call: GARBAGE everywhere before each call; index, vertices, normals, quads and summary lie GUARD bytes
-    apart, index at a start that moves by 4 bytes from call to call, the records by 16, the summary by 8; every byte outside the outputs (the records
-    that are not written among them) must survive."""
+class MeshOut(VO.GuardedOuts):
+    """The guarded device buffer of a mesh call: index at a start that moves by 4 bytes from call to call, the records by 16 (vertices every call,
+    normals every second, quads every fourth), the summary by 8; the records that are not written must survive like the guards."""
 
     def __init__(self, sites, rows_v, rows_q):
-        import torch
-        self.torch = torch
+        super().__init__(4 * sites + 32 * rows_v + 16 * rows_q + 32 + 6 * GUARD + 160, 16)
         self.sites, self.rows_v, self.rows_q = sites, rows_v, rows_q
-        self.tdev = torch.device("cuda", 0)
-        self.buf = torch.empty(4 * sites + 32 * rows_v + 16 * rows_q + 32 + 6 * GUARD + 160, dtype=torch.uint8, device=self.tdev)
-        assert self.buf.data_ptr() % 16 == 0
-        self.calls = 0
-
-    def upload(self, a):
-        return self.torch.from_numpy(np.ascontiguousarray(a, np.uint32).view(np.int32).copy()).to(self.tdev)
 
     def run(self, call, dims, max_v, max_q, written, normals=True, summary=True, index=True, what=""):
         """call(index_ptr, index_capacity, vertices_ptr, normals_ptr, quads_ptr, summary_ptr), complete on return -> index, the written vertex, normal
         and quad records, the summary tuple (None where the output was not asked for)"""
-        self.calls += 1
-        k = self.calls
         n = int(np.prod(dims)) * 4
         wv, wq = written
         assert n <= 4 * self.sites and max_v <= self.rows_v and max_q <= self.rows_q
-        i0 = GUARD + 4 * (k % 4)
-        v0 = _align(i0 + n + GUARD, 16) + 16 * (k % 2)
-        n0 = _align(v0 + 16 * max_v + GUARD, 16) + 16 * ((k // 2) % 2)
-        q0 = _align(n0 + 16 * max_v + GUARD, 16) + 16 * ((k // 4) % 2)
-        s0 = _align(q0 + 16 * max_q + GUARD, 8) + 8 * (k % 2)
-        assert s0 + 32 + GUARD <= self.buf.numel()
-        self.buf.fill_(GARBAGE)
-        self.torch.cuda.synchronize()
-        base = self.buf.data_ptr()
-        call(base + i0 if index else 0, n if index else 0, base + v0 if max_v else 0, base + n0 if normals and max_v else 0, base + q0 if max_q else 0,
-             base + s0 if summary else 0)
-        self.torch.cuda.synchronize()
-        raw = self.buf.cpu().numpy()
-        keep = np.ones(raw.size, bool)
-        if index:
-            keep[i0:i0 + n] = False
-        keep[v0:v0 + 16 * wv] = False
-        if normals:
-            keep[n0:n0 + 16 * wv] = False
-        keep[q0:q0 + 16 * wq] = False
-        if summary:
-            keep[s0:s0 + 32] = False
-        assert (raw[keep] == GARBAGE).all(), f"bytes outside the outputs were written ({what})"
-        return (raw[i0:i0 + n].copy().view(np.uint32).reshape(dims[::-1]) if index else None, raw[v0:v0 + 16 * wv].copy().view(vv.MESH_VERTEX_DTYPE),
-                raw[n0:n0 + 16 * wv].copy().view(vv.MESH_NORMAL_DTYPE) if normals else None, raw[q0:q0 + 16 * wq].copy().view(np.uint32).reshape(-1, 4),
-                _summary_tuple(vv.MeshSummary.from_bytes(raw[s0:s0 + 32])) if summary else None)
+        outs = [VO.Out(n, present=index), VO.Out(16 * max_v, 16 * wv, align=16, present=max_v > 0),
+                VO.Out(16 * max_v, 16 * wv, align=16, digit=2, present=normals and max_v > 0), VO.Out(16 * max_q, 16 * wq, align=16, digit=4, present=max_q > 0),
+                VO.Out(32, align=8, present=summary)]
+        i, v, nr, q, s = self.run_outs(lambda p: call(p[0], n if index else 0, p[1], p[2], p[3], p[4]), outs, what)
+        none = np.zeros(0, np.uint8)                                # (an output without a record to write: nothing of it was written)
+        return (i.view(np.uint32).reshape(dims[::-1]) if index else None, (none if v is None else v).view(vv.MESH_VERTEX_DTYPE),
+                (none if nr is None else nr).view(vv.MESH_NORMAL_DTYPE) if normals else None, (none if q is None else q).view(np.uint32).reshape(-1, 4),
+                _summary_tuple(vv.MeshSummary.from_bytes(s)) if summary else None)
 
 
 def _check_records(got, want, what):
@@ -577,26 +548,12 @@ def test_mesh_chunk_cap_and_block_order(ctx, chunks, monkeypatch):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("kind,nx", [("u8", 64), ("f32", 20)])     # (rows of a multiple of 16 bytes are re-pitched)
-@pytest.mark.parametrize("knobs", [{"VV_PITCH_FORCE": "1"}, {"VV_PITCH_FORCE": "1", "VV_PITCH_ROWS": "1"}, {"VV_PITCH_FORCE": "1", "VV_FORCE_BIG": "1"}, {"VV_FORCE_BIG": "1"}],
-                         ids=["pitch", "pitch_rows", "pitch_big", "big"])
+@VO.layout_sweep
 def test_mesh_layouts(kind, nx, knobs, monkeypatch):
     """A re-pitched volume and the 64-bit addressing build, as test_regions.py sweeps them.  The volume holds no zero: with bins (0, 0) the mesh is
     empty unless padding is read as data."""
-    VO.clear_env(monkeypatch, LAYOUT_KNOBS)
-    for k, v in knobs.items():
-        monkeypatch.setenv(k, v)
-    ny, nz = 11, 10
-    rng = np.random.default_rng(43)
-    vol = rng.integers(1, 256, (nz, ny, nx), dtype=np.uint8)
-    if kind == "f32":
-        vol = (vol.astype(f32) / f32(255)).astype(f32)
-    with vv.Context(0) as c:
-        c.load_volume(vol, TF)
-        if "VV_PITCH_FORCE" in knobs:
-            row = nx * vol.itemsize + 32
-            rows = ny + 1 if "VV_PITCH_ROWS" in knobs else ny
-            assert c.device_bytes()[0] == nz * rows * row + rows * row + 2 * row + 4096             # the volume is re-pitched
+    with VO.layout_context(kind, nx, knobs, monkeypatch, LAYOUT_KNOBS, TF) as (c, vol):
+        nz, ny, _ = vol.shape
         dev = _dev_for(vol)
         for src, box in ((dict(level=128), None), (dict(bins=(1, 100)), ((1, 0, 1), (nx - 1, ny, nz - 1))), (dict(level=40), ((0, 3, 2), (nx, 9, 8)))):
             for cap in (1, 0):
@@ -611,21 +568,12 @@ def test_mesh_load_paths_and_streams(ctx, monkeypatch):
     """A volume that came from a device buffer and one promoted by the streamed upload; then label and mesh calls enqueued on one torch stream,
     synchronised by the stream alone."""
     import torch
-    VO.clear_env(monkeypatch, LAYOUT_KNOBS)
-    ctx.reread_env()
     tdev = torch.device("cuda", 0)
     vol8 = _volume("u8:37x21x13")
-    nz, ny, nx = vol8.shape
     dev = _dev_for(vol8)
-    tt = torch.from_numpy(vol8.copy()).to(tdev)
-    ctx.load_volume_device(tt.data_ptr(), vv.VOXEL_U8, nx, ny, nz, TF)
-    torch.cuda.synchronize()
-    del tt
-    _run_case(ctx, dev, "load_volume_device", vol8, dict(level=128), 1)
-    promoted = (vol8.astype(f32) / f32(255)).astype(f32)
-    ctx.load_volume_streamed([(4, vol8[4:]), (0, vol8[:4])], vv.VOXEL_F32, nx, ny, nz, TF)
-    _run_case(ctx, dev, "streamed upload with promotion", promoted, dict(level=128), 0)
-    _run_case(ctx, dev, "streamed upload with promotion", promoted, dict(bins=(0, 100)), 1)
+    for (what, loaded), cap in zip(VO.load_paths(ctx, monkeypatch, LAYOUT_KNOBS, vol8, TF), (1, 0)):
+        _run_case(ctx, dev, what, loaded, dict(level=128), cap)
+    _run_case(ctx, dev, what, loaded, dict(bins=(0, 100)), 1)
     # enqueue only: count, then the full call, behind the labels they read
     _load(ctx, monkeypatch, "r70_u8")
     vol = _volume("r70_u8")
@@ -686,10 +634,7 @@ def test_mesh_errors_and_state(ctx, monkeypatch):
     nz, ny, nx = vol.shape
     n = vol.size
     sites = (nx + 1) * (ny + 1) * (nz + 1)
-    cam = vv.Camera.orbit(3.0, 1.0, 0.6)
-    frame_before = ctx.render(57, 43, cam, fill=1)
-    hist_before = ctx.histogram()
-    state, dbytes, ms = ctx.layout_state(), ctx.device_bytes(), ctx.last_frame_ms()
+    before = VO.Untouched(ctx)
     assert ctx.mesh_dims() == (nx + 1, ny + 1, nz + 1) and ctx.mesh_dims(False) == (nx - 1, ny - 1, nz - 1) and ctx.mesh_dims(False, ((1, 2, 3), (2, 5, 9))) == (0, 2, 5)
     m = (C.c_int * 3)(7, 7, 7)
     assert lib.vv_mesh_dims(hnd, C.byref(mk(cap=2)), C.byref(m)) == ERR_INVALID and lib.vv_mesh_dims(hnd, C.byref(mk(lo=(1, 0, 0))), C.byref(m)) == ERR_INVALID
@@ -813,14 +758,6 @@ def test_mesh_errors_and_state(ctx, monkeypatch):
             assert call(dp, 1, mk(source=source, bins=(0, 99)), labels=L0 if source >= 2 else None) == 0
         assert call(dp, 1, mk(max_vertices=0, max_quads=0), index=None, vertices=None, normals=None, quads=None) == 0
 
-    calls()
-    torch.cuda.synchronize()
-    free_before = torch.cuda.mem_get_info(tdev)[0]
-    calls()
-    torch.cuda.synchronize()
-    assert torch.cuda.mem_get_info(tdev)[0] == free_before, "a device call changed the device's free memory"
+    VO.free_memory_unchanged(calls)
     # the context is still usable and untouched: volume, layout copies, residency, scratch, frame time, histogram, frames
-    assert ctx.layout_state() == state and ctx.device_bytes() == dbytes and ctx.last_frame_ms() == ms
-    TH._same(ctx.histogram(prefill=GARBAGE), hist_before, "the volume's histogram after the calls")
-    assert np.array_equal(ctx.render(57, 43, cam, fill=1), frame_before)
-    assert ctx.layout_state() == state and ctx.device_bytes() == dbytes
+    before.check()

@@ -264,45 +264,22 @@ def _load(ctx, monkeypatch, vol):
     VO.load(ctx, monkeypatch, LAYOUT_KNOBS, _volume(vol) if isinstance(vol, str) else vol, TF)
 
 
-class RegionOut:
-    """The guarded device buffer of a region call: GARBAGE everywhere before each call; compact, table and summary lie GUARD bytes apart, compact at
-    a start that moves by 4 bytes from call to call, table and summary by 8; every byte outside the outputs (the rows that are not written among
-    them) must survive."""
+class RegionOut(VO.GuardedOuts):
+    """The guarded device buffer of a region call: compact at a start that moves by 4 bytes from call to call, table and summary by 8 (every call;
+    every second call); the rows that are not written must survive like the guards."""
 
     def __init__(self, voxels, rows):
-        import torch
-        self.torch = torch
+        super().__init__(4 * voxels + ROW * rows + 32 + 4 * GUARD + 64, 8)
         self.voxels, self.rows = voxels, rows
-        self.tdev = torch.device("cuda", 0)
-        self.buf = torch.empty(4 * voxels + ROW * rows + 32 + 4 * GUARD + 64, dtype=torch.uint8, device=self.tdev)
-        assert self.buf.data_ptr() % 8 == 0
-        self.calls = 0
-
-    def upload(self, a):
-        return self.torch.from_numpy(np.ascontiguousarray(a, np.uint32).view(np.int32).copy()).to(self.tdev)
 
     def run(self, call, shape, max_regions, written, table=True, summary=True, what=""):
         """call(compact_ptr, capacity, table_ptr, summary_ptr), complete on return -> compact, the written rows, the summary tuple or None"""
-        self.calls += 1
         n = int(np.prod(shape)) * 4
         assert n <= 4 * self.voxels and max_regions <= self.rows
-        c0 = GUARD + 4 * (self.calls % 4)
-        t0 = (c0 + n + GUARD + 7) // 8 * 8 + 8 * (self.calls % 2)
-        s0 = (t0 + ROW * max_regions + GUARD + 7) // 8 * 8 + 8 * ((self.calls // 2) % 2)
-        self.buf.fill_(GARBAGE)
-        self.torch.cuda.synchronize()
-        base = self.buf.data_ptr()
-        call(base + c0, n, base + t0 if table else 0, base + s0 if summary else 0)
-        raw = self.buf.cpu().numpy()
-        keep = np.ones(raw.size, bool)
-        keep[c0:c0 + n] = False
-        if table:
-            keep[t0:t0 + ROW * written] = False
-        if summary:
-            keep[s0:s0 + 32] = False
-        assert (raw[keep] == GARBAGE).all(), f"bytes outside the outputs were written ({what})"
-        return (raw[c0:c0 + n].copy().view(np.uint32).reshape(shape), raw[t0:t0 + ROW * written].copy().view(vv.REGION_DTYPE) if table else None,
-                _summary_tuple(vv.RegionSummary.from_bytes(raw[s0:s0 + 32])) if summary else None)
+        outs = [VO.Out(n), VO.Out(ROW * max_regions, ROW * written, align=8, present=table), VO.Out(32, align=8, digit=2, present=summary)]
+        c, t, s = self.run_outs(lambda p: call(p[0], n, p[1], p[2]), outs, what)
+        return (c.view(np.uint32).reshape(shape), t.view(vv.REGION_DTYPE) if table else None,
+                _summary_tuple(vv.RegionSummary.from_bytes(s)) if summary else None)
 
 
 def _run_case(ctx, dev, what, vol, labels, aux=None, source=RM.LABELS, box=None, max_regions=None, host=True):
@@ -572,26 +549,12 @@ def test_region_nonzero_source(ctx, monkeypatch):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("kind,nx", [("u8", 64), ("f32", 20)])     # (rows of a multiple of 16 bytes are re-pitched)
-@pytest.mark.parametrize("knobs", [{"VV_PITCH_FORCE": "1"}, {"VV_PITCH_FORCE": "1", "VV_PITCH_ROWS": "1"}, {"VV_PITCH_FORCE": "1", "VV_FORCE_BIG": "1"}, {"VV_FORCE_BIG": "1"}],
-                         ids=["pitch", "pitch_rows", "pitch_big", "big"])
+@VO.layout_sweep
 def test_region_layouts(kind, nx, knobs, monkeypatch):
     """A re-pitched volume and the 64-bit addressing build, as test_label.py sweeps them.  The volume holds no zero: bin_min is 0 only if padding is
     read as data."""
-    VO.clear_env(monkeypatch, LAYOUT_KNOBS)
-    for k, v in knobs.items():
-        monkeypatch.setenv(k, v)
-    ny, nz = 11, 10
-    rng = np.random.default_rng(43)
-    vol = rng.integers(1, 256, (nz, ny, nx), dtype=np.uint8)
-    if kind == "f32":
-        vol = (vol.astype(f32) / f32(255)).astype(f32)
-    with vv.Context(0) as c:
-        c.load_volume(vol, TF)
-        if "VV_PITCH_FORCE" in knobs:
-            row = nx * vol.itemsize + 32
-            rows = ny + 1 if "VV_PITCH_ROWS" in knobs else ny
-            assert c.device_bytes()[0] == nz * rows * row + rows * row + 2 * row + 4096             # the volume is re-pitched
+    with VO.layout_context(kind, nx, knobs, monkeypatch, LAYOUT_KNOBS, TF) as (c, vol):
+        nz, ny, _ = vol.shape
         dev = RegionOut(vol.size, vol.size)
         for conn, bins, box in ((6, (1, 100), None), (18, (200, 255), ((1, 0, 1), (nx - 1, ny, nz - 1))), (26, (0, 40), None)):
             labels = LM.label(vol, bins, conn, box)[0]
@@ -607,21 +570,12 @@ def test_region_load_paths_and_streams(ctx, monkeypatch):
     """A volume that came from a device buffer and one promoted by the streamed upload; then label, distance and region calls enqueued on one torch
     stream, synchronised by the stream alone."""
     import torch
-    VO.clear_env(monkeypatch, LAYOUT_KNOBS)
-    ctx.reread_env()
     tdev = torch.device("cuda", 0)
     vol8 = _volume("u8:37x21x13")
-    nz, ny, nx = vol8.shape
     dev = RegionOut(vol8.size, vol8.size)
-    tt = torch.from_numpy(vol8.copy()).to(tdev)
-    ctx.load_volume_device(tt.data_ptr(), vv.VOXEL_U8, nx, ny, nz, TF)
-    torch.cuda.synchronize()
-    del tt
     labels = TL._want("u8:37x21x13", (0, 100), 18)[0]
-    _run_case(ctx, dev, "load_volume_device", vol8, labels, aux=labels)
-    promoted = (vol8.astype(f32) / f32(255)).astype(f32)
-    ctx.load_volume_streamed([(4, vol8[4:]), (0, vol8[:4])], vv.VOXEL_F32, nx, ny, nz, TF)
-    _run_case(ctx, dev, "streamed upload with promotion", promoted, labels, aux=labels)
+    for what, loaded in VO.load_paths(ctx, monkeypatch, LAYOUT_KNOBS, vol8, TF):
+        _run_case(ctx, dev, what, loaded, labels, aux=labels)
     # enqueue only
     _load(ctx, monkeypatch, "r70_u8")
     vol = _volume("r70_u8")
@@ -703,10 +657,7 @@ def test_region_errors_and_state(ctx, monkeypatch):
     vol = _volume("aniso")
     nz, ny, nx = vol.shape
     n = vol.size
-    cam = vv.Camera.orbit(3.0, 1.0, 0.6)
-    frame_before = ctx.render(57, 43, cam, fill=1)
-    hist_before = ctx.histogram()
-    state, dbytes, ms = ctx.layout_state(), ctx.device_bytes(), ctx.last_frame_ms()
+    before = VO.Untouched(ctx)
 
     # one buffer each on the host and on the device: labels | aux | compact | table (8 rows) | summary, GUARD apart
     L0, A0, C0 = 0, n * 4 + GUARD, 2 * (n * 4 + GUARD)
@@ -795,14 +746,6 @@ def test_region_errors_and_state(ctx, monkeypatch):
         for source in (0, 1):
             assert call(dp, 1, mk(source=source, max_regions=8)) == 0
 
-    calls()
-    torch.cuda.synchronize()
-    free_before = torch.cuda.mem_get_info(tdev)[0]
-    calls()
-    torch.cuda.synchronize()
-    assert torch.cuda.mem_get_info(tdev)[0] == free_before, "a device call changed the device's free memory"
+    VO.free_memory_unchanged(calls)
     # the context is still usable and untouched: volume, layout copies, residency, scratch, frame time, histogram, frames
-    assert ctx.layout_state() == state and ctx.device_bytes() == dbytes and ctx.last_frame_ms() == ms
-    TH._same(ctx.histogram(prefill=GARBAGE), hist_before, "the volume's histogram after the calls")
-    assert np.array_equal(ctx.render(57, 43, cam, fill=1), frame_before)
-    assert ctx.layout_state() == state and ctx.device_bytes() == dbytes
+    before.check()

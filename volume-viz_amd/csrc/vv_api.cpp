@@ -388,11 +388,83 @@ static int run_out_volumes(vv_context *c, const char *who, CallBuf *b, int n, vo
         if (t) (void)hipFree(t);
     return rc;
 }
+// The roles a buffer of such a list can have.  `p` may be NULL (an optional argument): the buffer is then empty, whatever `bytes` says.
+//   buf_in      data the kernels read
+//   buf_out     an output the kernels write whole
+//   buf_inout   an output whose unwritten part keeps the caller's bytes (a table with rows to spare; a volume worked on in place)
+//   buf_out_at  an output with a fixed home on the device (the stats / summary structs, which live in the call's scratch)
+static CallBuf buf_role(const void *p, size_t bytes, bool host, bool in, bool out, void *home)
+{
+    return {(void *)p, p ? bytes : 0, host, in, out, 0, home, nullptr};
+}
+static CallBuf buf_in(const void *p, size_t bytes, bool host) { return buf_role(p, bytes, host, true, false, nullptr); }
+static CallBuf buf_out(void *p, size_t bytes, bool host) { return buf_role(p, bytes, host, false, true, nullptr); }
+static CallBuf buf_inout(void *p, size_t bytes, bool host) { return buf_role(p, bytes, host, true, true, nullptr); }
+static CallBuf buf_out_at(void *p, size_t bytes, bool host, void *home) { return buf_role(p, bytes, host, false, true, home); }
+
 template <class Body>
 static int run_out_volume(vv_context *c, const char *who, void *out, size_t bytes, int out_on_device, bool in_place, void *stream, Body body)
 {
-    CallBuf b = {out, bytes, !out_on_device, in_place, true, 0, nullptr, nullptr};
+    CallBuf b = in_place ? buf_inout(out, bytes, !out_on_device) : buf_out(out, bytes, !out_on_device);
     return run_out_volumes(c, who, &b, 1, stream, [&](CallBuf *bb, hipStream_t st) { return body(bb[0].dev, st); });
+}
+
+// ---- the calls that take or produce word-per-voxel arrays over a box of the loaded volume: label, mask, distance, region table, mesh ----------
+// Their opening, in the order every one of them refuses in: the context, the descriptor and the other arguments that must not be NULL
+// (`args_given`), the loaded volume, the descriptor's box, its voxel count (at most 2^32 - 2).  Then A is zeroed and told the source: the
+// box's first voxel, the pitches, the voxel type, the extents b and -- where the kernels want it -- the origin lo.  Yields lo, hi and voxels.
+// (err_to: vv_mesh_dims has a const context.)
+struct CallBox { int lo[3], hi[3]; unsigned long long voxels; };
+template <class Args> static auto tell_origin(Args &A, const int lo[3], int) -> decltype((void)A.lo[0]) { for (int a = 0; a < 3; ++a) A.lo[a] = lo[a]; }
+template <class Args> static void tell_origin(Args &, const int *, long) {}
+
+template <class Desc, class Args>
+static int open_box_call(const vv_context *c, vv_context *err_to, const char *who, const Desc *d, bool args_given, Args &A, CallBox &B)
+{
+    const std::string w(who);
+    if (!c) return fail(nullptr, VV_ERR_INVALID, w + ": NULL context");
+    if (!d || !args_given) return fail(err_to, VV_ERR_INVALID, w + ": NULL argument");
+    if (!c->d_vol) return fail(err_to, VV_ERR_NO_VOLUME, w + ": no volume loaded");
+    const int dims[3] = {c->nx, c->ny, c->nz};
+    const int rc = check_box(err_to, who, d->box_lo, d->box_hi, dims, B.lo, B.hi);
+    if (rc) return rc;
+    memset(&A, 0, sizeof A);
+    for (int a = 0; a < 3; ++a) A.b[a] = (uint32_t)(B.hi[a] - B.lo[a]);
+    B.voxels = (unsigned long long)A.b[0] * A.b[1] * A.b[2];        // (each below 2^24: the product fits)
+    if (B.voxels > 0xFFFFFFFEull) return fail(err_to, VV_ERR_INVALID, w + ": the box may hold at most 2^32 - 2 voxels");
+    A.src0 = (const char *)c->d_vol + voxel_offset(c, B.lo[0], B.lo[1], B.lo[2]);
+    A.row_pitch = c->row_pitch; A.slice_pitch = c->slice_pitch;
+    A.src_type = c->vtype;
+    tell_origin(A, B.lo, 0);
+    return VV_OK;
+}
+// what these kernels' source addressing is promised: the box's last voxel lies inside the allocation, f32 voxels are aligned.  (A step of its own:
+// every call refuses it behind its argument checks.)
+static bool label_source_ok(const vv_context *c, const int hi[3])
+{
+    return box_end(c, hi) <= c->alloc_bytes && !(c->vtype == VV_VOXEL_F32 && (((uintptr_t)c->d_vol | c->row_pitch | c->slice_pitch) & 3) != 0);
+}
+static int check_bins(vv_context *c, const char *who, int bin_lo, int bin_hi)
+{
+    if (!(0 <= bin_lo && bin_lo <= bin_hi && bin_hi <= 255)) return fail(c, VV_ERR_INVALID, std::string(who) + ": bins must satisfy 0 <= bin_lo <= bin_hi <= 255");
+    return VV_OK;
+}
+
+// Overlap of device buffers.  A NULL range overlaps nothing; an empty one inside another still does (nonempty() makes it NULL where a call
+// lets it pass).  first_overlap: of a list whose first `outs` spans are outputs, the name of the first output that overlaps a span behind it
+// in the list -- a later output, an input, the loaded volume -- or null.
+static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+    return a && b && (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na;
+}
+struct Span { const void *p; size_t n; const char *name; };
+static Span nonempty(const void *p, size_t n, const char *name) { return {n ? p : nullptr, n, name}; }
+static const char *first_overlap(const Span *s, int outs, int n)
+{
+    for (int i = 0; i < outs; ++i)
+        for (int k = i + 1; k < n; ++k)
+            if (ranges_overlap(s[i].p, s[i].n, s[k].p, s[k].n)) return s[i].name;
+    return nullptr;
 }
 
 static int finalize_layout(vv_context *c, hipStream_t st);
@@ -2141,63 +2213,35 @@ int vv_resample_volume(vv_context *c, const vv_resample *r, void *out, size_t ca
 }
 
 // ---- segmentation (include/volviz.h: vv_label_volume, vv_mask_volume) ------------------------
-static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    return a && b && (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na;
-}
-// the box of a label / mask descriptor (lo, hi, extents b) and its voxel count, at most 2^32 - 2
-static int label_box(vv_context *c, const char *who, const int box_lo[3], const int box_hi[3], int lo[3], int hi[3], uint32_t b[3], unsigned long long *voxels)
-{
-    const int dims[3] = {c->nx, c->ny, c->nz};
-    const int rc = check_box(c, who, box_lo, box_hi, dims, lo, hi);
-    if (rc) return rc;
-    for (int a = 0; a < 3; ++a) b[a] = (uint32_t)(hi[a] - lo[a]);
-    *voxels = (unsigned long long)b[0] * b[1] * b[2];                // (each below 2^24: the product fits)
-    if (*voxels > 0xFFFFFFFEull) return fail(c, VV_ERR_INVALID, std::string(who) + ": the box may hold at most 2^32 - 2 voxels");
-    return VV_OK;
-}
-// what both kernels' source addressing is promised: the box's last voxel lies inside the allocation, f32 voxels are aligned
-static bool label_source_ok(const vv_context *c, const int hi[3])
-{
-    return box_end(c, hi) <= c->alloc_bytes && !(c->vtype == VV_VOXEL_F32 && (((uintptr_t)c->d_vol | c->row_pitch | c->slice_pitch) & 3) != 0);
-}
-
 int vv_label_volume(vv_context *c, const vv_label *d, uint32_t *labels, size_t capacity, uint32_t *sizes, vv_label_stats *stats, int out_on_device, void *stream)
 {
     static const char who[] = "vv_label_volume";
-    if (!c) return fail(nullptr, VV_ERR_INVALID, "vv_label_volume: NULL context");
-    if (!d || !labels) return fail(c, VV_ERR_INVALID, "vv_label_volume: NULL argument");
-    if (!c->d_vol) return fail(c, VV_ERR_NO_VOLUME, "vv_label_volume: no volume loaded");
-    // the header's rule 9, in its order
-    int lo[3], hi[3];
     LabelArgs A;
-    memset(&A, 0, sizeof A);
-    unsigned long long voxels;
-    int rc = label_box(c, who, d->box_lo, d->box_hi, lo, hi, A.b, &voxels);
+    CallBox B;
+    int rc = open_box_call(c, c, who, d, labels != nullptr, A, B);
     if (rc) return rc;
-    if (!(0 <= d->bin_lo && d->bin_lo <= d->bin_hi && d->bin_hi <= 255)) return fail(c, VV_ERR_INVALID, "vv_label_volume: bins must satisfy 0 <= bin_lo <= bin_hi <= 255");
+    // the header's rule 9, in its order
+    if ((rc = check_bins(c, who, d->bin_lo, d->bin_hi)) != VV_OK) return rc;
     if (d->connectivity != 6 && d->connectivity != 18 && d->connectivity != 26) return fail(c, VV_ERR_INVALID, "vv_label_volume: connectivity must be 6, 18 or 26");
-    const size_t bytes = (size_t)voxels * sizeof(uint32_t);
+    const size_t bytes = (size_t)B.voxels * sizeof(uint32_t);
     if (capacity < bytes) return fail(c, VV_ERR_INVALID, "vv_label_volume: capacity is below 4 bytes per voxel of the box");
     if (out_on_device) {
         if ((((uintptr_t)labels | (uintptr_t)sizes) & 3) != 0) return fail(c, VV_ERR_INVALID, "vv_label_volume: device labels and sizes must be 4-byte aligned");
         if (((uintptr_t)stats & 7) != 0) return fail(c, VV_ERR_INVALID, "vv_label_volume: a device stats must be 8-byte aligned");
+        // (by hand: the message names the pair, and the volume's comes first)
         if (ranges_overlap(labels, bytes, c->d_vol, c->alloc_bytes) || ranges_overlap(sizes, bytes, c->d_vol, c->alloc_bytes))
             return fail(c, VV_ERR_INVALID, "vv_label_volume: labels / sizes overlap the loaded volume");
         if (ranges_overlap(labels, bytes, sizes, bytes)) return fail(c, VV_ERR_INVALID, "vv_label_volume: labels and sizes overlap");
     }
-    if (((uintptr_t)c->d_vol & 15) != 0 || !label_source_ok(c, hi) || !c->scratch[SC_LABEL].p)
+    if (((uintptr_t)c->d_vol & 15) != 0 || !label_source_ok(c, B.hi) || !c->scratch[SC_LABEL].p)
         return fail(c, VV_ERR_DEVICE, "vv_label_volume: volume allocation is not what the kernel expects");
-    A.src0 = (const char *)c->d_vol + voxel_offset(c, lo[0], lo[1], lo[2]);
-    A.row_pitch = c->row_pitch; A.slice_pitch = c->slice_pitch;
-    A.bin_lo = (uint32_t)d->bin_lo; A.bin_hi = (uint32_t)d->bin_hi;
-    A.src_type = c->vtype; A.connectivity = d->connectivity;
+    A.bin_lo = (uint32_t)d->bin_lo; A.bin_hi = (uint32_t)d->bin_hi; A.connectivity = d->connectivity;
     A.counters = (unsigned long long *)c->scratch[SC_LABEL].p;
     const bool host = !out_on_device;
     CallBuf b[3] = {
-        {labels, bytes, host, false, true, 0, nullptr, nullptr},
-        {sizes, sizes ? bytes : 0, host, false, true, 0, nullptr, nullptr},
-        {stats, stats ? sizeof(vv_label_stats) : 0, host, false, true, 0, (char *)c->scratch[SC_LABEL].p + kLabelStatsOffset, nullptr},
+        buf_out(labels, bytes, host),
+        buf_out(sizes, bytes, host),
+        buf_out_at(stats, sizeof(vv_label_stats), host, (char *)c->scratch[SC_LABEL].p + kLabelStatsOffset),
     };
     return run_out_volumes(c, who, b, 3, stream, [&](CallBuf *bb, hipStream_t st) {
         A.labels = (uint32_t *)bb[0].dev; A.sizes = (uint32_t *)bb[1].dev; A.stats = (vv_label_stats *)bb[2].dev;
@@ -2210,16 +2254,11 @@ int vv_label_volume(vv_context *c, const vv_label *d, uint32_t *labels, size_t c
 int vv_mask_volume(vv_context *c, const vv_mask *m, const uint32_t *labels, const uint32_t *sizes, void *out, size_t capacity, int on_device, void *stream)
 {
     static const char who[] = "vv_mask_volume";
-    if (!c) return fail(nullptr, VV_ERR_INVALID, "vv_mask_volume: NULL context");
-    if (!m || !labels || !out) return fail(c, VV_ERR_INVALID, "vv_mask_volume: NULL argument");
-    if (!c->d_vol) return fail(c, VV_ERR_NO_VOLUME, "vv_mask_volume: no volume loaded");
-    // the header's rule M5, in its order
-    int lo[3], hi[3];
     MaskArgs A;
-    memset(&A, 0, sizeof A);
-    unsigned long long voxels;
-    int rc = label_box(c, who, m->box_lo, m->box_hi, lo, hi, A.b, &voxels);
+    CallBox B;
+    int rc = open_box_call(c, c, who, m, labels && out, A, B);
     if (rc) return rc;
+    // the header's rule M5, in its order
     if ((rc = check_out_type(c, who, m->out_type)) != VV_OK) return rc;
     if (m->keep != VV_KEEP_LABEL && m->keep != VV_KEEP_FOREGROUND && m->keep != VV_KEEP_MIN_SIZE)
         return fail(c, VV_ERR_INVALID, "vv_mask_volume: keep must be VV_KEEP_LABEL, VV_KEEP_FOREGROUND or VV_KEEP_MIN_SIZE");
@@ -2229,22 +2268,20 @@ int vv_mask_volume(vv_context *c, const vv_mask *m, const uint32_t *labels, cons
     const int ext[3] = {(int)A.b[0], (int)A.b[1], (int)A.b[2]};
     size_t bytes;
     if ((rc = check_out_volume(c, who, "", out, capacity, on_device, m->out_type, ext, true, &bytes)) != VV_OK) return rc;
-    const size_t lbytes = (size_t)voxels * sizeof(uint32_t);
+    const size_t lbytes = (size_t)B.voxels * sizeof(uint32_t);
     if (on_device) {
         if ((((uintptr_t)labels | (uintptr_t)sizes) & 3) != 0) return fail(c, VV_ERR_INVALID, "vv_mask_volume: device labels and sizes must be 4-byte aligned");
-        if (ranges_overlap(out, bytes, labels, lbytes) || ranges_overlap(out, bytes, sizes, lbytes))
-            return fail(c, VV_ERR_INVALID, "vv_mask_volume: out overlaps labels or sizes (the pass is not in place)");
+        const Span s[3] = {{out, bytes, "out"}, {labels, lbytes, "labels"}, {sizes, lbytes, "sizes"}};
+        if (first_overlap(s, 1, 3)) return fail(c, VV_ERR_INVALID, "vv_mask_volume: out overlaps labels or sizes (the pass is not in place)");
     }
-    if (!label_source_ok(c, hi)) return fail(c, VV_ERR_DEVICE, "vv_mask_volume: volume allocation is not what the kernel expects");
-    A.src0 = (const char *)c->d_vol + voxel_offset(c, lo[0], lo[1], lo[2]);
-    A.row_pitch = c->row_pitch; A.slice_pitch = c->slice_pitch;
-    A.src_type = c->vtype; A.out_type = m->out_type; A.keep = m->keep; A.invert = m->invert;
+    if (!label_source_ok(c, B.hi)) return fail(c, VV_ERR_DEVICE, "vv_mask_volume: volume allocation is not what the kernel expects");
+    A.out_type = m->out_type; A.keep = m->keep; A.invert = m->invert;
     A.label = m->label; A.min_size = m->min_size; A.fill = m->fill;
     const bool host = !on_device;
     CallBuf b[3] = {
-        {(void *)labels, lbytes, host, true, false, 0, nullptr, nullptr},
-        {(void *)sizes, sizes && m->keep == VV_KEEP_MIN_SIZE ? lbytes : 0, host, true, false, 0, nullptr, nullptr},    // (read under VV_KEEP_MIN_SIZE only)
-        {out, bytes, host, false, true, 0, nullptr, nullptr},
+        buf_in(labels, lbytes, host),
+        buf_in(sizes, m->keep == VV_KEEP_MIN_SIZE ? lbytes : 0, host),         // (read under VV_KEEP_MIN_SIZE only)
+        buf_out(out, bytes, host),
     };
     return run_out_volumes(c, who, b, 3, stream, [&](CallBuf *bb, hipStream_t st) {
         A.labels = (const uint32_t *)bb[0].dev; A.sizes = (const uint32_t *)bb[1].dev; A.out = bb[2].dev;
@@ -2257,22 +2294,17 @@ int vv_mask_volume(vv_context *c, const vv_mask *m, const uint32_t *labels, cons
 int vv_distance_volume(vv_context *c, const vv_distance *d, const uint32_t *labels, uint32_t *out, size_t capacity, int on_device, void *stream)
 {
     static const char who[] = "vv_distance_volume";
-    if (!c) return fail(nullptr, VV_ERR_INVALID, "vv_distance_volume: NULL context");
-    if (!d || !out) return fail(c, VV_ERR_INVALID, "vv_distance_volume: NULL argument");
-    if (!c->d_vol) return fail(c, VV_ERR_NO_VOLUME, "vv_distance_volume: no volume loaded");
-    // the header's rule 10, in its order
-    int lo[3], hi[3];
     DistanceArgs A;
-    memset(&A, 0, sizeof A);
-    unsigned long long voxels;
-    int rc = label_box(c, who, d->box_lo, d->box_hi, lo, hi, A.b, &voxels);
+    CallBox B;
+    int rc = open_box_call(c, c, who, d, out != nullptr, A, B);
     if (rc) return rc;
+    // the header's rule 10, in its order
     for (int a = 0; a < 3; ++a)
         if (A.b[a] > (uint32_t)VV_DISTANCE_MAX_EXTENT) return fail(c, VV_ERR_INVALID, "vv_distance_volume: every extent of the box must be at most 2048");
     if (d->seed != VV_SEED_BINS && d->seed != VV_SEED_LABEL && d->seed != VV_SEED_NONZERO)
         return fail(c, VV_ERR_INVALID, "vv_distance_volume: seed must be VV_SEED_BINS, VV_SEED_LABEL or VV_SEED_NONZERO");
     const bool bins = d->seed == VV_SEED_BINS;
-    if (bins && !(0 <= d->bin_lo && d->bin_lo <= d->bin_hi && d->bin_hi <= 255)) return fail(c, VV_ERR_INVALID, "vv_distance_volume: bins must satisfy 0 <= bin_lo <= bin_hi <= 255");
+    if (bins && (rc = check_bins(c, who, d->bin_lo, d->bin_hi)) != VV_OK) return rc;
     if (bins ? labels != nullptr : labels == nullptr) return fail(c, VV_ERR_INVALID, "vv_distance_volume: labels must be NULL for VV_SEED_BINS and given for the labels sources");
     if (d->invert != 0 && d->invert != 1) return fail(c, VV_ERR_INVALID, "vv_distance_volume: invert must be 0 or 1");
     for (int a = 0; a < 3; ++a)
@@ -2284,26 +2316,25 @@ int vv_distance_volume(vv_context *c, const vv_distance *d, const uint32_t *labe
             return fail(c, VV_ERR_INVALID, "vv_distance_volume: the largest squared distance of the box, sum of (spacing (extent - 1))^2, must be at most 0xFFFFFFFE");
     }
     if (d->out != VV_DIST_SQUARED && d->out != VV_DIST_WITHIN) return fail(c, VV_ERR_INVALID, "vv_distance_volume: out must be VV_DIST_SQUARED or VV_DIST_WITHIN");
-    const size_t bytes = (size_t)voxels * sizeof(uint32_t);
+    const size_t bytes = (size_t)B.voxels * sizeof(uint32_t);
     if (capacity < bytes) return fail(c, VV_ERR_INVALID, "vv_distance_volume: capacity is below 4 bytes per voxel of the box");
     const bool aliased = labels == out;
     if (on_device) {
         if ((((uintptr_t)labels | (uintptr_t)out) & 3) != 0) return fail(c, VV_ERR_INVALID, "vv_distance_volume: device labels and out must be 4-byte aligned");
+        // (by hand: out == labels is the one overlap that is allowed)
         if (ranges_overlap(out, bytes, c->d_vol, c->alloc_bytes)) return fail(c, VV_ERR_INVALID, "vv_distance_volume: out overlaps the loaded volume");
         if (!aliased && ranges_overlap(out, bytes, labels, bytes))
             return fail(c, VV_ERR_INVALID, "vv_distance_volume: out overlaps labels without being the same pointer");
     }
-    if (!label_source_ok(c, hi)) return fail(c, VV_ERR_DEVICE, "vv_distance_volume: volume allocation is not what the kernel expects");
-    A.src0 = (const char *)c->d_vol + voxel_offset(c, lo[0], lo[1], lo[2]);
-    A.row_pitch = c->row_pitch; A.slice_pitch = c->slice_pitch;
+    if (!label_source_ok(c, B.hi)) return fail(c, VV_ERR_DEVICE, "vv_distance_volume: volume allocation is not what the kernel expects");
     for (int a = 0; a < 3; ++a) A.spacing[a] = (uint32_t)d->spacing[a];
     A.bin_lo = (uint32_t)d->bin_lo; A.bin_hi = (uint32_t)d->bin_hi; A.label = d->label; A.within_r2 = d->within_r2;
-    A.src_type = c->vtype; A.seed = d->seed; A.invert = d->invert; A.mode = d->out;
+    A.seed = d->seed; A.invert = d->invert; A.mode = d->out;
     const bool host = !on_device;
     // out == labels: one buffer, uploaded and downloaded; else the labels (if any) are an input and out an output
     CallBuf b[2] = {
-        {out, bytes, host, aliased, true, 0, nullptr, nullptr},
-        {(void *)labels, labels && !aliased ? bytes : 0, host, true, false, 0, nullptr, nullptr},
+        aliased ? buf_inout(out, bytes, host) : buf_out(out, bytes, host),
+        buf_in(labels, aliased ? 0 : bytes, host),
     };
     return run_out_volumes(c, who, b, 2, stream, [&](CallBuf *bb, hipStream_t st) {
         A.out = (uint32_t *)bb[0].dev;
@@ -2318,46 +2349,37 @@ int vv_region_table(vv_context *c, const vv_regions *d, const uint32_t *labels, 
                     vv_region *table, size_t table_capacity, vv_region_summary *summary, int on_device, void *stream)
 {
     static const char who[] = "vv_region_table";
-    if (!c) return fail(nullptr, VV_ERR_INVALID, "vv_region_table: NULL context");
-    if (!d || !labels || !compact) return fail(c, VV_ERR_INVALID, "vv_region_table: NULL argument");
-    if (!c->d_vol) return fail(c, VV_ERR_NO_VOLUME, "vv_region_table: no volume loaded");
-    // the header's rule 8, in its order
-    int lo[3], hi[3];
     RegionArgs A;
-    memset(&A, 0, sizeof A);
-    unsigned long long voxels;
-    int rc = label_box(c, who, d->box_lo, d->box_hi, lo, hi, A.b, &voxels);
+    CallBox B;
+    const int rc = open_box_call(c, c, who, d, labels && compact, A, B);
     if (rc) return rc;
+    // the header's rule 8, in its order
     if (d->source != VV_REGION_LABELS && d->source != VV_REGION_NONZERO) return fail(c, VV_ERR_INVALID, "vv_region_table: source must be VV_REGION_LABELS or VV_REGION_NONZERO");
     if (!table && d->max_regions != 0) return fail(c, VV_ERR_INVALID, "vv_region_table: table is NULL with max_regions != 0");
-    const size_t bytes = (size_t)voxels * sizeof(uint32_t);
+    const size_t bytes = (size_t)B.voxels * sizeof(uint32_t);
     const unsigned long long tbytes = (unsigned long long)sizeof(vv_region) * d->max_regions;      // (below 2^40)
     if (compact_capacity < bytes) return fail(c, VV_ERR_INVALID, "vv_region_table: compact capacity is below 4 bytes per voxel of the box");
     if ((unsigned long long)table_capacity < tbytes) return fail(c, VV_ERR_INVALID, "vv_region_table: table capacity is below sizeof(vv_region) * max_regions");
     if (on_device) {
         if ((((uintptr_t)labels | (uintptr_t)aux | (uintptr_t)compact) & 3) != 0) return fail(c, VV_ERR_INVALID, "vv_region_table: device labels, aux and compact must be 4-byte aligned");
         if ((((uintptr_t)table | (uintptr_t)summary) & 7) != 0) return fail(c, VV_ERR_INVALID, "vv_region_table: a device table and summary must be 8-byte aligned");
-        if (ranges_overlap(compact, bytes, labels, bytes) || ranges_overlap(compact, bytes, aux, bytes) || ranges_overlap(compact, bytes, table, (size_t)tbytes) ||
-            ranges_overlap(compact, bytes, c->d_vol, c->alloc_bytes))
-            return fail(c, VV_ERR_INVALID, "vv_region_table: compact overlaps labels, aux, table or the loaded volume");
-        if (ranges_overlap(table, (size_t)tbytes, labels, bytes) || ranges_overlap(table, (size_t)tbytes, aux, bytes) || ranges_overlap(table, (size_t)tbytes, c->d_vol, c->alloc_bytes))
-            return fail(c, VV_ERR_INVALID, "vv_region_table: table overlaps labels, aux or the loaded volume");
+        // (the summary is not checked; a table without rows inside another buffer is refused like any other)
+        const Span s[5] = {{compact, bytes, "compact"}, {table, (size_t)tbytes, "table"}, {labels, bytes, nullptr}, {aux, bytes, nullptr}, {c->d_vol, c->alloc_bytes, nullptr}};
+        const char *name = first_overlap(s, 2, 5);
+        if (name) return fail(c, VV_ERR_INVALID, std::string("vv_region_table: ") + name + (name == s[0].name ? " overlaps labels, aux, table or the loaded volume" : " overlaps labels, aux or the loaded volume"));
     }
-    if (!label_source_ok(c, hi) || !c->scratch[SC_REGION].p) return fail(c, VV_ERR_DEVICE, "vv_region_table: volume allocation is not what the kernel expects");
-    A.src0 = (const char *)c->d_vol + voxel_offset(c, lo[0], lo[1], lo[2]);
-    A.row_pitch = c->row_pitch; A.slice_pitch = c->slice_pitch;
-    for (int a = 0; a < 3; ++a) A.lo[a] = lo[a];
-    A.max_regions = d->max_regions; A.src_type = c->vtype; A.source = d->source;
+    if (!label_source_ok(c, B.hi) || !c->scratch[SC_REGION].p) return fail(c, VV_ERR_DEVICE, "vv_region_table: volume allocation is not what the kernel expects");
+    A.max_regions = d->max_regions; A.source = d->source;
     char *sc = (char *)c->scratch[SC_REGION].p;
     A.hdr = (unsigned long long *)sc; A.partials = (uint32_t *)(sc + kRegionPartialsOffset);
     const bool host = !on_device;
     // (a host table goes up before it comes down: the rows the kernels do not write keep the caller's bytes)
     CallBuf b[5] = {
-        {(void *)labels, bytes, host, true, false, 0, nullptr, nullptr},
-        {(void *)aux, aux ? bytes : 0, host, true, false, 0, nullptr, nullptr},
-        {compact, bytes, host, false, true, 0, nullptr, nullptr},
-        {table, table ? (size_t)tbytes : 0, host, true, true, 0, nullptr, nullptr},
-        {summary, summary ? sizeof(vv_region_summary) : 0, host, false, true, 0, sc + kRegionSummaryOffset, nullptr},
+        buf_in(labels, bytes, host),
+        buf_in(aux, bytes, host),
+        buf_out(compact, bytes, host),
+        buf_inout(table, (size_t)tbytes, host),
+        buf_out_at(summary, sizeof(vv_region_summary), host, sc + kRegionSummaryOffset),
     };
     return run_out_volumes(c, who, b, 5, stream, [&](CallBuf *bb, hipStream_t st) {
         A.labels = (const uint32_t *)bb[0].dev; A.aux = aux ? (const uint32_t *)bb[1].dev : nullptr; A.compact = (uint32_t *)bb[2].dev;
@@ -2369,36 +2391,29 @@ int vv_region_table(vv_context *c, const vv_regions *d, const uint32_t *labels, 
 }
 
 // ---- surface meshes (include/volviz.h: vv_mesh_dims, vv_surface_mesh) ------------------------
-// The checks both calls share, rule 11 up to the site grid: the box (lo, hi, extents b) and the site grid's extents m.  A cap outside 0 / 1 is refused
+// What both calls share, rule 11 up to the site grid: the family's opening and the site grid's extents A.m.  A cap outside 0 / 1 is refused
 // further down (rule 11's order); the grid is measured with it as it stands only where it is 0 or 1.
-static int mesh_box(const vv_context *c, vv_context *err_to, const char *who, const vv_mesh *d, int lo[3], int hi[3], uint32_t b[3], uint32_t m[3])
+static int mesh_box(const vv_context *c, vv_context *err_to, const char *who, const vv_mesh *d, bool args_given, MeshArgs &A, CallBox &B)
 {
-    const std::string w(who);
-    if (!c->d_vol) return fail(err_to, VV_ERR_NO_VOLUME, w + ": no volume loaded");
-    const int dims[3] = {c->nx, c->ny, c->nz};
-    const int rc = check_box(err_to, who, d->box_lo, d->box_hi, dims, lo, hi);
+    const int rc = open_box_call(c, err_to, who, d, args_given, A, B);
     if (rc) return rc;
-    for (int a = 0; a < 3; ++a) b[a] = (uint32_t)(hi[a] - lo[a]);
-    if ((unsigned long long)b[0] * b[1] * b[2] > 0xFFFFFFFEull) return fail(err_to, VV_ERR_INVALID, w + ": the box may hold at most 2^32 - 2 voxels");
     const uint32_t pad = d->cap == 1 ? 2u : 0u;
-    for (int a = 0; a < 3; ++a) m[a] = b[a] - 1u + pad;
+    for (int a = 0; a < 3; ++a) A.m[a] = A.b[a] - 1u + pad;
     // (each extent is below 2^24 + 2: the product of two fits 64 bits, and the third is applied only to a product below 2^32)
-    const unsigned long long two = (unsigned long long)m[0] * m[1];
-    if (two > 0xFFFFFFFEull || two * m[2] > 0xFFFFFFFEull) return fail(err_to, VV_ERR_INVALID, w + ": the site grid may hold at most 2^32 - 2 sites");
+    const unsigned long long two = (unsigned long long)A.m[0] * A.m[1];
+    if (two > 0xFFFFFFFEull || two * A.m[2] > 0xFFFFFFFEull) return fail(err_to, VV_ERR_INVALID, std::string(who) + ": the site grid may hold at most 2^32 - 2 sites");
     return VV_OK;
 }
 
 int vv_mesh_dims(const vv_context *c, const vv_mesh *d, int out_dims[3])
 {
-    if (!c) return fail(nullptr, VV_ERR_INVALID, "vv_mesh_dims: NULL context");
     vv_context *e = const_cast<vv_context *>(c);                    // (the message alone)
-    if (!d || !out_dims) return fail(e, VV_ERR_INVALID, "vv_mesh_dims: NULL argument");
-    int lo[3], hi[3];
-    uint32_t b[3], m[3];
-    const int rc = mesh_box(c, e, "vv_mesh_dims", d, lo, hi, b, m);
+    MeshArgs A;
+    CallBox B;
+    const int rc = mesh_box(c, e, "vv_mesh_dims", d, out_dims != nullptr, A, B);
     if (rc) return rc;
     if (d->cap != 0 && d->cap != 1) return fail(e, VV_ERR_INVALID, "vv_mesh_dims: cap must be 0 or 1");
-    for (int a = 0; a < 3; ++a) out_dims[a] = (int)m[a];
+    for (int a = 0; a < 3; ++a) out_dims[a] = (int)A.m[a];
     return VV_OK;
 }
 
@@ -2407,19 +2422,15 @@ int vv_surface_mesh(vv_context *c, const vv_mesh *d, const uint32_t *labels, uin
                     vv_mesh_summary *summary, int on_device, void *stream)
 {
     static const char who[] = "vv_surface_mesh";
-    if (!c) return fail(nullptr, VV_ERR_INVALID, "vv_surface_mesh: NULL context");
-    if (!d) return fail(c, VV_ERR_INVALID, "vv_surface_mesh: NULL argument");
-    // the header's rule 11, in its order
-    int lo[3], hi[3];
     MeshArgs A;
-    memset(&A, 0, sizeof A);
-    int rc = mesh_box(c, c, who, d, lo, hi, A.b, A.m);
+    CallBox B;
+    int rc = mesh_box(c, c, who, d, true, A, B);
     if (rc) return rc;
+    // the header's rule 11, in its order
     if (d->source != VV_MESH_INDEX && d->source != VV_MESH_BINS && d->source != VV_MESH_LABEL && d->source != VV_MESH_NONZERO)
         return fail(c, VV_ERR_INVALID, "vv_surface_mesh: source must be VV_MESH_INDEX, VV_MESH_BINS, VV_MESH_LABEL or VV_MESH_NONZERO");
     if (d->source == VV_MESH_INDEX && !(1 <= d->level && d->level <= 255)) return fail(c, VV_ERR_INVALID, "vv_surface_mesh: level must lie in 1..255");
-    if (d->source == VV_MESH_BINS && !(0 <= d->bin_lo && d->bin_lo <= d->bin_hi && d->bin_hi <= 255))
-        return fail(c, VV_ERR_INVALID, "vv_surface_mesh: bins must satisfy 0 <= bin_lo <= bin_hi <= 255");
+    if (d->source == VV_MESH_BINS && (rc = check_bins(c, who, d->bin_lo, d->bin_hi)) != VV_OK) return rc;
     const bool from_labels = d->source == VV_MESH_LABEL || d->source == VV_MESH_NONZERO;
     if (from_labels ? labels == nullptr : labels != nullptr)
         return fail(c, VV_ERR_INVALID, "vv_surface_mesh: labels must be given for the labels sources and NULL for VV_MESH_INDEX and VV_MESH_BINS");
@@ -2432,43 +2443,36 @@ int vv_surface_mesh(vv_context *c, const vv_mesh *d, const uint32_t *labels, uin
     if ((unsigned long long)index_capacity < ibytes) return fail(c, VV_ERR_INVALID, "vv_surface_mesh: index capacity is below 4 bytes per site (vv_mesh_dims)");
     if ((unsigned long long)vertices_capacity < vbytes) return fail(c, VV_ERR_INVALID, "vv_surface_mesh: vertices capacity is below 16 bytes * max_vertices");
     if ((unsigned long long)quads_capacity < qbytes) return fail(c, VV_ERR_INVALID, "vv_surface_mesh: quads capacity is below 16 bytes * max_quads");
-    const size_t lbytes = from_labels ? (size_t)A.b[0] * A.b[1] * A.b[2] * sizeof(uint32_t) : 0;
-    const size_t nbytes = normals ? (size_t)vbytes : 0;
+    const size_t lbytes = (size_t)B.voxels * sizeof(uint32_t);        // (labels are NULL unless the source reads them)
     if (on_device) {
         if ((((uintptr_t)labels | (uintptr_t)index) & 3) != 0) return fail(c, VV_ERR_INVALID, "vv_surface_mesh: device labels and index must be 4-byte aligned");
         if ((((uintptr_t)vertices | (uintptr_t)normals | (uintptr_t)quads) & 15) != 0)
             return fail(c, VV_ERR_INVALID, "vv_surface_mesh: device vertices, normals and quads must be 16-byte aligned");
         if (((uintptr_t)summary & 7) != 0) return fail(c, VV_ERR_INVALID, "vv_surface_mesh: a device summary must be 8-byte aligned");
-        // every output against the input, the volume and the outputs behind it in the list
-        const void *ptr[7] = {index, vertices, normals, quads, summary, labels, c->d_vol};
-        const size_t len[7] = {(size_t)ibytes, vertices ? (size_t)vbytes : 0, nbytes, quads ? (size_t)qbytes : 0, summary ? sizeof(vv_mesh_summary) : 0, lbytes, c->alloc_bytes};
-        static const char *const name[5] = {"index", "vertices", "normals", "quads", "summary"};
-        for (int i = 0; i < 5; ++i)
-            for (int k = i + 1; k < 7; ++k)
-                if (len[i] && len[k] && ranges_overlap(ptr[i], len[i], ptr[k], len[k]))
-                    return fail(c, VV_ERR_INVALID, std::string("vv_surface_mesh: ") + name[i] + " overlaps another buffer of the call or the loaded volume");
+        // every output against the input, the volume and the outputs behind it in the list; a buffer without a record overlaps nothing
+        const Span s[7] = {nonempty(index, (size_t)ibytes, "index"), nonempty(vertices, (size_t)vbytes, "vertices"), nonempty(normals, (size_t)vbytes, "normals"),
+                           nonempty(quads, (size_t)qbytes, "quads"), {summary, sizeof(vv_mesh_summary), "summary"}, {labels, lbytes, nullptr}, {c->d_vol, c->alloc_bytes, nullptr}};
+        const char *name = first_overlap(s, 5, 7);
+        if (name) return fail(c, VV_ERR_INVALID, std::string("vv_surface_mesh: ") + name + " overlaps another buffer of the call or the loaded volume");
     }
     // what the kernels may read of [d_vol, d_vol + alloc_bytes): the box's voxels at the two pitches and nothing else (virtual voxels are clamped into
     // the box before they are addressed); f32 voxels are loaded as aligned words
-    if (!label_source_ok(c, hi) || !c->scratch[SC_MESH].p) return fail(c, VV_ERR_DEVICE, "vv_surface_mesh: volume allocation is not what the kernel expects");
-    A.src0 = (const char *)c->d_vol + voxel_offset(c, lo[0], lo[1], lo[2]);
-    A.row_pitch = c->row_pitch; A.slice_pitch = c->slice_pitch;
-    for (int a = 0; a < 3; ++a) A.lo[a] = lo[a];
+    if (!label_source_ok(c, B.hi) || !c->scratch[SC_MESH].p) return fail(c, VV_ERR_DEVICE, "vv_surface_mesh: volume allocation is not what the kernel expects");
     A.level = d->source == VV_MESH_INDEX ? (uint32_t)d->level : 1u;
     A.bin_lo = (uint32_t)d->bin_lo; A.bin_hi = (uint32_t)d->bin_hi; A.label = d->label;
     A.max_vertices = d->max_vertices; A.max_quads = d->max_quads;
-    A.src_type = c->vtype; A.source = d->source; A.cap = d->cap;
+    A.source = d->source; A.cap = d->cap;
     char *sc = (char *)c->scratch[SC_MESH].p;
     A.hdr = (unsigned long long *)sc; A.partials = (MeshPartial *)(sc + kMeshPartialsOffset);
     const bool host = !on_device;
     // (host tables go up before they come down: the records the kernels do not write keep the caller's bytes)
     CallBuf b[6] = {
-        {(void *)labels, lbytes, host, true, false, 0, nullptr, nullptr},
-        {index, (size_t)ibytes, host, false, true, 0, nullptr, nullptr},
-        {vertices, vertices ? (size_t)vbytes : 0, host, true, true, 0, nullptr, nullptr},
-        {normals, nbytes, host, true, true, 0, nullptr, nullptr},
-        {quads, quads ? (size_t)qbytes : 0, host, true, true, 0, nullptr, nullptr},
-        {summary, summary ? sizeof(vv_mesh_summary) : 0, host, false, true, 0, sc + kMeshSummaryOffset, nullptr},
+        buf_in(labels, lbytes, host),
+        buf_out(index, (size_t)ibytes, host),
+        buf_inout(vertices, (size_t)vbytes, host),
+        buf_inout(normals, (size_t)vbytes, host),
+        buf_inout(quads, (size_t)qbytes, host),
+        buf_out_at(summary, sizeof(vv_mesh_summary), host, sc + kMeshSummaryOffset),
     };
     return run_out_volumes(c, who, b, 6, stream, [&](CallBuf *bb, hipStream_t st) {
         A.labels = from_labels ? (const uint32_t *)bb[0].dev : nullptr; A.index = index ? (uint32_t *)bb[1].dev : nullptr;

@@ -448,6 +448,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.vv_set_layout_policy.argtypes = [vp, C.c_ulonglong, i]
     lib.vv_layout_state.argtypes = [vp, vp]
     lib.vv_volume_dims.argtypes = [vp, C.POINTER(i * 3), C.POINTER(i)]
+    # (the HIP runtime the library links: the working buffers of the composed calls, _DeviceBuffers)
+    lib.hipMalloc.argtypes, lib.hipFree.argtypes, lib.hipMemcpy.argtypes = [C.POINTER(vp), sz], [vp], [vp, vp, sz, i]
     for name in EXPORTS:
         if path is not None and name in _NEWER_EXPORTS and not hasattr(lib, name):
             continue
@@ -465,6 +467,74 @@ class VolvizError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"volviz error {code}: {msg}")
         self.code = code
+
+
+# ---- what the methods of the box-of-the-volume calls share ----
+def _set_box(d, box):
+    """box = ((x0, y0, z0), (x1, y1, z1)) or None = all of it (the descriptor's six zeros)."""
+    if box is not None:
+        d.box_lo[:] = [int(v) for v in box[0]]
+        d.box_hi[:] = [int(v) for v in box[1]]
+    return d
+
+
+def _set_bins(d, bins):
+    """bins = (bin_lo, bin_hi), both inclusive, or one bin."""
+    d.bin_lo, d.bin_hi = (int(bins), int(bins)) if np.isscalar(bins) else (int(bins[0]), int(bins[1]))
+
+
+def _words_like(a, shape, what):
+    """`a` as a contiguous uint32 array of the box's `shape` (None stays None); `what`: how the ValueError begins ("labels have")."""
+    if a is None:
+        return None
+    a = np.ascontiguousarray(a, np.uint32)
+    if a.shape != tuple(shape):
+        raise ValueError(f"{what} shape {a.shape}, the box has {tuple(shape)}")
+    return a
+
+
+def _prefill(byte, *objs):
+    """Every byte of the numpy arrays and ctypes structures `objs` becomes `byte`; a None byte or object is skipped."""
+    for o in objs if byte is not None else ():
+        if isinstance(o, np.ndarray):
+            o.view(np.uint8)[...] = byte
+        elif o is not None:
+            C.memset(C.byref(o), byte, C.sizeof(o))
+
+
+def _one_or_tuple(out):
+    return out[0] if len(out) == 1 else tuple(out)
+
+
+class _DeviceBuffers:
+    """The working buffers of a composed call (`who`, for the messages), as a context manager: alloc() on demand, upload() and download()
+    between them and host arrays, all of them freed on every way out.  VolvizError -4: no memory; -3: a copy failed."""
+
+    def __init__(self, lib, who):
+        self.lib, self.who, self.bufs = lib, who, []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        for p in self.bufs:
+            self.lib.hipFree(p)
+
+    def alloc(self, nbytes, what="a working buffer") -> int:
+        p = C.c_void_p()
+        if self.lib.hipMalloc(C.byref(p), max(int(nbytes), 8)) != 0 or not p.value:
+            raise VolvizError(-4, f"{self.who}: no device memory for {what}")
+        self.bufs.append(p)
+        return p.value
+
+    def upload(self, dev_ptr, a, what):
+        if self.lib.hipMemcpy(dev_ptr, a.ctypes.data, a.nbytes, 1) != 0:
+            raise VolvizError(-3, f"{self.who}: the upload of {what} failed")
+
+    def download(self, a, dev_ptr, what):
+        if a.nbytes and self.lib.hipMemcpy(a.ctypes.data, dev_ptr, a.nbytes, 2) != 0:
+            raise VolvizError(-3, f"{self.who}: the download of {what} failed")
+        return a
 
 
 def transfer_preset(preset: int) -> np.ndarray:
@@ -912,7 +982,7 @@ class Context:
         """vv_volume_histogram of the loaded volume, or of box = ((x0, y0, z0), (x1, y1, z1)), lo inclusive, hi exclusive, in voxels.
         `prefill`: the byte the output structure holds before the call (the result does not depend on it)."""
         out = vv_histogram()
-        C.memset(C.byref(out), prefill, C.sizeof(out))
+        _prefill(prefill, out)
         lo, hi = self._box(box)
         self._chk(self.lib.vv_volume_histogram(self.h, lo, hi, C.addressof(out), 0, None))
         return Histogram.from_bytes(out)
@@ -943,9 +1013,7 @@ class Context:
     # what the volume-to-volume calls share: the descriptor's box and output type, the output's extents, the host and the device call
     def _box_and_type(self, d, box, out_type):
         """box = ((x0, y0, z0), (x1, y1, z1)) or None = all of it (six zeros); out_type None = the volume's type."""
-        if box is not None:
-            d.box_lo[:] = [int(v) for v in box[0]]
-            d.box_hi[:] = [int(v) for v in box[1]]
+        _set_box(d, box)
         d.out_type = self.volume_type() if out_type is None else int(out_type)
         return d
 
@@ -961,8 +1029,7 @@ class Context:
     def _volume_to_host(self, call, d, dims, prefill) -> np.ndarray:
         """`call` (a vv_*_volume) into a new host array [bz, by, bx] of the descriptor's out_type, prefilled with the byte `prefill` unless None."""
         out = np.empty(tuple(dims)[::-1], np.float32 if d.out_type == VOXEL_F32 else np.uint8)
-        if prefill is not None:
-            out.view(np.uint8)[...] = prefill
+        _prefill(prefill, out)
         self._chk(call(self.h, C.byref(d), out.ctypes.data if out.size else None, out.nbytes, 0, None))
         return out
 
@@ -1070,11 +1137,8 @@ class Context:
     # vv_label_volume / vv_mask_volume (no reference counterpart)
     def _label(self, bins, connectivity, box) -> vv_label:
         """bins = (bin_lo, bin_hi), both inclusive, or one bin; box = ((x0, y0, z0), (x1, y1, z1)) or None = the whole volume."""
-        d = vv_label()
-        if box is not None:
-            d.box_lo[:] = [int(v) for v in box[0]]
-            d.box_hi[:] = [int(v) for v in box[1]]
-        d.bin_lo, d.bin_hi = (int(bins), int(bins)) if np.isscalar(bins) else (int(bins[0]), int(bins[1]))
+        d = _set_box(vv_label(), box)
+        _set_bins(d, bins)
         d.connectivity = int(connectivity)
         return d
 
@@ -1086,20 +1150,10 @@ class Context:
         labels = np.empty(shape, np.uint32)
         size_arr = np.empty(shape, np.uint32) if sizes else None
         st = vv_label_stats() if stats else None
-        if prefill is not None:
-            labels.view(np.uint8)[...] = prefill
-            if sizes:
-                size_arr.view(np.uint8)[...] = prefill
-            if stats:
-                C.memset(C.byref(st), prefill, C.sizeof(st))
+        _prefill(prefill, labels, size_arr, st)
         self._chk(self.lib.vv_label_volume(self.h, C.byref(d), labels.ctypes.data if labels.size else None, labels.nbytes,
                                            size_arr.ctypes.data if sizes else None, C.addressof(st) if stats else None, 0, None))
-        out = [labels]
-        if sizes:
-            out.append(size_arr)
-        if stats:
-            out.append(LabelStats.from_bytes(st))
-        return out[0] if len(out) == 1 else tuple(out)
+        return _one_or_tuple([labels] + ([size_arr] if sizes else []) + ([LabelStats.from_bytes(st)] if stats else []))
 
     def label_device(self, labels_ptr: int, capacity: int, bins, connectivity=6, box=None, sizes_ptr: int = 0, stats_ptr: int = 0, stream: int = 0):
         """vv_label_volume into device buffers (labels and sizes: `capacity` bytes each, 4-byte aligned; stats: 32 bytes, 8-byte aligned),
@@ -1118,17 +1172,11 @@ class Context:
         """vv_mask_volume with host labels (and sizes) [bz, by, bx] uint32 into a host array of the same shape, uint8 or float32: the volume's
         voxels where the test on the labels holds, `fill` elsewhere."""
         d = self._mask(keep, label, min_size, invert, fill, box, out_type)
-        dims = self._out_dims(d)
-        labels = np.ascontiguousarray(labels, np.uint32)
-        if labels.shape != tuple(dims)[::-1]:
-            raise ValueError(f"labels have shape {labels.shape}, the box has {tuple(dims)[::-1]}")
-        if sizes is not None:
-            sizes = np.ascontiguousarray(sizes, np.uint32)
-            if sizes.shape != labels.shape:
-                raise ValueError(f"sizes have shape {sizes.shape}, the box has {labels.shape}")
-        out = np.empty(labels.shape, np.float32 if d.out_type == VOXEL_F32 else np.uint8)
-        if prefill is not None:
-            out.view(np.uint8)[...] = prefill
+        shape = self._out_dims(d)[::-1]
+        labels = _words_like(labels, shape, "labels have")
+        sizes = _words_like(sizes, shape, "sizes have")
+        out = np.empty(shape, np.float32 if d.out_type == VOXEL_F32 else np.uint8)
+        _prefill(prefill, out)
         self._chk(self.lib.vv_mask_volume(self.h, C.byref(d), labels.ctypes.data, sizes.ctypes.data if sizes is not None else None,
                                           out.ctypes.data, out.nbytes, 0, None))
         return out
@@ -1160,13 +1208,10 @@ class Context:
         None = VV_DIST_SQUARED, an integer r^2 = VV_DIST_WITHIN."""
         if (bins is None) != bool(have_labels):
             raise ValueError("give either bins or labels")
-        d = vv_distance()
-        if box is not None:
-            d.box_lo[:] = [int(v) for v in box[0]]
-            d.box_hi[:] = [int(v) for v in box[1]]
+        d = _set_box(vv_distance(), box)
         if bins is not None:
             d.seed = SEED_BINS
-            d.bin_lo, d.bin_hi = (int(bins), int(bins)) if np.isscalar(bins) else (int(bins[0]), int(bins[1]))
+            _set_bins(d, bins)
         else:
             d.seed, d.label = (SEED_NONZERO, 0) if label is None else (SEED_LABEL, int(label))
         d.invert = int(bool(invert))
@@ -1180,13 +1225,9 @@ class Context:
         [bz, by, bx] that equal `label` (label None: that are not 0); `invert`: the others.  `prefill`: the byte the output holds before the call."""
         d = self._distance(bins, labels is not None, label, invert, spacing, box, within)
         shape = self._out_dims(d)[::-1]
-        if labels is not None:
-            labels = np.ascontiguousarray(labels, np.uint32)
-            if labels.shape != tuple(shape):
-                raise ValueError(f"labels have shape {labels.shape}, the box has {tuple(shape)}")
+        labels = _words_like(labels, shape, "labels have")
         out = np.empty(shape, np.uint32)
-        if prefill is not None:
-            out.view(np.uint8)[...] = prefill
+        _prefill(prefill, out)
         self._chk(self.lib.vv_distance_volume(self.h, C.byref(d), labels.ctypes.data if labels is not None else None,
                                               out.ctypes.data if out.size else None, out.nbytes, 0, None))
         return out
@@ -1215,19 +1256,11 @@ class Context:
         probe = self._distance(bins, labels is not None, label, False, spacing, box, r2)
         shape = self._out_dims(probe)[::-1]
         out = np.empty(shape, np.uint32)
-        if labels is not None:
-            labels = np.ascontiguousarray(labels, np.uint32)
-            if labels.shape != tuple(shape):
-                raise ValueError(f"labels have shape {labels.shape}, the box has {tuple(shape)}")
-        vp, lib = C.c_void_p, self.lib
-        lib.hipMalloc.argtypes, lib.hipFree.argtypes, lib.hipMemcpy.argtypes = [C.POINTER(vp), C.c_size_t], [vp], [vp, vp, C.c_size_t, C.c_int]
-        buf = vp()
-        if lib.hipMalloc(C.byref(buf), max(out.nbytes, 4)) != 0 or not buf.value:
-            raise VolvizError(-4, "morphology: no device memory for the working buffer")
-        try:
-            p = buf.value
-            if labels is not None and lib.hipMemcpy(p, labels.ctypes.data, labels.nbytes, 1) != 0:
-                raise VolvizError(-3, "morphology: the upload of the labels failed")
+        labels = _words_like(labels, shape, "labels have")
+        with _DeviceBuffers(self.lib, "morphology") as dev:
+            p = dev.alloc(out.nbytes, "the working buffer")
+            if labels is not None:
+                dev.upload(p, labels, "the labels")
             src = dict(bins=bins, label=label, labels_ptr=p if labels is not None else 0)
             again = dict(labels_ptr=p, invert=True)                 # the complement of what the buffer holds
             first_invert = op in (MORPH_ERODE, MORPH_OPEN)
@@ -1236,18 +1269,11 @@ class Context:
                 self.distance_device(p, out.nbytes, spacing=spacing, box=box, within=r2, **again)
             if op in (MORPH_ERODE, MORPH_CLOSE):
                 self.distance_device(p, out.nbytes, spacing=spacing, box=box, within=0, **again)
-            if lib.hipMemcpy(out.ctypes.data, p, out.nbytes, 2) != 0:
-                raise VolvizError(-3, "morphology: the download of the result failed")
-        finally:
-            lib.hipFree(buf)
-        return out
+            return dev.download(out, p, "the result")
 
     # vv_region_table (no reference counterpart)
     def _regions(self, source, box, max_regions) -> vv_regions:
-        d = vv_regions()
-        if box is not None:
-            d.box_lo[:] = [int(v) for v in box[0]]
-            d.box_hi[:] = [int(v) for v in box[1]]
+        d = _set_box(vv_regions(), box)
         d.source, d.max_regions = int(source), int(max_regions)
         return d
 
@@ -1262,29 +1288,16 @@ class Context:
             max_regions = int((flat == np.arange(1, flat.size + 1, dtype=np.uint64)).sum()) if source == REGION_LABELS else int(flat.any())
         d = self._regions(source, box, max_regions)
         shape = self._out_dims(d)[::-1]
-        if labels.shape != tuple(shape):
-            raise ValueError(f"labels have shape {labels.shape}, the box has {tuple(shape)}")
-        if aux is not None:
-            aux = np.ascontiguousarray(aux, np.uint32)
-            if aux.shape != labels.shape:
-                raise ValueError(f"aux has shape {aux.shape}, the box has {labels.shape}")
+        labels = _words_like(labels, shape, "labels have")
+        aux = _words_like(aux, shape, "aux has")
         table = np.zeros(int(max_regions), REGION_DTYPE)
         compact = np.empty(shape, np.uint32)
         st = vv_region_summary() if return_summary else None
-        if prefill is not None:
-            table.view(np.uint8)[...] = prefill
-            compact.view(np.uint8)[...] = prefill
-            if return_summary:
-                C.memset(C.byref(st), prefill, C.sizeof(st))
+        _prefill(prefill, table, compact, st)
         self._chk(self.lib.vv_region_table(self.h, C.byref(d), labels.ctypes.data, aux.ctypes.data if aux is not None else None,
                                            compact.ctypes.data, compact.nbytes, table.ctypes.data if max_regions else None, table.nbytes,
                                            C.addressof(st) if return_summary else None, 0, None))
-        out = [table]
-        if return_compact:
-            out.append(compact)
-        if return_summary:
-            out.append(RegionSummary.from_bytes(st))
-        return out[0] if len(out) == 1 else tuple(out)
+        return _one_or_tuple([table] + ([compact] if return_compact else []) + ([RegionSummary.from_bytes(st)] if return_summary else []))
 
     def regions_device(self, labels_ptr: int, compact_ptr: int, compact_capacity: int, table_ptr: int = 0, max_regions: int = 0, aux_ptr: int = 0,
                        summary_ptr: int = 0, source=REGION_LABELS, box=None, stream: int = 0):
@@ -1300,40 +1313,19 @@ class Context:
         `thickness` the squared distance of every foreground voxel to the background (distance of the labels, inverted, with the integer `spacing`)
         as aux; then regions with one row per component.  Only the label statistics (32 bytes, for the row count) and the table leave the device.
         region_properties(table, spacing) turns the rows into centroids, areas and radii."""
-        d = self._label(bins, connectivity, box)
-        voxels = int(np.prod(self._out_dims(d)))
-        nbytes = 4 * voxels
-        vp, lib = C.c_void_p, self.lib
-        lib.hipMalloc.argtypes, lib.hipFree.argtypes, lib.hipMemcpy.argtypes = [C.POINTER(vp), C.c_size_t], [vp], [vp, vp, C.c_size_t, C.c_int]
-        bufs = []
-
-        def alloc(n):
-            p = vp()
-            if lib.hipMalloc(C.byref(p), max(int(n), 8)) != 0 or not p.value:
-                raise VolvizError(-4, "measure: no device memory for a working buffer")
-            bufs.append(p)
-            return p.value
-
-        try:
-            lab, comp, st = alloc(nbytes), alloc(nbytes), alloc(32)
+        nbytes = 4 * int(np.prod(self._out_dims(self._label(bins, connectivity, box))))
+        with _DeviceBuffers(self.lib, "measure") as dev:
+            lab, comp, st = dev.alloc(nbytes), dev.alloc(nbytes), dev.alloc(32)
             self.label_device(lab, nbytes, bins, connectivity, box, stats_ptr=st)
-            raw = np.empty(32, np.uint8)
-            if lib.hipMemcpy(raw.ctypes.data, st, 32, 2) != 0:
-                raise VolvizError(-3, "measure: the download of the label statistics failed")
-            k = LabelStats.from_bytes(raw).components
+            k = LabelStats.from_bytes(dev.download(np.empty(32, np.uint8), st, "the label statistics")).components
             aux = 0
             if thickness:
-                aux = alloc(nbytes)
+                aux = dev.alloc(nbytes)
                 self.distance_device(aux, nbytes, invert=True, spacing=spacing, box=box, labels_ptr=lab)
             table = np.zeros(k, REGION_DTYPE)
-            tab = alloc(table.nbytes)
+            tab = dev.alloc(table.nbytes)
             self.regions_device(lab, comp, nbytes, tab if k else 0, k, aux_ptr=aux, box=box)
-            if k and lib.hipMemcpy(table.ctypes.data, tab, table.nbytes, 2) != 0:
-                raise VolvizError(-3, "measure: the download of the table failed")
-        finally:
-            for p in bufs:
-                lib.hipFree(p)
-        return table
+            return dev.download(table, tab, "the table")
 
     # vv_mesh_dims / vv_surface_mesh (no reference counterpart)
     def _mesh(self, level, bins, have_labels, label, cap, box, max_vertices=0, max_quads=0) -> vv_mesh:
@@ -1341,15 +1333,12 @@ class Context:
         (MESH_NONZERO)."""
         if (level is not None) + (bins is not None) + bool(have_labels) != 1:
             raise ValueError("give exactly one of level, bins and labels")
-        d = vv_mesh()
-        if box is not None:
-            d.box_lo[:] = [int(v) for v in box[0]]
-            d.box_hi[:] = [int(v) for v in box[1]]
+        d = _set_box(vv_mesh(), box)
         if level is not None:
             d.source, d.level = MESH_INDEX, int(level)
         elif bins is not None:
             d.source = MESH_BINS
-            d.bin_lo, d.bin_hi = (int(bins), int(bins)) if np.isscalar(bins) else (int(bins[0]), int(bins[1]))
+            _set_bins(d, bins)
         else:
             d.source, d.label = (MESH_NONZERO, 0) if label is None else (MESH_LABEL, int(label))
         d.cap, d.max_vertices, d.max_quads = int(cap), int(max_vertices), int(max_quads)
@@ -1368,11 +1357,8 @@ class Context:
         """vv_surface_mesh with host buffers: the surface-nets mesh of the voxels whose classification index is at least `level`, or lies in `bins`, or
         whose word of host `labels` [bz, by, bx] uint32 equals `label` (label None: is not 0).  cap: close the surface at the box's faces.  A
         count-only call, then the full call into exactly sized arrays."""
-        if labels is not None:
-            labels = np.ascontiguousarray(labels, np.uint32)
         d = self._mesh(level, bins, labels is not None, label, cap, box)
-        if labels is not None and labels.shape != tuple(self._out_dims(d)[::-1]):
-            raise ValueError(f"labels have shape {labels.shape}, the box has {tuple(self._out_dims(d)[::-1])}")
+        labels = _words_like(labels, self._out_dims(d)[::-1], "labels have")
         lp = labels.ctypes.data if labels is not None else None
         st = vv_mesh_summary()
         self._chk(self.lib.vv_surface_mesh(self.h, C.byref(d), lp, None, 0, None, 0, None, None, 0, C.addressof(st), 0, None))
